@@ -8,6 +8,7 @@ One step = forward + CE + KL*seq_len/len(train_data) + backward + gradient all-r
 + global-norm clip + SGD, nothing skipped.  Prints ONE JSON line on rank 0.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs   (+ what the last timed step computed, .npy)
     python bench.py --gpus N ...        (starts its own N ranks: a torch.distributed.run child process, before
                                          this process has touched the GPU; the child's JSON line and exit code are
                                          relayed)
@@ -81,7 +82,40 @@ def parse():
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launch plumbing only (spawn, rendezvous, barrier, max-over-ranks, one JSON line from rank 0) "
                          "with NO GPU work: what the CPU-side test of `--gpus N` self-launch runs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="rank 0 writes what the LAST timed step computed to DIR/<name>.npy (float32), right after the timed "
+                         "region: loss and kl as Trainer.step returns them, and a fixed, seeded sample of the updated parameters "
+                         "and of the gradient buffer (DUMP_SAMPLE elements each).  Same arguments -> same inputs, so two builds "
+                         "can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22  # elements per sampled buffer: 16 MB each in float32, well under the 64 MB of a dump
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, loss, kl, flat):
+    """What the timed path handed its caller in the last step: `loss`, `kl` (Trainer.step's return values) and the model's
+    state after it -- a seeded sample of the flat parameter buffer and of the flat gradient buffer (the same indices for both;
+    they depend only on DUMP_SEED and the parameter count).  -> total bytes written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = min(DUMP_SAMPLE, flat.total)
+    idx = np.sort(np.random.RandomState(DUMP_SEED).choice(flat.total, size=n, replace=False))
+    idx_dev = torch.from_numpy(idx).to(flat.flat_param.device)
+    arrays = {"loss": loss.detach().float().reshape(1),
+              "kl": (kl.detach().float().reshape(1) if kl is not None else torch.zeros(1)),
+              "params_sample": flat.flat_param.index_select(0, idx_dev).float(),
+              "grads_sample": flat.flat_grad.index_select(0, idx_dev).float()}
+    total = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return total
 
 
 ERROR_LINE_KEYS = ("metric", "value", "unit", "n_gpus", "error", "last_stage")
@@ -1310,10 +1344,13 @@ def main():
     timer = ops.KernelTimer(only={"sampled_gemm_fwd"}) if side_tags else ops.KernelTimer()
     timer_all = ops.KernelTimer()
 
+    last = {}
+
     def one(i, timed):
         data, targets = get_batch(train, i * T, T)
         ops.set_kernel_timer(timed)
         loss, kl, _ = tr.step(data, targets, kl_fn=kl_fn)
+        last["kl"] = kl
         return loss
 
     busbw = None
@@ -1362,6 +1399,9 @@ def main():
         every = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         replicas_identical = all(bool(torch.equal(e, every[0])) for e in every)
+    if args.dump_outputs and rank == 0:  # before anything else steps the model (comm A/B legs, opt-in modes)
+        nbytes = dump_outputs(args.dump_outputs, loss, last["kl"], tr.flat)
+        sys.stderr.write("[bench] last timed step's outputs: %.1f MB in %s\n" % (nbytes / 2**20, args.dump_outputs))
     final_loss = float(loss)
     if world > 1:
         # outside the timed region, every rank: per-bucket brackets of one more step, then the A/B legs (overlap off; comm-window

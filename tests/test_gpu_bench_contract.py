@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,12 +14,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.skipif(os.environ.get("BLM_GEMM_MODE", "f32") not in ("", "f32"),
                     reason="the contract line is the fp32 parity mode's; an opt-in GEMM mode relabels dtype / gemm_mode")
-def test_bench_prints_one_json_line_with_the_contract_fields():
+def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-                        "--no-opt-in", "--no-extra"], capture_output=True, text=True, timeout=900, env=env)
+                        "--no-opt-in", "--no-extra", "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -38,4 +40,9 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     sr = out["step_roofline"]  # whole step: SURVEY 8(d) model FLOPs per token over the measured step time
     assert sr["model_flops_per_token"] == 294838272 and sr["peak"] == 157.3
     assert abs(sr["achieved"] - 294838272 * out["value"] / 1e12) < 0.01 * sr["achieved"] and abs(sr["frac"] - sr["achieved"] / 157.3) < 1e-3
+    # --dump-outputs: the last timed step's loss / kl and the parameter / gradient samples, float32, finite
+    dump = {k: np.load(str(tmp_path / "dump" / (k + ".npy"))) for k in ("loss", "kl", "params_sample", "grads_sample")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in dump.values())
+    assert sum(v.nbytes for v in dump.values()) <= 64 << 20 and dump["params_sample"].shape == dump["grads_sample"].shape
+    assert abs(float(dump["loss"][0]) - out["final_loss"]) < 1e-3
     assert out["value"] > 2.0e5  # a silent fallback (vendor / eager path) or a broken kernel shows up here

@@ -449,6 +449,31 @@ def test_bench_extra_legs_of_a_multi_rank_run_cannot_cost_the_headline(hang):
         assert r.returncode == 0 and "extra_configs" not in out and "headline ok; extra legs" not in r.stderr
 
 
+
+def test_bench_dump_outputs_writes_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: loss, kl and the same seeded sample of the parameter and gradient buffers, float32,
+    under 64 MB, identical from call to call; `--steps` below 1 is refused before any work."""
+    import importlib
+    import types
+    monkeypatch.delenv("HSA_ENABLE_IPC_MODE_LEGACY", raising=False)  # bench.py sets it on import; undone after the test
+    bench = importlib.import_module("bench")
+    n = bench.DUMP_SAMPLE + 12345
+    flat = types.SimpleNamespace(total=n, flat_param=torch.arange(n, dtype=torch.float32),
+                                 flat_grad=-torch.arange(n, dtype=torch.float32))
+    nbytes = bench.dump_outputs(str(tmp_path / "a"), torch.tensor(5.5), torch.tensor(0.25), flat)
+    bench.dump_outputs(str(tmp_path / "b"), torch.tensor(5.5), None, flat)
+    assert nbytes <= 64 << 20
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("loss", "kl", "params_sample", "grads_sample")}
+    assert all(v.dtype == np.float32 for v in got.values()) and sum(v.nbytes for v in got.values()) == nbytes
+    assert got["loss"].tolist() == [5.5] and got["kl"].tolist() == [0.25]
+    p = got["params_sample"]
+    assert p.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(p) > 0) and np.array_equal(got["grads_sample"], -p)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "params_sample.npy")), p)
+    assert np.load(str(tmp_path / "b" / "kl.npy")).tolist() == [0.0]
+    r, _ = _bench(["--steps", "0"], timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
 def test_init_distributed_is_bounded_and_checks_its_first_all_reduce(monkeypatch):
     """engine.init_distributed hands init_process_group a timeout (BLM_DIST_TIMEOUT_S / argument / 180 s) instead of torch's
     10-30 minutes: a rank whose peers never come raises inside it."""
