@@ -10,6 +10,7 @@ import argparse
 import math
 import os
 from collections import OrderedDict
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -156,10 +157,11 @@ def _interp_decoder(model, model_2, alpha):
     return dec
 
 
-def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, alpha, rows=None):
+def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, alpha, rows=None, decoder_input=False):
     """Per-token NLL of a padded batch of hypotheses (all columns start from the same state): (T, N), or -- with
     ``rows`` (flat indices t*N + n of the real tokens) -- one value per selected row, the decoder being applied to those
-    rows only (model._ProjHolder.rows)."""
+    rows only (model._ProjHolder.rows).  ``decoder_input`` (one model, with ``rows``): the decoder's input rows (R, K)
+    instead, for a decoder launch over several passes at once (ops.linear_mc_stats)."""
     from . import ops
     import contextlib
     # Transformers whose operations outside the attention core are all token-wise keep ONLY the real tokens' rows through
@@ -172,7 +174,7 @@ def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, 
     # one model: the decoder returns the NLL itself, its (rows, V) logits are never stored (ops.linear_nll); two models
     # interpolate LOGITS (reference :163) and keep the materialised pair + the two-input CE kernel
     fused = (model_2 is None and _FUSED_NLL and not torch.is_grad_enabled() and hasattr(model.decoder, "nll_targets")
-             and ops.linear_nll_supported(model.decoder.weight, model.decoder.bias))
+             and ops.linear_nll_supported(model.decoder.weight, model.decoder.bias) and not decoder_input)
     # two models: the reference interpolates LOGITS (:163); alpha (x1 W1^T + b1) + (1 - alpha) (x2 W2^T + b2) is one product
     # over packed operands, so one decoder + cross-entropy launch takes both and no logits are stored (ops.linear_nll_interp)
     fused2 = (model_2 is not None and _FUSED_NLL and not torch.is_grad_enabled()
@@ -181,6 +183,8 @@ def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, 
                                                   model_2.decoder.bias))
     if fused:
         model.decoder.nll_targets = target_flat
+    if decoder_input:
+        model.decoder.return_input = True
     if fused2:
         model.decoder.return_input = model_2.decoder.return_input = True
     try:
@@ -192,6 +196,8 @@ def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, 
             out2 = None
             if model_2 is not None:
                 out2 = model_2(data) if model_type == 'Transformer' else model_2(data, hidden_2)[0]
+        if decoder_input:
+            return out.reshape(-1, out.shape[-1])
         if fused:
             nll = out
         elif fused2:
@@ -206,6 +212,8 @@ def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, 
                 m.decoder.rows = None
         if fused:
             model.decoder.nll_targets = None
+        if decoder_input:
+            model.decoder.return_input = False
         if fused2:
             model.decoder.return_input = model_2.decoder.return_input = False
     return nll if rows is not None else nll.view(data.shape[0], data.shape[1])
@@ -261,8 +269,17 @@ def _carry_chain(model, stream_ids, offs, hidden, max_tokens=8192):
     return carries
 
 
+class HypUncertainty(NamedTuple):
+    """Uncertainty of one hypothesis under S Monte-Carlo weight samples (compute_scores_batched(uncertainty=True)).  The per-token
+    arrays run over exactly the targets the score sums; definitions in include/bayeslm.h (blm_linear_mc_stats)."""
+    bma_nll: np.ndarray    # NLL of each target under the sample-averaged distribution
+    h_pred: np.ndarray     # predictive entropy of the sample-averaged distribution
+    mi: np.ndarray         # mutual information between the prediction and the weights (epistemic part); h_pred - mi = E_s H[p_s]
+    sent_logp_std: float   # population std over the samples of the sentence log-probability -NLL_s
+
+
 def compute_scores_batched(nbest, model, vocab, model_type, device, model_2=None, alpha=0.0, mc_samples=0, seed=1111,
-                           batch_tokens=None):
+                           batch_tokens=None, uncertainty=False):
     """the N hypotheses of an utterance are padded into ONE (T_max, N) batch instead
     of N separate launches.  Exact for causal Transformers (padding sits after every real token) and
     for LSTMs (all hypotheses of an utterance start from the same carried state; the carry is the state after
@@ -275,7 +292,11 @@ def compute_scores_batched(nbest, model, vocab, model_type, device, model_2=None
     S passes with the variational weights sampled (dropout off) and the sentence PROBABILITIES
     averaged, score = -log(mean_s exp(-NLL_s)).  Sample s is ONE model for the whole n-best list: its
     eps comes from Philox step s of every variational tensor's stream (seed, tensor id, step = s), so the scores do not
-    depend on how utterances are packed into batches; an LSTM's carried state stays the mean-weight one."""
+    depend on how utterances are packed into batches; an LSTM's carried state stays the mean-weight one.
+
+    uncertainty=True (new, needs mc_samples >= 2 and one model): each sample's pass hands back its decoder input rows and ONE
+    decoder launch per batch over all S of them (ops.linear_mc_stats) gives the per-sample NLLs -- the scores follow from them by
+    the formula above -- and the token-level uncertainty: returns (scores, unc), unc[key] = [(hyp, HypUncertainty)]."""
     # The loop builds hundreds of thousands of short-lived, acyclic Python objects (token lists, views); the cyclic collector's
     # full passes over them stall the host while the GPU waits -- 20000 hypotheses: 177 ms with the collector off against
     # 190-225 ms with it on (the first call of a process, with a small heap, hides it).  Off for the duration of the call.
@@ -283,13 +304,18 @@ def compute_scores_batched(nbest, model, vocab, model_type, device, model_2=None
     gc_was = gc.isenabled()
     gc.disable()
     try:
-        return _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, alpha, mc_samples, seed, batch_tokens)
+        return _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, alpha, mc_samples, seed, batch_tokens,
+                                       uncertainty)
     finally:
         if gc_was:
             gc.enable()
 
 
-def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, alpha, mc_samples, seed, batch_tokens):
+def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, alpha, mc_samples, seed, batch_tokens, uncertainty):
+    if uncertainty and (int(mc_samples) < 2 or model_2 is not None):
+        raise BayesLMError("uncertainty needs --mc-samples >= 2 and one model (got %d samples%s)"
+                           % (int(mc_samples), ", two models" if model_2 is not None else ""))
+    unc = OrderedDict()
     model.eval()
     if model_2 is not None:
         model_2.eval()
@@ -351,34 +377,63 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
                 h2N = tuple(torch.cat([hidden_2[u][i].expand(-1, c, -1) for u, c in enumerate(counts)], 1).contiguous()
                             for i in (0, 1))
         sent = []
+        xs = []
         for smp in range(S):
             if mc_samples > 0:
                 model.set_step(smp)
+            if uncertainty:
+                xs.append(_batch_nll(model, data, d_tsel, model_type, hN, None, None, alpha, rows=d_sel, decoder_input=True))
+                continue
             nll = _batch_nll(model, data, d_tsel, model_type, hN, model_2, h2N, alpha, rows=d_sel)  # (R,)
             run = torch.cumsum(nll.double(), 0)
             hi = run[d_ends - 1]
             sent.append((hi - torch.cat([hi.new_zeros(1), hi[:-1]])).float())
+        stats = None
+        if uncertainty:  # one decoder launch over the S passes' rows: per-sample NLLs and the token-level uncertainty
+            from . import ops
+            if not mc_dec:  # the decoder padded once for this scoring run (its weights do not change during it)
+                mc_dec.append(ops.McDecoder(model.decoder.weight, model.decoder.bias))
+            st = ops.linear_mc_stats(torch.stack(xs), model.decoder.weight, model.decoder.bias, d_tsel, dec=mc_dec[0])
+            del xs
+            for smp in range(S):
+                run = torch.cumsum(st.nll_s[:, smp].double(), 0)
+                hi = run[d_ends - 1]
+                sent.append((hi - torch.cat([hi.new_zeros(1), hi[:-1]])).float())
+            stats = (torch.stack([st.bma_nll, st.h_pred, st.mi]), torch.stack(sent).double().std(0, unbiased=False), d_ends)
         if S == 1:
             tot = sent[0]
         else:
             tot = -(torch.logsumexp(-torch.stack(sent), 0) - torch.log(torch.tensor(float(S), device=device)))
         # the scores stay on the device: no host sync per batch (the LSTM path launches one small batch per
         # utterance); they are read back together in flush()
-        pending.append((group, tot))
+        pending.append((group, tot, stats))
         if len(pending) >= 1024:
             flush()
 
     pending = []
+    mc_dec = []  # uncertainty: ops.McDecoder of this run, dropped with it
 
     def flush():
         if not pending:
             return
-        flat = torch.cat([t for _, t in pending]).tolist()
+        flat = torch.cat([t for _, t, _ in pending]).tolist()
         o = 0
-        for group, _ in pending:
+        for group, _, stats in pending:
+            o0 = o
             for key, hyps, ps in group:
                 scores[key] = [(h, float(v)) for h, v in zip(hyps, flat[o:o + len(hyps)])]
                 o += len(hyps)
+            if stats is not None:
+                tok, std, ends = (t.cpu().numpy() for t in stats)
+                n = 0
+                for key, hyps, ps in group:
+                    lst = []
+                    for h in hyps:
+                        a, b = (ends[n - 1] if n else 0), ends[n]
+                        lst.append((h, HypUncertainty(tok[0, a:b].copy(), tok[1, a:b].copy(), tok[2, a:b].copy(), float(std[n]))))
+                        n += 1
+                    unc[key] = lst
+                assert n == o - o0
         pending.clear()
 
     try:
@@ -390,7 +445,7 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
             model.eval()
             for m in raised:
                 m.sample = False
-    return scores
+    return (scores, unc) if uncertainty else scores
 
 
 def _score_all(nbest, model, model_2, vocab, device, is_rnn, hidden, hidden_2, batch_tokens, score_group, flush):
@@ -434,6 +489,17 @@ def write_scores(scores, path):
         for key, lst in scores.items():
             for idx, (_, s) in enumerate(lst, 1):
                 f.write('%s %.4f\n' % ('-'.join([key, str(idx)]), s))
+
+
+def write_uncertainty(scores, unc, path):
+    """--write-uncertainty: one line per hypothesis in the score file's order, no header:
+    key-n score sent_logp_std sum_bma_nll sum_h_pred sum_mi n_tokens (the score as write_scores prints it, the rest %.6g)."""
+    with open(path, 'w', encoding='utf-8') as f:
+        for key, lst in scores.items():
+            for idx, ((_, s), (_, u)) in enumerate(zip(lst, unc[key]), 1):
+                f.write('%s %.4f %.6g %.6g %.6g %.6g %d\n' % ('-'.join([key, str(idx)]), s, u.sent_logp_std, float(np.sum(u.bma_nll, dtype=np.float64)),
+                                                             float(np.sum(u.h_pred, dtype=np.float64)), float(np.sum(u.mi, dtype=np.float64)),
+                                                             len(u.mi)))
 
 
 def interpolate_scores(nolm_path, lmonly_path, nn_path, nnweight, out_path):
@@ -494,6 +560,9 @@ def build_parser():
     p.add_argument('--batched', type=int, default=1, help='1: all hypotheses of an utterance in one padded batch; '
                    '0: one launch per hypothesis like the reference')
     p.add_argument('--mc-samples', type=int, default=0, help='S > 0: average sentence probabilities over S weight samples')
+    p.add_argument('--write-uncertainty', type=str, default='', metavar='PATH',
+                   help='with --mc-samples >= 2 (one model): per hypothesis "key-n score sent_logp_std sum_bma_nll sum_h_pred sum_mi '
+                   'n_tokens" -- the token-level predictive entropy, mutual information (epistemic part) and model-average NLL summed')
     p.add_argument('--batch-tokens', type=int, default=0, help='padded tokens per batch across utterances (0: 16384 for Transformers, 8192 for LSTMs)')
     p.add_argument('--gemm-mode', type=str, default='f32', choices=['f32', 'bf16x6', 'bf16x3'],
                    help='opt-in split-bf16 arithmetic of the GEMM family (DESIGN.md section 7); default fp32 MFMA')
@@ -523,6 +592,9 @@ def job_device_index(job, n_devices, local_rank=0):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.write_uncertainty and (args.mc_samples < 2 or args.interpolation_flag != 0):
+        raise SystemExit("--write-uncertainty needs --mc-samples >= 2 and --interpolation_flag 0 (got --mc-samples %d, "
+                         "--interpolation_flag %d)" % (args.mc_samples, args.interpolation_flag))
     for pth, what in ((args.nbest_list, "Nbest list"), (args.vocabulary, "Vocabulary"), (args.model_path, "Model")):
         assert os.path.exists(pth), "%s path does not exists." % what
     if not torch.cuda.is_available():
@@ -543,11 +615,16 @@ def main(argv=None):
     nbest = load_nbest(args.nbest_list)
     if args.batched or args.mc_samples > 0:
         scores = compute_scores_batched(nbest, model_1, vocab, args.model, device, model_2, args.inter_alpha, args.mc_samples,
-                                        batch_tokens=args.batch_tokens)
+                                        batch_tokens=args.batch_tokens, uncertainty=bool(args.write_uncertainty))
+        if args.write_uncertainty:
+            scores, unc = scores
     else:
         scores = compute_scores(nbest, model_1, vocab, args.model, device, model_2, args.inter_alpha)
     write_scores(scores, args.outfile)
     print("Write to %s" % args.outfile)
+    if args.write_uncertainty:
+        write_uncertainty(scores, unc, args.write_uncertainty)
+        print("Write to %s" % args.write_uncertainty)
     if args.interp_out:
         interpolate_scores(args.interp_nolm, args.interp_lmonly, args.outfile, args.interp_nnweight, args.interp_out)
         print("Write to %s" % args.interp_out)

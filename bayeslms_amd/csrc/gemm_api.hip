@@ -84,6 +84,7 @@ extern "C" int blm_gemm(const blm_gemm_args* a, void* stream) {
         return blm_fail(BLM_ERR_INVALID, "blm_gemm: var_c row window outside W");
       break;
     case BLM_EPI_CE_PART: return blm_fail(BLM_ERR_INVALID, "blm_gemm: BLM_EPI_CE_PART is internal to blm_linear_nll");
+    case BLM_EPI_MC_PART: return blm_fail(BLM_ERR_INVALID, "blm_gemm: BLM_EPI_MC_PART is internal to blm_linear_mc_stats");
     default: return blm_fail(BLM_ERR_INVALID, "blm_gemm: unknown epilogue");
   }
   const bool samp = a->var_b.lgstd != nullptr;
@@ -156,13 +157,11 @@ extern "C" int64_t blm_linear_nll_ws_floats(int M, int N) {
   return (int64_t)2 * M * ((N + 63) / 64) + M;  // [M][column tiles][2] partials (64-column tiles at most) + the target logits
 }
 
-extern "C" int blm_linear_nll(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
-                              float* nll, float* lse, float* ws, int M, int N, int K, void* stream) {
-  if (M < 0 || N <= 0 || K <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll: bad shape");
-  if (M == 0) return BLM_OK;
-  if (!x || !w || !tgt || !nll || !ws || ldx < K || ldw < K) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll: bad arguments");
-  if (N % 4 != 0 || !aligned16(ws) || (bias && !aligned16(bias)))
-    return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll: needs N %% 4 == 0 and 16-byte aligned bias / workspace");
+namespace {
+// The decoder launch of blm_linear_nll and of both passes of blm_linear_mc_stats: the NT product over M rows x N columns, one K
+// slice (the softmax epilogues cannot take atomics), the opt-in GEMM mode, the plan of the shape, and the column tiles it runs.
+GemmP decoder_params(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* ws, int M, int N, int K,
+                     int* gn) {
   blm_gemm_args a{};
   a.abi_version = BLM_ABI_VERSION;
   a.op = BLM_GEMM_NT; a.M = M; a.N = N; a.K = K;
@@ -171,10 +170,9 @@ extern "C" int blm_linear_nll(const float* x, int64_t ldx, const float* w, int64
   GemmP p{};
   p.M = M; p.N = N; p.K = K;
   p.A = x; p.lda = (int)ldx; p.B = w; p.ldb = (int)ldw; p.C = ws; p.ldc = N;
-  p.alpha = 1.f; p.epi = BLM_EPI_CE_PART;
+  p.alpha = 1.f;
   p.bias = bias; p.aux = ws;
-  p.ce_tgt = reinterpret_cast<const long long*>(tgt);
-  p.ce_tlogit = ws + (int64_t)2 * M * ((N + 63) / 64);
+  p.ce_nv = N;
   p.split = blm_get_gemm_mode() == BLM_GEMM_MODE_BF16X3 ? 3 : (blm_get_gemm_mode() == BLM_GEMM_MODE_BF16X6 ? 6 : 0);
   p.a_vec = aligned16(x) && (ldx % 4 == 0);
   p.b_vec = aligned16(w) && (ldw % 4 == 0);
@@ -185,17 +183,117 @@ extern "C" int blm_linear_nll(const float* x, int64_t ldx, const float* w, int64
   p.plan_tile = (key.fast != 0) == (p.fast != 0) ? pl.tile : 11;
   p.plan_splits = 1;
   p.plan_cus = pl.cus;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  // column tiles of the launch: 64 columns on tiles 11 / 21 (and on the guarded 64x64 kernel), 128 otherwise
+  const int tile = p.fast ? p.plan_tile : 11;
+  const int bn = (tile == 11 || tile == 21) ? 64 : 128;
+  *gn = (N + bn - 1) / bn;
+  return p;
+}
+
+// CE_PART launch + fold: nll (and lse) of every row; row r's target is tgt[r >> row_shift], columns >= nv are padding
+int linear_nll_launch(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt, int row_shift,
+                      int nv, float* nll, float* lse, float* ws, int M, int N, int K, hipStream_t st) {
+  int gn = 0;
+  GemmP p = decoder_params(x, ldx, w, ldw, bias, ws, M, N, K, &gn);
+  p.epi = BLM_EPI_CE_PART;
+  p.ce_tgt = reinterpret_cast<const long long*>(tgt);
+  p.ce_tlogit = ws + (int64_t)2 * M * ((N + 63) / 64);
+  p.ce_nv = nv;
+  p.ce_row_shift = row_shift;
   // the target's logit is written by the one lane whose column window holds it: a target outside [0, N) (a padding id, -1)
   // would leave its slot uninitialised -- every slot starts as NaN, so such a row's NLL is NaN, not garbage
   BLM_HIP(hipMemsetAsync(p.ce_tlogit, 0xFF, (size_t)M * sizeof(float), st));
   const int rc = launch_op<BLM_GEMM_NT, false>(p, st);
   if (rc) return rc;
-  // column tiles of the launch: 64 columns on tiles 11 / 21 (and on the guarded 64x64 kernel), 128 otherwise
-  const int tile = p.fast ? p.plan_tile : 11;
-  const int bn = (tile == 11 || tile == 21) ? 64 : 128;
-  const int gn = (N + bn - 1) / bn;
   hipLaunchKernelGGL(ce_part_finish_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ws, p.ce_tlogit, nll, lse, M, gn);
+  BLM_HIP(hipGetLastError());
+  return BLM_OK;
+}
+}  // namespace
+
+extern "C" int blm_linear_nll(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
+                              float* nll, float* lse, float* ws, int M, int N, int K, void* stream) {
+  if (M < 0 || N <= 0 || K <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll: bad shape");
+  if (M == 0) return BLM_OK;
+  if (!x || !w || !tgt || !nll || !ws || ldx < K || ldw < K) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll: bad arguments");
+  if (N % 4 != 0 || !aligned16(ws) || (bias && !aligned16(bias)))
+    return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll: needs N %% 4 == 0 and 16-byte aligned bias / workspace");
+  return linear_nll_launch(x, ldx, w, ldw, bias, tgt, 0, N, nll, lse, ws, M, N, K, static_cast<hipStream_t>(stream));
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Token-level predictive uncertainty of S Monte-Carlo weight samples (include/bayeslm.h: definition; no reference counterpart).
+// Rows m * Sp + s of x are sample s of token m.  Pass 1 is blm_linear_nll's launch over all M * Sp rows (lse and nll per row);
+// pass 2 runs the same product again with the MC_PART epilogue, which reads lse back and leaves two partials per (token, column
+// tile); the fold below sums a token's tiles in a fixed order and forms bma_nll from the S per-sample NLLs.
+namespace blm {
+__global__ __launch_bounds__(256) void mc_stats_finish_kernel(const float* __restrict__ part, const float* __restrict__ nll_rows,
+                                                              float* __restrict__ nll_s, float* __restrict__ bma, float* __restrict__ h_pred,
+                                                              float* __restrict__ mi, int M, int S, int sh, int gn) {
+  const int tok = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (tok >= M) return;
+  const float* p = part + (long)tok * gn * 2;
+  float hs = 0.f, ms = 0.f;
+  for (int j = lane; j < gn; j += 64) { hs += p[2 * j]; ms += p[2 * j + 1]; }
+  hs = wave_sum(hs);
+  ms = wave_sum(ms);
+  // bma_nll = -log((1/S) sum_s exp(-nll_s)) with the largest -nll_s taken out; a NaN (target outside [0, V)) propagates
+  const float nl = lane < S ? nll_rows[((long)tok << sh) + lane] : 0.f;
+  if (nll_s && lane < S) nll_s[(long)tok * S + lane] = nl;
+  const float a = wave_max(lane < S ? -nl : -INFINITY);
+  const float e = wave_sum(lane < S ? __expf(-nl - a) : 0.f);
+  if (lane == 0) {
+    bma[tok] = -(a + (__logf(e) - __logf((float)S)));
+    h_pred[tok] = -hs;
+    mi[tok] = ms / (float)S;
+  }
+}
+}  // namespace blm
+
+extern "C" int64_t blm_linear_mc_stats_ws_floats(int M, int S, int V) {
+  if (S < 1 || S > 64 || V <= 0) return 0;
+  int sp = 1;
+  while (sp < S) sp *= 2;
+  const long R = (long)M * sp;
+  if (!blm::extents_ok({M, V}) || !blm::extents_ok({R, V})) return 0;
+  const int64_t lin = blm_linear_nll_ws_floats((int)R, (V + 3) / 4 * 4);
+  return lin ? lin + 2 * R : 0;  // blm_linear_nll's workspace over M * Sp rows (pass 2's partials reuse it), nll and lse per row
+}
+
+extern "C" int blm_linear_mc_stats(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
+                                   int S, float* nll_s, float* bma_nll, float* h_pred, float* mi, float* ws, int M, int V, int K,
+                                   void* stream) {
+  if (M < 0 || V <= 0 || K <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_stats: bad shape");
+  if (S < 1 || S > 64) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_stats: S must be in 1..64");
+  if (!bma_nll || !h_pred || !mi) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_stats: null output");
+  if (!x || !w || !tgt || !ws) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_stats: null operand");
+  if (ldx < K || ldw < K) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_stats: leading dimension too small");
+  int sh = 0;
+  while ((1 << sh) < S) ++sh;
+  const long R = (long)M << sh;
+  const int Np = (V + 3) / 4 * 4;
+  if (!blm::extents_ok({R, ldx}) || !blm::extents_ok({Np, ldw}) || !blm::extents_ok({R, Np}))
+    return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_stats: extents too large");
+  if (!aligned16(ws) || (bias && !aligned16(bias)))
+    return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_mc_stats: needs 16-byte aligned bias / workspace");
+  if (M == 0) return BLM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rows = (int)R;
+  float* nll_rows = ws + blm_linear_nll_ws_floats(rows, Np);
+  float* lse_rows = nll_rows + R;
+  int rc = linear_nll_launch(x, ldx, w, ldw, bias, tgt, sh, V, nll_rows, lse_rows, ws, rows, Np, K, st);
+  if (rc) return rc;
+  int gn = 0;
+  GemmP p = decoder_params(x, ldx, w, ldw, bias, ws, rows, Np, K, &gn);
+  p.epi = BLM_EPI_MC_PART;
+  p.ce_nv = V;
+  p.ce_row_shift = sh;
+  p.mc_lse = lse_rows;
+  p.mc_s = S;
+  rc = launch_op<BLM_GEMM_NT, false>(p, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(mc_stats_finish_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ws, nll_rows, nll_s, bma_nll, h_pred, mi, M, S, sh, gn);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

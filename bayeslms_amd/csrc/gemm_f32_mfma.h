@@ -52,6 +52,12 @@ struct GemmP {
   // exp(logit - maximum) go to aux[(row * gn + tile) * 2 + {0, 1}], the target's logit to ce_tlogit[row]
   const long long* ce_tgt;
   float* ce_tlogit;
+  int ce_nv;         // CE_PART / MC_PART: columns >= ce_nv are vocabulary padding and enter no statistic (= N for blm_linear_nll)
+  int ce_row_shift;  // CE_PART: row r's target is ce_tgt[r >> ce_row_shift]; MC_PART: rows come in token groups of 1 << ce_row_shift
+  // BLM_EPI_MC_PART (blm_linear_mc_stats): per (token group, column tile) sum_v pbar log pbar and sum_s sum_v p (log p - log pbar)
+  // go to aux[(token * gn + tile) * 2 + {0, 1}]; mc_lse = the log-sum-exp of every row (the CE_PART pass), mc_s = real samples
+  const float* mc_lse;
+  int mc_s;
   int tail_from;             // tiles (in launch order) below this index are computed whole by one workgroup; only the rest -- the
                              // tiles beyond the last full round of workgroup slots -- are sliced (0: every tile is sliced)
   // fused activation dropout
@@ -585,7 +591,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmP& p, f32x16 (&acc)[WTM]
   const int col = n0 + c4;
   const bool accum = p.flags & BLM_GEMM_ACCUMULATE;
   float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (EPI == BLM_EPI_BIAS || EPI == BLM_EPI_BIAS_GELU || EPI == BLM_EPI_GP_MIX || EPI == BLM_EPI_CE_PART)
+  if constexpr (EPI == BLM_EPI_BIAS || EPI == BLM_EPI_BIAS_GELU || EPI == BLM_EPI_GP_MIX || EPI == BLM_EPI_CE_PART || EPI == BLM_EPI_MC_PART)
     if (col < p.N && p.bias) bias = *reinterpret_cast<const float4*>(p.bias + col);
 #pragma unroll
   for (int pass = 0; pass < NP; ++pass) {
@@ -604,12 +610,19 @@ __device__ __forceinline__ void epilogue_rows(const GemmP& p, f32x16 (&acc)[WTM]
     __syncthreads();
     if constexpr (EPI == BLM_EPI_CE_PART) {
       // every lane of a row takes part in the row's reductions (lanes past N carry -inf): TPRW consecutive lanes hold one row
-      const bool valid = col < p.N;  // N % 4 == 0: a lane's four columns are all inside or all outside
+      const bool valid = col < p.ce_nv;  // N % 4 == 0: a lane's four columns are all inside or all outside N
+      // the quad that holds the last of ce_nv < N columns (blm_linear_mc_stats over a vocabulary padded to 4): its padding -> -inf
+      const bool part = valid && col + 4 > p.ce_nv;
       for (int lr = t / TPRW; lr < 64; lr += RPS) {
         const int row = m0 + 64 * pass + lr;
         if (row >= p.M) break;  // uniform over the lanes of a row
         float4 v = *reinterpret_cast<const float4*>(stage + lr * SS + c4);
         v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w;
+        if (part) {
+          if (col + 1 >= p.ce_nv) v.y = -INFINITY;
+          if (col + 2 >= p.ce_nv) v.z = -INFINITY;
+          v.w = -INFINITY;
+        }
         float m = valid ? fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)) : -INFINITY;
 #pragma unroll
         for (int o = TPRW / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -621,8 +634,67 @@ __device__ __forceinline__ void epilogue_rows(const GemmP& p, f32x16 (&acc)[WTM]
           d[0] = m;
           d[1] = sum;
         }
-        const long long tg = p.ce_tgt[row];
-        if (valid && tg >= col && tg < col + 4) p.ce_tlogit[row] = tg == col ? v.x : (tg == col + 1 ? v.y : (tg == col + 2 ? v.z : v.w));
+        const long long tg = p.ce_tgt[row >> p.ce_row_shift];
+        if (valid && tg >= col && tg < col + 4 && tg < p.ce_nv) p.ce_tlogit[row] = tg == col ? v.x : (tg == col + 1 ? v.y : (tg == col + 2 ? v.z : v.w));
+      }
+    } else if constexpr (EPI == BLM_EPI_MC_PART) {
+      // 64 staged rows = 64 >> ce_row_shift whole token groups (the group size divides 64, m0 is a multiple of 64).  A lane takes
+      // (token group, its 4 columns) and walks the group's samples twice: r = max_s log p[s, v], then w_s = exp(log p[s, v] - r).
+      // With W = sum_s w_s and L = log(W / S):  pbar = e^r W / S,  log pbar = r + L  and  sum_s p_s (log p_s - log pbar) =
+      // e^r (sum_s w_s u_s - L W), u_s = log p_s - r -- one exp per element, one log per column and group; identical samples give
+      // u = 0, W = S, L = 0: exactly zero.  Padding samples (s >= mc_s) and padding columns (>= ce_nv) are never read / masked.
+      // From Sp = 16 on there are fewer groups (64 >> sh) than row slots (RPS): the idle slots wait on the busy ones, pass 2 / pass 1
+      // = 0.95 / 0.96 / 1.02 / 1.12 at S = 8 / 16 / 32 / 64 (profiles/r06_mc_uncertainty_probe.txt); not split across slots.
+      const int sh = p.ce_row_shift, S = p.mc_s;
+      const float logS = __logf((float)S);
+      const bool valid = col < p.ce_nv;
+      const bool in1 = col + 1 < p.ce_nv, in2 = col + 2 < p.ce_nv, in3 = col + 3 < p.ce_nv;
+      for (int g = t / TPRW; g < (64 >> sh); g += RPS) {
+        const int row0 = m0 + 64 * pass + (g << sh);
+        if (row0 >= p.M) break;  // uniform over the lanes of a group
+        float hs = 0.f, ms = 0.f;
+        if (valid) {
+          const float* z = stage + (g << sh) * SS + c4;
+          const float* lse = p.mc_lse + row0;
+          float4 r = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+          for (int s = 0; s < S; ++s) {
+            const float4 v = *reinterpret_cast<const float4*>(z + s * SS);
+            const float l = lse[s];
+            r.x = fmaxf(r.x, v.x + bias.x - l); r.y = fmaxf(r.y, v.y + bias.y - l);
+            r.z = fmaxf(r.z, v.z + bias.z - l); r.w = fmaxf(r.w, v.w + bias.w - l);
+          }
+          float4 sw = make_float4(0.f, 0.f, 0.f, 0.f), su = sw;
+          for (int s = 0; s < S; ++s) {
+            const float4 v = *reinterpret_cast<const float4*>(z + s * SS);
+            const float l = lse[s];
+            const float ux = v.x + bias.x - l - r.x, uy = v.y + bias.y - l - r.y, uz = v.z + bias.z - l - r.z, uw = v.w + bias.w - l - r.w;
+            const float wx = __expf(ux), wy = __expf(uy), wz = __expf(uz), ww = __expf(uw);
+            sw.x += wx; sw.y += wy; sw.z += wz; sw.w += ww;
+            su.x = fmaf(wx, ux, su.x); su.y = fmaf(wy, uy, su.y); su.z = fmaf(wz, uz, su.z); su.w = fmaf(ww, uw, su.w);
+          }
+          const float invS = 1.f / S;
+          auto col_terms = [&](float rr, float W, float U, bool in) {
+            const float L = __logf(W) - logS, er = __expf(rr);
+            if (in) {
+              hs = fmaf(er * W * invS, rr + L, hs);
+              ms = fmaf(er, fmaf(-L, W, U), ms);
+            }
+          };
+          col_terms(r.x, sw.x, su.x, true);
+          col_terms(r.y, sw.y, su.y, in1);
+          col_terms(r.z, sw.z, su.z, in2);
+          col_terms(r.w, sw.w, su.w, in3);
+        }
+#pragma unroll
+        for (int o = TPRW / 2; o > 0; o >>= 1) {
+          hs += __shfl_xor(hs, o, 64);
+          ms += __shfl_xor(ms, o, 64);
+        }
+        if (t % TPRW == 0) {
+          float* d = p.aux + ((long)(row0 >> sh) * p.gn + n0 / BN) * 2;
+          d[0] = hs;
+          d[1] = ms;
+        }
       }
     } else if (col < p.N) {
       auto keep4 = [&](int row) {  // dropout keep factors of this lane's 4 consecutive columns: one Philox block
@@ -1278,6 +1350,9 @@ __global__ __launch_bounds__(128 * WGN, WGN == 2 ? 2 : 1) void gemm_f32_kernel(c
       case BLM_EPI_GP_MIX: epilogue_rows<BLM_EPI_GP_MIX, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return;
       case BLM_EPI_MUL_DGP_MIX: epilogue_rows<BLM_EPI_MUL_DGP_MIX, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return;
       case BLM_EPI_CE_PART: epilogue_rows<BLM_EPI_CE_PART, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return;
+      case BLM_EPI_MC_PART:  // blm_linear_mc_stats launches NT products only
+        if constexpr (OP == BLM_GEMM_NT) { epilogue_rows<BLM_EPI_MC_PART, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return; }
+        break;
       default: break;
     }
   }
@@ -1338,8 +1413,9 @@ static int launch_cfg(const GemmP& p, hipStream_t st) {
     const bool al = ((reinterpret_cast<uintptr_t>(p.C) | reinterpret_cast<uintptr_t>(p.aux) | reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.C2)) & 15) == 0;
     q.vec_epi = (!q.atomic || q.tail_from > 0) && al && p.N % 4 == 0 && p.ldc % 4 == 0 &&
                 (p.epi == BLM_EPI_NONE || p.epi == BLM_EPI_BIAS || p.epi == BLM_EPI_BIAS_GELU || p.epi == BLM_EPI_MUL_DGELU ||
-                 p.epi == BLM_EPI_GP_MIX || p.epi == BLM_EPI_MUL_DGP_MIX || p.epi == BLM_EPI_CE_PART);
-    if (p.epi == BLM_EPI_CE_PART && !q.vec_epi) return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll: needs N % 4 == 0 and 16-byte aligned bias / workspace");
+                 p.epi == BLM_EPI_GP_MIX || p.epi == BLM_EPI_MUL_DGP_MIX || p.epi == BLM_EPI_CE_PART || p.epi == BLM_EPI_MC_PART);
+    if ((p.epi == BLM_EPI_CE_PART || p.epi == BLM_EPI_MC_PART) && !q.vec_epi)
+      return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll: needs N % 4 == 0 and 16-byte aligned bias / workspace");
   }
   if (q.atomic && !(p.flags & BLM_GEMM_ACCUMULATE))
     BLM_HIP(hipMemsetAsync(p.C, 0, (size_t)p.M * p.N * sizeof(float), st));

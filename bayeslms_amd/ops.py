@@ -15,6 +15,7 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -1332,6 +1333,85 @@ def linear_nll(x, weight, bias, targets):
     check(lib().blm_linear_nll(ptr(x2), x2.stride(0), ptr(weight), weight.stride(0), ptr(bias), ptr(tgt), ptr(nll), None, ptr(ws),
                                M, V, K, stream()), "blm_linear_nll")
     return nll
+
+
+class McStats(NamedTuple):
+    """Per-token uncertainty of S Monte-Carlo weight samples (include/bayeslm.h, blm_linear_mc_stats)."""
+    nll_s: torch.Tensor    # (M, S) NLL of the target under each sample
+    bma_nll: torch.Tensor  # (M,) NLL of the target under the sample-averaged distribution pbar
+    h_pred: torch.Tensor   # (M,) predictive entropy H[pbar]
+    mi: torch.Tensor       # (M,) mutual information between prediction and weights, mean_s KL(p_s || pbar); H[pbar] - mi = E_s H[p_s]
+
+
+def _mc_pad(weight, bias):
+    """(weight, bias) as blm_linear_mc_stats takes them: Np = V rounded up to 4 rows, contiguous, 16-byte aligned -- the tensors
+    themselves when they are, else a copy onto zero padding rows."""
+    V, K = weight.shape
+    if V % 4 == 0 and weight.is_contiguous() and weight.data_ptr() % 16 == 0 and (
+            bias is None or (bias.is_contiguous() and bias.data_ptr() % 16 == 0)):
+        return weight, bias
+    Np = (V + 3) // 4 * 4
+    wp = torch.zeros(Np, K, device=weight.device, dtype=torch.float32)
+    wp[:V] = weight
+    bp = None
+    if bias is not None:
+        bp = torch.zeros(Np, device=weight.device, dtype=torch.float32)
+        bp[:V] = bias
+    return wp, bp
+
+
+class McDecoder:
+    """The padded decoder of a run of linear_mc_stats calls over FIXED weights (one scoring run), built once and passed as ``dec``
+    to each call, as InterpDecoder is for the two-model launch.  It holds the source tensors and the caller scopes it to the run:
+    a copy made here is not refreshed when the weights change, so it must not outlive the run."""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight, bias
+        self.wp, self.bp = _mc_pad(_f32(weight, "weight"), None if bias is None else _f32(bias, "bias"))
+
+
+def linear_mc_stats(x, weight, bias, targets, S=None, dec=None):
+    """Inference only: token-level predictive uncertainty of S Monte-Carlo weight samples without materialising any of the
+    S x M x V logits (blm_linear_mc_stats: two decoder products whose epilogues keep per-tile partials, and a folding kernel).
+    ``x``: (S, M, K), sample-major as the S forward passes produce it; ``weight`` (V, K), ``bias`` (V,) or None, ``targets`` (M,).
+    ``dec``: McDecoder(weight, bias) of the run, reused instead of padding the vocabulary (V % 4 != 0) again per call.
+    -> McStats(nll_s (M, S), bma_nll, h_pred, mi (M,)); definitions in include/bayeslm.h."""
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        raise BayesLMError("linear_mc_stats is an inference-only path (no backward): call it under torch.no_grad()")
+    if dec is not None and (dec.weight is not weight or dec.bias is not bias):
+        raise ValueError("linear_mc_stats: dec was built for another decoder")
+    x = _f32(x, "x")
+    if x.dim() != 3:
+        raise ValueError("linear_mc_stats: x must be (S, M, K)")
+    S_, M, K = x.shape
+    if S is not None and int(S) != S_:
+        raise ValueError("linear_mc_stats: S = %d but x holds %d samples" % (S, S_))
+    S = S_
+    if not 1 <= S <= 64:
+        raise BayesLMError("linear_mc_stats: 1..64 samples, got %d" % S)
+    weight = _f32(weight, "weight")
+    if weight.dim() != 2 or weight.shape[1] != K or targets.numel() != M or (bias is not None and bias.numel() != weight.shape[0]):
+        raise ValueError("linear_mc_stats: x (S, M, K), weight (V, K), bias (V,) and M targets expected")
+    if bias is not None:
+        bias = _f32(bias, "bias")
+    L.require_gfx950()
+    V = weight.shape[0]
+    wp, bp = (dec.wp, dec.bp) if dec is not None else _mc_pad(weight, bias)
+    tgt = dev_tensor(targets.reshape(-1), "targets", torch.int64)
+    dev = x.device
+    nll_s = torch.empty(M, S, device=dev, dtype=torch.float32)
+    bma, h, mi = (torch.empty(M, device=dev, dtype=torch.float32) for _ in range(3))
+    if M == 0:
+        return McStats(nll_s, bma, h, mi)
+    Sp = 1 << (S - 1).bit_length()
+    chunks = _row_chunks(M, Sp * K)  # token chunks whose M * Sp * K * 4 bytes stay under the LDS-DMA loaders' 2^32
+    ws = torch.empty(int(lib().blm_linear_mc_stats_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
+    for a, b in chunks:
+        xt = torch.zeros(b - a, Sp, K, device=dev, dtype=torch.float32)  # token-major, samples padded to Sp rows
+        xt[:, :S] = x[:, a:b].transpose(0, 1)
+        check(lib().blm_linear_mc_stats(ptr(xt), K, ptr(wp), K, ptr(bp), ptr(tgt[a:b]), S, ptr(nll_s[a:b]), ptr(bma[a:b]),
+                                        ptr(h[a:b]), ptr(mi[a:b]), ptr(ws), b - a, V, K, stream()), "blm_linear_mc_stats")
+    return McStats(nll_s, bma, h, mi)
 
 
 class InterpDecoder:

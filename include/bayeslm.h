@@ -150,7 +150,8 @@ typedef enum blm_epilogue {
   BLM_EPI_BAYES_WGRAD = 4, /* TN only, C = dmu, C2 = dlgstd, see below                 */
   BLM_EPI_GP_MIX = 5,      /* z = acc + bias; aux = z; C = sum_i act_i(z) coef[i,n]     */
   BLM_EPI_MUL_DGP_MIX = 6, /* C = acc * sum_i act_i'(aux) coef[i,n]; C2 (optional) = acc (after dropout) */
-  BLM_EPI_CE_PART = 7      /* internal to blm_linear_nll (blm_gemm refuses it): no C, per-tile softmax partials instead */
+  BLM_EPI_CE_PART = 7,     /* internal to blm_linear_nll (blm_gemm refuses it): no C, per-tile softmax partials instead */
+  BLM_EPI_MC_PART = 8      /* internal to blm_linear_mc_stats (blm_gemm refuses it): no C, per-tile uncertainty partials */
 } blm_epilogue;
 
 #define BLM_GEMM_ACCUMULATE 1u /* C (+= C2) accumulate into existing contents */
@@ -228,6 +229,26 @@ int blm_get_gemm_mode(void);
 int64_t blm_linear_nll_ws_floats(int M, int N);
 int blm_linear_nll(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
                    float* nll, float* lse, float* ws, int M, int N, int K, void* stream);
+/* Token-level predictive uncertainty from S Monte-Carlo weight samples, inference only; no reference counterpart (the
+ * reference scores with mean weights).  For token m and sample s < S the logits are z[s,v] = x[m,s].w[v] + b[v], v < V:
+ *   lse_s = logsumexp_v z[s,v],   p[s,v] = exp(z[s,v] - lse_s),   pbar[v] = (1/S) sum_s p[s,v]
+ *   nll_s[m,s] = lse_s - z[s,tgt[m]]                        (optional; what blm_linear_nll gives for that row)
+ *   bma_nll[m] = -log pbar[tgt[m]] = -log((1/S) sum_s exp(-nll_s[m,s]))   (computed with a max shift)
+ *   h_pred[m]  = -sum_v pbar[v] log pbar[v]                 (0 log 0 = 0: predictive entropy of the model average)
+ *   mi[m]      = (1/S) sum_s sum_v p[s,v] (log p[s,v] - log pbar[v])   (mean_s KL(p_s || pbar): the epistemic part)
+ * mi is computed in this KL form, never as h_pred - mean_s H[p_s] (two ~10-nat entropies whose fp32 difference loses small
+ * values): mi >= 0 up to rounding, and the expected entropy is h_pred - mi.  A target outside [0, V) gives NaN for that token's
+ * nll_s and bma_nll.
+ * Layout: x is token-major, Sp = S rounded up to a power of two, 1 <= S <= 64: row m * Sp + s holds sample s of token m; rows
+ * with s >= S are padding and enter no statistic.  w and bias have Np = V rounded up to 4 rows, 16-byte aligned; columns >= V
+ * enter no statistic (masked, whatever w / bias hold there).  bias may be NULL, nll_s (M x S) may be NULL.
+ * Two launches of the NT decoder product over M * Sp rows, neither storing a logit: blm_linear_nll's (lse and nll per row), then
+ * the same product with per (token, column tile) partials of sum pbar log pbar and sum_s sum_v p (log p - log pbar) in its
+ * epilogue; a fold kernel sums a token's tiles in a fixed order.  One K slice in both: bit-identical run to run in every mode.
+ * ws: blm_linear_mc_stats_ws_floats(M, S, V) floats (0: extents out of range), 16-byte aligned, owned by the caller. */
+int64_t blm_linear_mc_stats_ws_floats(int M, int S, int V);
+int blm_linear_mc_stats(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
+                        int S, float* nll_s, float* bma_nll, float* h_pred, float* mi, float* ws, int M, int V, int K, void* stream);
 /* Two-model scoring, reference compute_sentence_scores_bayes_jianwei.py:157-168: per-row NLL of the INTERPOLATED logits
  * alpha * (x1 w1^T + b1) + (1 - alpha) * (x2 w2^T + b2) against tgt, as ONE decoder + cross-entropy launch over the packed
  * operands [alpha x1 | (1 - alpha) x2] (M x (K1 + K2)) and [w1 | w2] (N x (K1 + K2)): neither model's (M x N) logits are stored.
