@@ -110,6 +110,7 @@ SIGNATURES = {
     "blm_add_dropout_ln_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _rngp, _i, _i, _vp]),
     "blm_attn_fwd": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _f, _rngp, _i, _i, _vp]),
     "blm_attn_fwd_rows": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "blm_attn_fwd_tree": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "blm_attn_bwd": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _rngp, _i, _i, _vp]),
     "blm_attn_bwd_ws": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _rngp, _i, _i, _vp,
                             _i64, _vp]),
@@ -125,6 +126,11 @@ SIGNATURES = {
     "blm_linear_nll2_wcat_floats": (_i64, [_i, _i, _i]),
     "blm_linear_nll2_ws_floats": (_i64, [_i, _i, _i, _i]),
     "blm_linear_nll2": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "blm_linear_nll_edges_ws_floats": (_i64, [_i, _i]),
+    "blm_linear_nll_edges": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "blm_linear_nll2_edges_ws_floats": (_i64, [_i, _i, _i, _i]),
+    "blm_linear_nll2_edges": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i,
+                                   _vp]),
     "blm_ce_bwd": (_i, [_vp, _i64, _vp, _vp, _vp, _f, _vp, _i, _i, _vp]),
     "blm_gp_coef_grad": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "blm_colsum": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp]),

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from ._lib import BayesLMError
+from .prefix_trie import build_trie
 
 
 def load_nbest(path):
@@ -219,6 +220,41 @@ def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, 
     return nll if rows is not None else nll.view(data.shape[0], data.shape[1])
 
 
+def _tree_nll(model, data, model_type, hidden, model_2, hidden_2, alpha, tree, dec):
+    """Per-EDGE NLL of a padded batch scored over its prefix tries (compute_scores_batched(share_prefixes=True)): ``tree`` =
+    (sel, end, lo, edge_node, edge_tgt) device tensors of prefix_trie.build_trie.  Transformers run under ops.tree_tokens (every
+    layer on the M node rows, attention over each node's path); LSTMs run the recurrence over the padded batch as _batch_nll does
+    and only the decoder moves to the node rows.  The decoders hand back their input rows; ONE edge launch gives the NLLs
+    (ops.linear_nll_edges, or ops.linear_nll_interp_edges for two models).  ``dec``: the run's McDecoder (one model)."""
+    from . import ops
+    import contextlib
+    sel, end, lo, en, et = tree
+    models = [m for m in (model, model_2) if m is not None]
+    for m in models:
+        if not hasattr(m.decoder, "return_input"):
+            raise BayesLMError("share_prefixes: %s's decoder cannot hand back its input rows" % type(m).__name__)
+    is_tf = model_type == 'Transformer'
+    try:
+        for m in models:
+            m.decoder.return_input = True
+            m.decoder.rows = None if is_tf else sel
+        with (ops.tree_tokens(sel, data.shape[0], data.shape[1], end, lo, model) if is_tf else contextlib.nullcontext()):
+            if is_tf:
+                x = model(data)
+                x2 = model_2(data) if model_2 is not None else None
+            else:
+                x = model(data, hidden)[0]
+                x2 = model_2(data, hidden_2)[0] if model_2 is not None else None
+    finally:
+        for m in models:
+            m.decoder.return_input = False
+            m.decoder.rows = None
+    x = x.reshape(-1, x.shape[-1])
+    if model_2 is None:
+        return ops.linear_nll_edges(x, dec, en, et)
+    return ops.linear_nll_interp_edges(x, x2.reshape(-1, x2.shape[-1]), _interp_decoder(model, model_2, alpha), en, et)
+
+
 def _carry(model, x0, hidden):
     """State after running x0 (T,1) from ``hidden`` in eval mode: the recurrent stack only -- every LSTM family here is
     embedding -> self.rnn -> dropout -> decoder (model.py:217-229 and its siblings), and the decoder's (T,V) logits
@@ -279,7 +315,7 @@ class HypUncertainty(NamedTuple):
 
 
 def compute_scores_batched(nbest, model, vocab, model_type, device, model_2=None, alpha=0.0, mc_samples=0, seed=1111,
-                           batch_tokens=None, uncertainty=False):
+                           batch_tokens=None, uncertainty=False, share_prefixes=False):
     """the N hypotheses of an utterance are padded into ONE (T_max, N) batch instead
     of N separate launches.  Exact for causal Transformers (padding sits after every real token) and
     for LSTMs (all hypotheses of an utterance start from the same carried state; the carry is the state after
@@ -296,7 +332,15 @@ def compute_scores_batched(nbest, model, vocab, model_type, device, model_2=None
 
     uncertainty=True (new, needs mc_samples >= 2 and one model): each sample's pass hands back its decoder input rows and ONE
     decoder launch per batch over all S of them (ops.linear_mc_stats) gives the per-sample NLLs -- the scores follow from them by
-    the formula above -- and the token-level uncertainty: returns (scores, unc), unc[key] = [(hyp, HypUncertainty)]."""
+    the formula above -- and the token-level uncertainty: returns (scores, unc), unc[key] = [(hyp, HypUncertainty)].
+
+    share_prefixes=True (new, default off): each packed batch is scored over a prefix trie per utterance (prefix_trie.py).  A
+    token's activations and next-word distribution depend on its prefix only (causal Transformer; LSTM columns starting from
+    their utterance's carry), so every distinct (utterance, input prefix) is computed once -- Transformers run every layer on the
+    trie's node rows with attention along each node's path (ops.tree_tokens) -- and the decoder's log-sum-exp runs once per node,
+    the target logit once per distinct (node, target) edge (ops.linear_nll_edges).  The LSTM recurrence itself still runs over the
+    padded batch.  Same scores up to floating-point reordering of the sums (a %.4f score may change its last digit); works with
+    mc_samples and two-model interpolation, not with uncertainty, and needs a Transformer with supports_packed."""
     # The loop builds hundreds of thousands of short-lived, acyclic Python objects (token lists, views); the cyclic collector's
     # full passes over them stall the host while the GPU waits -- 20000 hypotheses: 177 ms with the collector off against
     # 190-225 ms with it on (the first call of a process, with a small heap, hides it).  Off for the duration of the call.
@@ -305,13 +349,21 @@ def compute_scores_batched(nbest, model, vocab, model_type, device, model_2=None
     gc.disable()
     try:
         return _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, alpha, mc_samples, seed, batch_tokens,
-                                       uncertainty)
+                                       uncertainty, share_prefixes)
     finally:
         if gc_was:
             gc.enable()
 
 
-def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, alpha, mc_samples, seed, batch_tokens, uncertainty):
+def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, alpha, mc_samples, seed, batch_tokens, uncertainty,
+                            share_prefixes=False):
+    if share_prefixes and uncertainty:
+        raise BayesLMError("share_prefixes does not take uncertainty (token-level uncertainty over a prefix trie is not built)")
+    if share_prefixes and model_type == 'Transformer':
+        for m in (model, model_2):
+            if m is not None and not getattr(m, "supports_packed", False):
+                raise BayesLMError("share_prefixes: %s does not keep its activations token-wise outside the attention core "
+                                   "(no supports_packed): it cannot score over a prefix trie" % type(m).__name__)
     if uncertainty and (int(mc_samples) < 2 or model_2 is not None):
         raise BayesLMError("uncertainty needs --mc-samples >= 2 and one model (got %d samples%s)"
                            % (int(mc_samples), ", two models" if model_2 is not None else ""))
@@ -366,9 +418,35 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
             tsel[o:o + ln] = t
             o += ln
             ends[n] = o
-        dev_buf = torch.from_numpy(host).to(device, non_blocking=True)
-        data = dev_buf[:Tm * N].view(Tm, N)
-        d_sel, d_tsel, d_ends = dev_buf[Tm * N:Tm * N + R], dev_buf[Tm * N + R:Tm * N + 2 * R], dev_buf[Tm * N + 2 * R:]
+        tree = d_tok_edge = None
+        if share_prefixes:  # the batch's prefix tries, built once and reused by the S passes; one host-to-device copy of
+            # [data | node rows | end, lo (int32 pairs) | edge nodes | edge targets | token -> edge | hypothesis ends]
+            counts = [len(ps) for _, _, ps in group]
+            tr = build_trie(dat, np.asarray(lens, dtype=np.int64), tsel, np.repeat(np.arange(len(group)), counts))
+            M, E = tr.sel.shape[0], tr.edge_node.shape[0]
+            hb = np.empty(Tm * N + 2 * M + 2 * E + R + N, dtype=np.int64)
+            o = Tm * N
+            hb[:o] = host[:o]
+            hb[o:o + M] = tr.sel
+            el = hb[o + M:o + 2 * M].view(np.int32)
+            el[:M], el[M:] = tr.end, tr.lo
+            o += 2 * M
+            hb[o:o + E], hb[o + E:o + 2 * E], hb[o + 2 * E:o + 2 * E + R] = tr.edge_node, tr.edge_tgt, tr.tok_edge
+            hb[o + 2 * E + R:] = ends
+            dev_buf = torch.from_numpy(hb).to(device, non_blocking=True)
+            el_d = dev_buf[Tm * N + M:Tm * N + 2 * M].view(torch.int32)
+            tree = (dev_buf[Tm * N:Tm * N + M], el_d[:M], el_d[M:], dev_buf[o:o + E], dev_buf[o + E:o + 2 * E])
+            d_tok_edge = dev_buf[o + 2 * E:o + 2 * E + R]
+            data = dev_buf[:Tm * N].view(Tm, N)
+            d_sel = d_tsel = None
+            d_ends = dev_buf[o + 2 * E + R:]
+            if model_2 is None and not tree_dec:  # the decoder padded once for this scoring run (its weights do not change during it)
+                from . import ops
+                tree_dec.append(ops.McDecoder(model.decoder.weight, model.decoder.bias))
+        else:
+            dev_buf = torch.from_numpy(host).to(device, non_blocking=True)
+            data = dev_buf[:Tm * N].view(Tm, N)
+            d_sel, d_tsel, d_ends = dev_buf[Tm * N:Tm * N + R], dev_buf[Tm * N + R:Tm * N + 2 * R], dev_buf[Tm * N + 2 * R:]
         hN = h2N = None
         if is_rnn:  # every column starts from the state carried into ITS utterance
             counts = [len(ps) for _, _, ps in group]
@@ -384,7 +462,10 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
             if uncertainty:
                 xs.append(_batch_nll(model, data, d_tsel, model_type, hN, None, None, alpha, rows=d_sel, decoder_input=True))
                 continue
-            nll = _batch_nll(model, data, d_tsel, model_type, hN, model_2, h2N, alpha, rows=d_sel)  # (R,)
+            if share_prefixes:  # per edge -> per real token, n-major as the padded path orders them
+                nll = _tree_nll(model, data, model_type, hN, model_2, h2N, alpha, tree, tree_dec[0] if tree_dec else None)[d_tok_edge]
+            else:
+                nll = _batch_nll(model, data, d_tsel, model_type, hN, model_2, h2N, alpha, rows=d_sel)  # (R,)
             run = torch.cumsum(nll.double(), 0)
             hi = run[d_ends - 1]
             sent.append((hi - torch.cat([hi.new_zeros(1), hi[:-1]])).float())
@@ -412,6 +493,7 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
 
     pending = []
     mc_dec = []  # uncertainty: ops.McDecoder of this run, dropped with it
+    tree_dec = []  # share_prefixes, one model: the same
 
     def flush():
         if not pending:
@@ -563,6 +645,9 @@ def build_parser():
     p.add_argument('--write-uncertainty', type=str, default='', metavar='PATH',
                    help='with --mc-samples >= 2 (one model): per hypothesis "key-n score sent_logp_std sum_bma_nll sum_h_pred sum_mi '
                    'n_tokens" -- the token-level predictive entropy, mutual information (epistemic part) and model-average NLL summed')
+    p.add_argument('--share-prefixes', type=int, default=0, choices=[0, 1],
+                   help='1: score each batch over a prefix trie per utterance, every shared hypothesis prefix once (scores equal up to '
+                   'floating-point reordering; needs --batched 1, not with --write-uncertainty)')
     p.add_argument('--batch-tokens', type=int, default=0, help='padded tokens per batch across utterances (0: 16384 for Transformers, 8192 for LSTMs)')
     p.add_argument('--gemm-mode', type=str, default='f32', choices=['f32', 'bf16x6', 'bf16x3'],
                    help='opt-in split-bf16 arithmetic of the GEMM family (DESIGN.md section 7); default fp32 MFMA')
@@ -595,6 +680,10 @@ def main(argv=None):
     if args.write_uncertainty and (args.mc_samples < 2 or args.interpolation_flag != 0):
         raise SystemExit("--write-uncertainty needs --mc-samples >= 2 and --interpolation_flag 0 (got --mc-samples %d, "
                          "--interpolation_flag %d)" % (args.mc_samples, args.interpolation_flag))
+    if args.share_prefixes and not args.batched:
+        raise SystemExit("--share-prefixes 1 needs --batched 1 (the per-hypothesis path has nothing to share)")
+    if args.share_prefixes and args.write_uncertainty:
+        raise SystemExit("--share-prefixes 1 does not take --write-uncertainty (token-level uncertainty over a prefix trie is not built)")
     for pth, what in ((args.nbest_list, "Nbest list"), (args.vocabulary, "Vocabulary"), (args.model_path, "Model")):
         assert os.path.exists(pth), "%s path does not exists." % what
     if not torch.cuda.is_available():
@@ -615,7 +704,8 @@ def main(argv=None):
     nbest = load_nbest(args.nbest_list)
     if args.batched or args.mc_samples > 0:
         scores = compute_scores_batched(nbest, model_1, vocab, args.model, device, model_2, args.inter_alpha, args.mc_samples,
-                                        batch_tokens=args.batch_tokens, uncertainty=bool(args.write_uncertainty))
+                                        batch_tokens=args.batch_tokens, uncertainty=bool(args.write_uncertainty),
+                                        share_prefixes=bool(args.share_prefixes))
         if args.write_uncertainty:
             scores, unc = scores
     else:

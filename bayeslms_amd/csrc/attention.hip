@@ -497,6 +497,53 @@ __global__ __launch_bounds__(64) void attn_fwd_generic_kernel(const AttnP p, int
   if (p.lse && lane == 0) p.lse[(long)bhl * T + q] = m + __logf(l);
 }
 
+// Tree attention (n-best prefix sharing, inference; blm_attn_fwd_tree): row i attends row j iff lo[i] <= j <= i and end[j] > i --
+// i and its ancestors in a prefix trie laid out in DFS preorder.  One wave per (query, head), head_dim <= 128 (two features per
+// lane): the wave tests 64 candidate keys of [lo[i], i] at a time and walks the ones on the path (a wave-uniform ballot), so its
+// work is the node's depth, not the width of its utterance.  The correctness kernel for head sizes other than 64.
+__global__ __launch_bounds__(64) void attn_fwd_tree_generic_kernel(const AttnP p, const int* __restrict__ tend, const int* __restrict__ tlo,
+                                                                   int hd) {
+  const int q = blockIdx.x, head = blockIdx.y, off = head * hd, lane = threadIdx.x;
+  float qv[2], acc[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int f = lane + 64 * j;
+    qv[j] = f < hd ? p.q[(long)q * p.ld + off + f] * p.scale : 0.f;
+    acc[j] = 0.f;
+  }
+  float m = -INFINITY, l = 0.f;
+  for (int c = max(tlo[q], 0); c <= q; c += 64) {
+    const int key = c + lane;
+    const unsigned long long on = __ballot(key <= q && tend[key] > q);
+    for (unsigned long long bits = on; bits; bits &= bits - 1) {
+      const int kj = c + __ffsll(bits) - 1;
+      const float* kr = p.k + (long)kj * p.ld + off;
+      const float* vr = p.v + (long)kj * p.ld + off;
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int f = lane + 64 * j;
+        if (f < hd) s += qv[j] * kr[f];
+      }
+      s = wave_sum(s);
+      const float mn = fmaxf(m, s), alpha = __expf(m - mn), e = __expf(s - mn);
+      l = l * alpha + e;
+      m = mn;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int f = lane + 64 * j;
+        if (f < hd) acc[j] = acc[j] * alpha + e * vr[f];
+      }
+    }
+  }
+  const float inv = 1.f / l;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int f = lane + 64 * j;
+    if (f < hd) p.out[(long)q * ((long)p.nhead * hd) + off + f] = acc[j] * inv;
+  }
+}
+
 __global__ __launch_bounds__(64) void attn_bwd_dq_generic_kernel(const AttnP p, int hd) {
   const int q = blockIdx.x, bhl = blockIdx.y, b = bhl / p.nhead, head = bhl % p.nhead, off = head * hd;
   const int lane = threadIdx.x, T = p.T;
@@ -740,6 +787,29 @@ extern "C" int blm_attn_fwd_rows(const float* q, const float* k, const float* v,
   if ((long)T * B == 0) return BLM_OK;
   if (!use_mfma(head_dim)) return blm_fail(BLM_ERR_UNSUPPORTED, "blm_attn_fwd_rows: head_dim 64 only");
   return blm_attn_fwd_rows_mfma(q, k, v, ld_qkv, out, rowmap, T, B, nhead, static_cast<hipStream_t>(stream));
+}
+
+int blm_attn_fwd_tree_mfma(const float* q, const float* k, const float* v, int64_t ld, float* out, const int* end, const int* lo, int R,
+                           int nhead, hipStream_t st);
+
+extern "C" int blm_attn_fwd_tree(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, const int32_t* end,
+                                 const int32_t* lo, int R, int nhead, int head_dim, void* stream) {
+  if (!q || !k || !v || !out || !end || !lo || R < 0 || nhead <= 0 || head_dim <= 0)
+    return blm_fail(BLM_ERR_INVALID, "blm_attn_fwd_tree: bad arguments");
+  if (head_dim > 128) return blm_fail(BLM_ERR_UNSUPPORTED, "blm_attn_fwd_tree: head_dim %d not in 1..128", head_dim);
+  if (ld_qkv < (int64_t)nhead * head_dim) return blm_fail(BLM_ERR_INVALID, "blm_attn_fwd_tree: ld_qkv too small");
+  if (!blm::extents_ok({R, (long)ld_qkv}) || !blm::extents_ok({R, nhead, head_dim}) || nhead > 65535)
+    return blm_fail(BLM_ERR_INVALID, "blm_attn_fwd_tree: extents too large");
+  if (R == 0) return BLM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (use_mfma(head_dim)) return blm_attn_fwd_tree_mfma(q, k, v, ld_qkv, out, end, lo, R, nhead, st);
+  AttnP p{};
+  p.T = R; p.B = 1; p.nhead = nhead; p.hd = head_dim;
+  p.scale = 1.0f / sqrtf((float)head_dim);
+  p.q = q; p.k = k; p.v = v; p.ld = ld_qkv; p.out = out;
+  hipLaunchKernelGGL(attn_fwd_tree_generic_kernel, dim3(R, nhead), dim3(64), 0, st, p, end, lo, head_dim);
+  BLM_HIP(hipGetLastError());
+  return BLM_OK;
 }
 
 extern "C" int64_t blm_attn_bwd_ws_floats(int T, int B, int nhead, int head_dim) {

@@ -695,6 +695,85 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const AttnM p) {
   }
 }
 
+// ------------------------------------------------------------------ tree attention (n-best prefix sharing, inference)
+// The R rows are the nodes of prefix tries in DFS preorder (bayeslms_amd/prefix_trie.py): query row i attends key row j iff
+// lo[i] <= j <= i and end[j] > i, i.e. j is i or one of its ancestors.  The flash-style loop of attn_fwd_long_kernel over the
+// flat row range: a workgroup owns 128 queries (a 32-row tile per wave) and walks 128-row key chunks from the smallest lo among
+// its rows to its last row, the chunk's end[] staged in LDS beside K / V.  Under this mask a whole 32-key tile can be masked for
+// some queries (every key of it outside their path), so the online softmax guards the -inf - -inf case; tiles below every lo of a
+// wave are skipped (wave-uniform).  No dropout, no lse.
+__global__ __launch_bounds__(256) void attn_fwd_tree_kernel(const AttnM p, const int* __restrict__ tend, const int* __restrict__ tlo) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* Ks = sm;
+  float* Vs = sm + AT * LS;
+  int* Es = reinterpret_cast<int*>(sm + 2 * AT * LS);
+  __shared__ int s_lo;
+  const int head = blockIdx.y, off = head * HD;
+  const int R = p.T, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
+  const int qb = blockIdx.x;
+  const int q = 128 * qb + 32 * wave + li, qc = min(q, R - 1);
+  const int qlast = min(128 * qb + 127, R - 1), wlast = 128 * qb + 32 * wave + 31;
+  const int mylo = max(tlo[qc], 0);
+  int wlo = mylo;  // the smallest lo of the wave's 32 queries (both lane halves hold the same ones)
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) wlo = min(wlo, __shfl_xor(wlo, o, 64));
+  if (threadIdx.x == 0) s_lo = R;
+  __syncthreads();
+  if (lane == 0) atomicMin(&s_lo, wlo);
+  float qa[32];
+  fetch_op(qa, p.q + (long)qc * p.ld + off + 32 * lh);
+#pragma unroll
+  for (int s = 0; s < 32; ++s) qa[s] *= p.scale;
+  float m = -INFINITY, l = 0.f;
+  f32x16 ot[2] = {(f32x16)(0.f), (f32x16)(0.f)};
+  __syncthreads();
+  const int k0 = s_lo;
+#pragma unroll 1
+  for (int c = k0; c <= qlast; c += AT) {
+    __syncthreads();  // every wave is done with the previous chunk
+    {
+      float4 kk[8], vv[8];
+      fetch_rows_at<256>(kk, p.k, p.ld, R, 1, 0, off, c);  // rows past R read row R - 1 and are zeroed below
+      fetch_rows_at<256>(vv, p.v, p.ld, R, 1, 0, off, c);
+      put_rows<256>(Ks, kk, R - c, 1.f, threadIdx.x);
+      put_rows<256>(Vs, vv, R - c, 1.f, threadIdx.x);
+      if (threadIdx.x < AT) Es[threadIdx.x] = c + (int)threadIdx.x < R ? tend[c + threadIdx.x] : -1;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int kt = 0; kt < 4; ++kt) {
+      const int gk0 = c + 32 * kt;  // first key of the tile
+      if (gk0 > wlast || gk0 >= R) break;  // wave-uniform: after every query of the wave / past the rows
+      if (gk0 + 31 < wlo) continue;        // wave-uniform: before every query's utterance
+      f32x16 st = tile_rows_x_regs(Ks, 32 * kt, qa, li, lh);
+      float tm = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = gk0 + mrow(r, lh);
+        if (j > qc || j < mylo || Es[j - c] <= qc) st[r] = -INFINITY;  // not an ancestor of the query (nor the query itself)
+        tm = fmaxf(tm, st[r]);
+      }
+      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+      const float mn = fmaxf(m, tm);
+      const float ms = mn == -INFINITY ? 0.f : mn;  // no key of the query seen yet: exp(-inf - 0) = 0 keeps l and ot at 0
+      const float alpha = __expf(m - ms);
+      float ts = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        st[r] = __expf(st[r] - ms);
+        ts += st[r];
+      }
+      ts += __shfl_xor(ts, 32, 64);
+      l = l * alpha + ts;
+      m = mn;
+      ot[0] *= alpha;
+      ot[1] *= alpha;
+      acc_xt_regs(ot, Vs, 32 * kt, st, li, lh);
+    }
+  }
+  if (q < R) store_t(p.out + (long)q * ((long)p.nhead * HD) + off, ot, lh, 1.f / l);
+}
+
 __global__ __launch_bounds__(256) void attn_bwd_dq_long_kernel(const AttnM p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* Ks = sm;
@@ -917,6 +996,24 @@ int blm_attn_fwd_rows_mfma(const float* q, const float* k, const float* v, int64
     once_s = true;
   }
   hipLaunchKernelGGL(attn_fwd_short_kernel, dim3((B * nhead + 3) / 4), dim3(256), lds_s, st, p);
+  BLM_HIP(hipGetLastError());
+  return BLM_OK;
+}
+
+// Tree attention over R packed trie nodes (blm_attn_fwd_tree, attention.hip: arguments already checked), head_dim 64
+int blm_attn_fwd_tree_mfma(const float* q, const float* k, const float* v, int64_t ld, float* out, const int* end, const int* lo, int R,
+                           int nhead, hipStream_t st) {
+  AttnM p{};
+  fill_m(p, R, 1, nhead, 0.f, nullptr, 0);
+  p.q = q; p.k = k; p.v = v; p.ld = ld; p.out = out; p.lse = nullptr;
+  const size_t lds = (size_t)2 * AT * LS * sizeof(float) + AT * sizeof(int);
+  static bool once_t = false;
+  if (!once_t) {
+    const int rc = set_lds(attn_fwd_tree_kernel, lds);
+    if (rc) return rc;
+    once_t = true;
+  }
+  hipLaunchKernelGGL(attn_fwd_tree_kernel, dim3((R + AT - 1) / AT, nhead), dim3(256), lds, st, p, end, lo);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

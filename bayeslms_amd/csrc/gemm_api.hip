@@ -368,3 +368,110 @@ extern "C" int blm_linear_nll2(const float* x1, int64_t ldx1, const float* w1, i
   BLM_HIP(hipGetLastError());
   return blm_linear_nll(ws, K, wcat, K, bias, tgt, nll, lse, ws + (int64_t)M * K, M, Np, K, stream);
 }
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// N-best rescoring over a prefix trie (compute_scores_batched(share_prefixes=True)): the decoder's input rows are the M trie nodes,
+// its targets the E distinct (node, target) edges.  nll[e] = lse[node] - (x[node] . w[tgt] + b[tgt]): the log-sum-exp per node
+// comes from blm_linear_nll's launch (CE_PART + fold, the target logit it also leaves is not used: target 0 is passed for every
+// node), the edge's logit from a wave-per-edge dot product in a fixed order.  No logit is stored.
+namespace blm {
+__global__ __launch_bounds__(256) void edge_nll_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ w, long ldw,
+                                                       const float* __restrict__ bias, const long long* __restrict__ en,
+                                                       const long long* __restrict__ et, const float* __restrict__ lse,
+                                                       float* __restrict__ nll, long E, int M, int nv, int K, int vec) {
+  const long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (e >= E) return;
+  const long long node = en[e], t = et[e];
+  if (node < 0 || node >= M || t < 0 || t >= nv) {  // an edge outside the decoder: NaN, nothing read
+    if (lane == 0) nll[e] = __int_as_float(0x7fc00000);
+    return;
+  }
+  const float* xr = x + node * ldx;
+  const float* wr = w + t * ldw;
+  float s = 0.f;
+  if (vec) {
+    const float4* x4 = reinterpret_cast<const float4*>(xr);
+    const float4* w4 = reinterpret_cast<const float4*>(wr);
+    for (int k = lane; k < (K >> 2); k += 64) {
+      const float4 a = x4[k], b = w4[k];
+      s = fmaf(a.x, b.x, s); s = fmaf(a.y, b.y, s); s = fmaf(a.z, b.z, s); s = fmaf(a.w, b.w, s);
+    }
+  } else {
+    for (int k = lane; k < K; k += 64) s = fmaf(xr[k], wr[k], s);
+  }
+  s = wave_sum(s);
+  if (lane == 0) nll[e] = lse[node] - (s + (bias ? bias[t] : 0.f));
+}
+}  // namespace blm
+
+extern "C" int64_t blm_linear_nll_edges_ws_floats(int M, int N) {
+  if (M < 0 || N <= 0 || !blm::extents_ok({M, N})) return 0;
+  // blm_linear_nll's workspace, then (from a 16-byte boundary) int64 zero targets, nll and lse per node
+  return blm_linear_nll_ws_floats(M, N) + 4 + 4 * (int64_t)M;
+}
+
+extern "C" int blm_linear_nll_edges(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* edge_node,
+                                    const int64_t* edge_tgt, float* nll, float* ws, int M, int E, int N, int nv, int K, void* stream) {
+  if (M < 0 || E < 0 || N <= 0 || nv <= 0 || nv > N || K <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll_edges: bad shape");
+  if (!x || !w || !edge_node || !edge_tgt || !nll || !ws || ldx < K || ldw < K)
+    return blm_fail(BLM_ERR_INVALID, "blm_linear_nll_edges: bad arguments");
+  if (!blm::extents_ok({M, ldx}) || !blm::extents_ok({N, ldw}) || !blm::extents_ok({M, N}))
+    return blm_fail(BLM_ERR_INVALID, "blm_linear_nll_edges: extents too large");
+  if (N % 4 != 0 || !aligned16(ws) || (bias && !aligned16(bias)))
+    return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll_edges: needs N %% 4 == 0 and 16-byte aligned bias / workspace");
+  if (E == 0) return BLM_OK;
+  if (M == 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll_edges: edges without nodes");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t lin = (blm_linear_nll_ws_floats(M, N) + 3) / 4 * 4;
+  int64_t* tgt0 = reinterpret_cast<int64_t*>(ws + lin);
+  float* nll_rows = ws + lin + 2 * (int64_t)M;
+  float* lse_rows = nll_rows + M;
+  BLM_HIP(hipMemsetAsync(tgt0, 0, (size_t)M * sizeof(int64_t), st));
+  const int rc = linear_nll_launch(x, ldx, w, ldw, bias, tgt0, 0, nv, nll_rows, lse_rows, ws, M, N, K, st);
+  if (rc) return rc;
+  const int vec = aligned16(x) && aligned16(w) && ldx % 4 == 0 && ldw % 4 == 0 && K % 4 == 0;
+  hipLaunchKernelGGL(edge_nll_kernel, dim3((unsigned)(((long)E + 3) / 4)), dim3(256), 0, st, x, (long)ldx, w, (long)ldw, bias,
+                     reinterpret_cast<const long long*>(edge_node), reinterpret_cast<const long long*>(edge_tgt), lse_rows, nll, (long)E,
+                     M, nv, K, vec);
+  BLM_HIP(hipGetLastError());
+  return BLM_OK;
+}
+
+// Two models over the trie: the packed operands of blm_linear_nll2 ([alpha x1 | (1 - alpha) x2], [w1 | w2], the mixed bias with -inf
+// on the padding words) through blm_linear_nll_edges.
+extern "C" int64_t blm_linear_nll2_edges_ws_floats(int M, int N, int K1, int K2) {
+  if (M < 0 || N <= 0 || K1 <= 0 || K2 <= 0 || !blm::extents_ok({M, K1}) || !blm::extents_ok({M, K2})) return 0;
+  const int64_t e = blm_linear_nll_edges_ws_floats(M, (N + 3) / 4 * 4);
+  return e ? (int64_t)M * (K1 + K2) + e : 0;  // packed activations, then blm_linear_nll_edges' own workspace
+}
+
+extern "C" int blm_linear_nll2_edges(const float* x1, int64_t ldx1, const float* w1, int64_t ldw1, const float* b1, int K1,
+                                     const float* x2, int64_t ldx2, const float* w2, int64_t ldw2, const float* b2, int K2, float alpha,
+                                     const int64_t* edge_node, const int64_t* edge_tgt, float* nll, float* wcat, int pack_w, float* ws,
+                                     int M, int E, int N, void* stream) {
+  if (M < 0 || E < 0 || N <= 0 || K1 <= 0 || K2 <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll2_edges: bad shape");
+  if (!x1 || !x2 || !w1 || !w2 || !edge_node || !edge_tgt || !nll || !wcat || !ws || ldx1 < K1 || ldx2 < K2 || ldw1 < K1 || ldw2 < K2)
+    return blm_fail(BLM_ERR_INVALID, "blm_linear_nll2_edges: bad arguments");
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (K1 % 4 || K2 % 4 || ldx1 % 4 || ldx2 % 4 || ldw1 % 4 || ldw2 % 4 || !al(x1) || !al(x2) || !al(w1) || !al(w2) || !al(wcat) || !al(ws))
+    return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll2_edges: needs K1, K2 and the row strides to be multiples of 4 and 16-byte aligned operands");
+  const int K = K1 + K2, Np = (N + 3) / 4 * 4;
+  if (!blm::extents_ok({M, K}) || !blm::extents_ok({Np, K}) || !blm::extents_ok({M, Np}))
+    return blm_fail(BLM_ERR_INVALID, "blm_linear_nll2_edges: extents too large");
+  if (E == 0) return BLM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* bias = wcat + (int64_t)Np * K;
+  auto blocks = [](long n) { long b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); };
+  if (pack_w) {
+    hipLaunchKernelGGL(pack2_kernel, dim3(blocks((long)Np * K / 4)), dim3(256), 0, st, wcat, (long)K, w1, (long)ldw1, K1, 1.f, w2, (long)ldw2,
+                       K2, 1.f, (long)N, (long)Np);
+    hipLaunchKernelGGL(bias_mix_kernel, dim3((Np + 255) / 256), dim3(256), 0, st, bias, b1, alpha, b2, 1.f - alpha, N, Np);
+  }
+  if (M > 0)
+    hipLaunchKernelGGL(pack2_kernel, dim3(blocks((long)M * K / 4)), dim3(256), 0, st, ws, (long)K, x1, (long)ldx1, K1, alpha, x2, (long)ldx2,
+                       K2, 1.f - alpha, (long)M, (long)M);
+  BLM_HIP(hipGetLastError());
+  return blm_linear_nll_edges(ws, K, wcat, K, bias, edge_node, edge_tgt, nll, ws + (int64_t)M * K, M, E, Np, N, K, stream);
+}

@@ -1588,6 +1588,97 @@ class packed_tokens:
         return self.pack(attention_qkv(self.unpack(q), self.unpack(k), self.unpack(v), nhead))
 
 
+
+class tree_tokens(packed_tokens):
+    """Inference helper (the n-best scorer with shared prefixes): ``packed_tokens`` whose rows are the M nodes of the batch's prefix
+    tries (bayeslms_amd/prefix_trie.py) instead of every real token -- ``sel`` (M,) int64 gives one padded position t * N + n per
+    node, t being its depth, so the embedding and positional encoding are packed as for a real token; every token-wise operation
+    runs on M rows.  The attention core is blm_attn_fwd_tree over the nodes: a node attends itself and its ancestors, ``end`` and
+    ``lo`` (M,) int32 device tensors (one past the node's subtree, first node of its utterance).  The model must declare
+    ``supports_packed``."""
+
+    def __init__(self, sel, T, N, end, lo, model=None):
+        if model is not None and not getattr(model, "supports_packed", False):
+            raise BayesLMError("ops.tree_tokens: %s does not keep its activations token-wise outside the attention core "
+                               "(no supports_packed): it cannot score over a prefix trie" % type(model).__name__)
+        super().__init__(sel, T, N)
+        if end.dtype != torch.int32 or lo.dtype != torch.int32 or end.numel() != sel.numel() or lo.numel() != sel.numel():
+            raise ValueError("ops.tree_tokens: end and lo must be (M,) int32, one entry per node")
+        self.end, self.lo = end.contiguous(), lo.contiguous()
+
+    def attention(self, q, k, v, nhead):
+        """q / k / v (M, 1, d) (or q = the fused (M, 1, 3d) projection, k = v = None) -> (M, 1, d) over the trie mask."""
+        if k is None:
+            qkv = _f32(q, "qkv")
+            d = qkv.shape[-1] // 3
+            qq, kk, vv, ld = qkv, qkv[..., d:], qkv[..., 2 * d:], 3 * d
+        else:
+            qq, kk, vv = _f32(q, "q").contiguous(), _f32(k, "k").contiguous(), _f32(v, "v").contiguous()
+            d = ld = qq.shape[-1]
+        R = qq.numel() // qq.shape[-1]
+        out = torch.empty(R, 1, d, device=qq.device, dtype=torch.float32)
+        L.require_gfx950()
+        check(lib().blm_attn_fwd_tree(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(self.end), ptr(self.lo), R, nhead,
+                                      d // nhead, stream()), "blm_attn_fwd_tree")
+        return out
+
+
+def linear_nll_edges(x, dec, edge_node, edge_tgt):
+    """Inference only: per-edge NLL over a prefix trie, nll[e] = logsumexp(x[node] W^T + b) - (x[node] . W[tgt] + b[tgt]) for the
+    E (node, target) edges, no logit stored (blm_linear_nll_edges).  ``x`` (M, K) node rows; ``dec``: McDecoder(weight, bias) of the
+    scoring run (the vocabulary padded to a multiple of 4 once); ``edge_node`` / ``edge_tgt`` (E,) int64.  -> (E,) NLL"""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise BayesLMError("linear_nll_edges is an inference-only path (no backward): call it under torch.no_grad()")
+    x2 = _f32(x, "x").reshape(-1, x.shape[-1])
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    M, K = x2.shape
+    V, Np = dec.weight.shape[0], dec.wp.shape[0]
+    if dec.wp.shape[1] != K or edge_node.numel() != edge_tgt.numel():
+        raise ValueError("linear_nll_edges: x (M, K), a (V, K) decoder and E (node, target) pairs expected")
+    L.require_gfx950()
+    en = dev_tensor(edge_node.reshape(-1), "edge_node", torch.int64)
+    et = dev_tensor(edge_tgt.reshape(-1), "edge_tgt", torch.int64)
+    E = en.numel()
+    nll = torch.empty(E, device=x2.device, dtype=torch.float32)
+    if E == 0:
+        return nll
+    ws = torch.empty(int(lib().blm_linear_nll_edges_ws_floats(M, Np)), device=x2.device, dtype=torch.float32)
+    check(lib().blm_linear_nll_edges(ptr(x2), x2.stride(0), ptr(dec.wp), dec.wp.stride(0), ptr(dec.bp), ptr(en), ptr(et), ptr(nll), ptr(ws),
+                                     M, E, Np, V, K, stream()), "blm_linear_nll_edges")
+    return nll
+
+
+def linear_nll_interp_edges(x1, x2, dec, edge_node, edge_tgt):
+    """Inference only: linear_nll_edges over two models' INTERPOLATED logits alpha (x1 W1^T + b1) + (1 - alpha) (x2 W2^T + b2)
+    (the mixing of linear_nll_interp; ``dec``: the run's InterpDecoder).  -> (E,) NLL"""
+    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
+        raise BayesLMError("linear_nll_interp_edges is an inference-only path (no backward): call it under torch.no_grad()")
+    a = _f32(x1, "x1").reshape(-1, x1.shape[-1])
+    b = _f32(x2, "x2").reshape(-1, x2.shape[-1])
+    a = a if a.stride(-1) == 1 else a.contiguous()
+    b = b if b.stride(-1) == 1 else b.contiguous()
+    M, K1 = a.shape
+    K2 = b.shape[1]
+    V = dec.w1.shape[0]
+    if b.shape[0] != M or dec.w1.shape[1] != K1 or dec.w2.shape[1] != K2 or edge_node.numel() != edge_tgt.numel():
+        raise ValueError("linear_nll_interp_edges: x1 (M, K1), x2 (M, K2), decoders (V, K1) / (V, K2) and E (node, target) pairs expected")
+    L.require_gfx950()
+    en = dev_tensor(edge_node.reshape(-1), "edge_node", torch.int64)
+    et = dev_tensor(edge_tgt.reshape(-1), "edge_tgt", torch.int64)
+    E = en.numel()
+    nll = torch.empty(E, device=a.device, dtype=torch.float32)
+    if E == 0:
+        return nll
+    ws = torch.empty(int(lib().blm_linear_nll2_edges_ws_floats(M, V, K1, K2)), device=a.device, dtype=torch.float32)
+    check(lib().blm_linear_nll2_edges(ptr(a), a.stride(0), ptr(dec.w1), dec.w1.stride(0), ptr(dec.b1), K1,
+                                      ptr(b), b.stride(0), ptr(dec.w2), dec.w2.stride(0), ptr(dec.b2), K2, dec.alpha,
+                                      ptr(en), ptr(et), ptr(nll), ptr(dec.wcat), 0 if dec.packed else 1, ptr(ws), M, E, V, stream()),
+          "blm_linear_nll2_edges")
+    dec.packed = True
+    return nll
+
+
 def packing():
     return getattr(_PACK, "cur", None)
 

@@ -262,6 +262,25 @@ int blm_linear_nll2(const float* x1, int64_t ldx1, const float* w1, int64_t ldw1
                     const float* x2, int64_t ldx2, const float* w2, int64_t ldw2, const float* b2, int K2, float alpha,
                     const int64_t* tgt, float* nll, float* lse, float* wcat, int pack_w, float* ws, int M, int N, void* stream);
 
+/* N-best rescoring over a prefix trie (compute_scores_batched(share_prefixes=True)), inference only; no reference counterpart.
+ * x holds the decoder's input rows of the M trie nodes, edge e = (edge_node[e], edge_tgt[e]) a distinct (node, target) pair:
+ *   nll[e] = logsumexp_{v < nv}(x[node,:] . w[v,:] + bias[v]) - (x[node,:] . w[tgt,:] + bias[tgt])
+ * without storing the M x N logits: the log-sum-exp per node is blm_linear_nll's launch, the edge's logit a dot product per edge
+ * in a fixed order (bit-identical run to run).  w and bias have N rows, N % 4 == 0 (a vocabulary padded once per scoring run);
+ * columns >= nv are padding and enter no sum.  bias may be NULL.  An edge whose node is outside [0, M) or whose target is outside
+ * [0, nv) gives NaN.  ws: blm_linear_nll_edges_ws_floats(M, N) floats (0: extents out of range), 16-byte aligned, caller-owned. */
+int64_t blm_linear_nll_edges_ws_floats(int M, int N);
+int blm_linear_nll_edges(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* edge_node,
+                         const int64_t* edge_tgt, float* nll, float* ws, int M, int E, int N, int nv, int K, void* stream);
+/* The same over two models' INTERPOLATED logits alpha (x1 w1^T + b1) + (1 - alpha) (x2 w2^T + b2), operands and wcat exactly as
+ * blm_linear_nll2 takes them (any N; K1, K2 and the row strides multiples of 4, 16-byte aligned operands).
+ * ws: blm_linear_nll2_edges_ws_floats(M, N, K1, K2) floats per call. */
+int64_t blm_linear_nll2_edges_ws_floats(int M, int N, int K1, int K2);
+int blm_linear_nll2_edges(const float* x1, int64_t ldx1, const float* w1, int64_t ldw1, const float* b1, int K1,
+                          const float* x2, int64_t ldx2, const float* w2, int64_t ldw2, const float* b2, int K2, float alpha,
+                          const int64_t* edge_node, const int64_t* edge_tgt, float* nll, float* wcat, int pack_w, float* ws, int M, int E,
+                          int N, void* stream);
+
 /* Kernel-selection options: switches that pick between two BUILT forms of a kernel (each form is parity-tested; the defaults are
  * the measured winners).  Settable at run time; each is initialised from its environment variable on first use.
  *   "attn_hpw"   (BLM_ATTN_HPW,   0) heads per workgroup of the T <= 128 attention kernels: 0 = by head count, 1, 2
@@ -404,6 +423,14 @@ int blm_attn_bwd(const float* q, const float* k, const float* v, int64_t ld_qkv,
  * T <= 32 (one wave per head); anything else returns BLM_ERR_UNSUPPORTED and the caller scatters / gathers around blm_attn_fwd. */
 int blm_attn_fwd_rows(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, const int32_t* rowmap, int T,
                       int B, int nhead, int head_dim, void* stream);
+/* Inference over the R nodes of prefix tries (the n-best scorer with shared prefixes): q / k / v are (R, ld_qkv) and out
+ * (R, nhead * head_dim) matrices of the nodes in DFS preorder, each utterance's nodes contiguous; row i attends row j iff
+ * lo[i] <= j <= i and end[j] > i (j is i or an ancestor of i: end[j] is one past j's subtree, lo[i] the first node of i's
+ * utterance).  Same scaling and softmax as blm_attn_fwd without dropout; a row that attends no key gives NaN.  head_dim 64 --
+ * matrix cores, 128-query tiles of the flat row range walking the key chunks from their smallest lo (attention_mfma.hip);
+ * any other head_dim <= 128 -- vector ALU, one wave per query walking its path; larger head sizes return BLM_ERR_UNSUPPORTED. */
+int blm_attn_fwd_tree(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, const int32_t* end, const int32_t* lo,
+                      int R, int nhead, int head_dim, void* stream);
 /* The same backward with a caller-owned scratch buffer of blm_attn_bwd_ws_floats() floats (0: this shape has no use
  * for one): the dK/dV kernel leaves dS (B*nhead, T, T) there and dQ = dS K is one small product instead of a second
  * recomputation of the probabilities and their dropout masks.  ws == NULL is blm_attn_bwd.  Same results. */
