@@ -7,8 +7,12 @@ MI355X of one node, synthetic AMI-shaped token stream, random-init weights, fp32
 One step = forward + CE + KL*seq_len/len(train_data) + backward + gradient all-reduce (N > 1)
 + global-norm clip + SGD, nothing skipped.  Prints ONE JSON line on rank 0.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5          (the headline alone: set up, warm up, timed steps, the line)
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs   (+ what the last timed step computed, .npy)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   (+ everything else the line can carry, after the headline: eval
+                                                             PPL, chip probe, CPU baselines, opt-in GEMM modes, extra_configs;
+                                                             at N > 1 the stand-alone all-reduces, comm diagnostics and
+                                                             configs[4]'s data-parallel legs)
     python bench.py --gpus N ...        (starts its own N ranks: a torch.distributed.run child process, before
                                          this process has touched the GPU; the child's JSON line and exit code are
                                          relayed)
@@ -48,14 +52,19 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--fused-sampling", type=int, default=-1,
                     help="1: eps generated inside the GEMM tile loader; 0: one materialisation pass; -1: engine default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline, after it: evaluation PPL, the bare-MFMA chip "
+                         "probe, the CPU baselines, the opt-in GEMM modes and extra_configs (N = 1); the stand-alone all-reduces, "
+                         "the comm diagnostics and configs[4]'s data-parallel legs (N > 1).  Without it a run sets up, warms up, "
+                         "times its steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-all-cores", action="store_true",
-                    help="also time the CPU baseline with one thread per VISIBLE host core, live (~3 minutes on a one-GPU box: "
-                         "256 threads on a 16-core share); the default run reports the committed measurement")
+                    help="--full: also time the CPU baseline with one thread per VISIBLE host core, live (~3 minutes on a one-GPU "
+                         "box: 256 threads on a 16-core share); otherwise the line reports the committed measurement")
     ap.add_argument("--no-opt-in", action="store_true",
-                    help="skip the extra, separately reported runs in the opt-in split-bf16 GEMM modes (N = 1 only)")
+                    help="--full: skip the extra, separately reported runs in the opt-in split-bf16 GEMM modes (N = 1 only)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip extra_configs (BASELINE configs[1] and configs[4] legs, reported after the headline)")
+                    help="--full: skip extra_configs (BASELINE configs[1] and configs[4] legs, reported after the headline)")
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="columns per GPU (default = the named config)")
     ap.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for "
                     "rehearsing several ranks on one GPU)")
@@ -72,9 +81,9 @@ def parse():
                          "(barrier-bracketed, max over ranks: the same numbers on every rank); a setting that is more than 2 %% faster than "
                          "the configured one is kept for the timed region and reported in comm.autotune; 0 = run as configured")
     ap.add_argument("--comm-ab-steps", type=int, default=5,
-                    help="N > 1: steps of each A/B leg after the timed region (overlap off, comm-window plans off); 0 skips them")
+                    help="N > 1, --full: steps of each A/B leg after the timed region (overlap off, comm-window plans off); 0 skips them")
     ap.add_argument("--dp-extras-budget-s", type=float, default=120.0,
-                    help="N > 1: wall-clock budget of the extra legs after the headline (configs[4] data-parallel); when it (or the "
+                    help="N > 1, --full: wall-clock budget of the extra legs after the headline (configs[4] data-parallel); when it (or the "
                          "deadline) passes, rank 0 prints the headline line it already holds, marked, and every rank exits 0")
     ap.add_argument("--rehearse-hang", type=str, default="",
                     help="test knob of --rehearse-launch: RANK:STAGE[:gil] (RANK `*` = every rank) -- that rank stops for ever when it reaches STAGE "
@@ -90,6 +99,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.cpu_all_cores and not args.full:
+        ap.error("--cpu-all-cores times the CPU baseline of a --full run")
     return args
 
 
@@ -428,15 +439,18 @@ class _HostStandIn:
 def rehearse_launch(args, world, rank):
     """No GPU: every step of the multi-rank protocol around (and after) the timed region, on CPU tensors over gloo -- the bounded
     rendezvous, the heartbeats, the deadline timer, the stand-alone all-reduce, warm-up, the barrier-bracketed timed steps with
-    max over ranks, the replica check, the comm diagnostics (per-bucket times, A/B legs) and the one JSON line from rank 0."""
+    max over ranks, the replica check, the comm diagnostics (per-bucket times, A/B legs) and the one JSON line from rank 0.  As in
+    main, the stand-alone all-reduce, the comm diagnostics and the extra legs run with --full only."""
     from bayeslms_amd import engine
     timer = arm_deadline(args, rank, world)
     _maybe_hang(args, rank, "rendezvous")
     backend = "gloo" if args.backend == "nccl" else args.backend
     engine.init_distributed(backend, None, args.dist_timeout_s)
     tr = _HostStandIn(engine, rank, world, bool(args.dp_overlap))
-    busbw = [engine.allreduce_busbw(tr.flat.total * 4, 3), engine.allreduce_busbw(1 << 16, 3)]
-    engine.heartbeat("stand-alone all-reduce ok", rank)
+    busbw = None
+    if args.full:
+        busbw = [engine.allreduce_busbw(tr.flat.total * 4, 3), engine.allreduce_busbw(1 << 16, 3)]
+        engine.heartbeat("stand-alone all-reduce ok", rank)
     _maybe_hang(args, rank, "warmup")
     for i in range(args.warmup):
         tr.step(i)
@@ -450,8 +464,10 @@ def rehearse_launch(args, world, rank):
     every = [torch.empty_like(mine) for _ in range(world)]
     dist.all_gather(every, mine)
     identical = all(bool(torch.equal(e, every[0])) for e in every)
-    diag = comm_diagnostics(tr.reducer, tr.step, args.warmup + args.steps, args.comm_ab_steps, None, world)
-    engine.heartbeat("comm diagnostics ok", rank)
+    diag = None
+    if args.full:
+        diag = comm_diagnostics(tr.reducer, tr.step, args.warmup + args.steps, args.comm_ab_steps, None, world)
+        engine.heartbeat("comm diagnostics ok", rank)
     out = None
     if rank == 0:
         args.backend = backend
@@ -459,7 +475,7 @@ def rehearse_launch(args, world, rank):
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
                "comm": comm_block(args, engine, tr.reducer, tr.flat, None, busbw, diag, identical, autotune),
                "rehearsal": "launch plumbing only, no GPU work: NOT a measurement", "baseline_configs": None}
-    if not args.no_extra:  # the protocol of the extra legs (main: configs[4]'s data-parallel legs) around a stand-in leg
+    if args.full and not args.no_extra:  # the protocol of the extra legs (main: configs[4]'s data-parallel legs) around a stand-in leg
         def legs():
             ms2 = _timed_steps(tr.step, 2, args.warmup, None, world)
             return [{"id": "rehearsal_extra_leg", "ms_per_step": ms2}]
@@ -1356,6 +1372,7 @@ def main():
     busbw = None
     if world > 1:
         _eng.heartbeat("model built (%d parameters, %d buckets)" % (tr.flat.total, len(tr.reducer.buckets)), rank)
+    if world > 1 and args.full:
         # stand-alone all-reduces before training: the whole gradient and one 32 MB bucket (gloo rehearsals: 8 MB, the host moves it)
         cap = None if args.backend == "nccl" else (8 << 20)
         busbw = [_eng.allreduce_busbw(min(tr.flat.total * 4, cap or (1 << 62)), 5, dev),
@@ -1403,7 +1420,8 @@ def main():
         nbytes = dump_outputs(args.dump_outputs, loss, last["kl"], tr.flat)
         sys.stderr.write("[bench] last timed step's outputs: %.1f MB in %s\n" % (nbytes / 2**20, args.dump_outputs))
     final_loss = float(loss)
-    if world > 1:
+    # everything below that measures or checks more than the headline runs with --full only
+    if world > 1 and args.full:
         # outside the timed region, every rank: per-bucket brackets of one more step, then the A/B legs (overlap off; comm-window
         # plans off), the windows of the stream re-used
         try:
@@ -1414,13 +1432,13 @@ def main():
     # eval PPL (the other half of BASELINE.json's metric): mean-weight forward on held-out synthetic
     # text exactly as train.py:441-458 (eval batch 20), outside the timed region
     eval_ppl = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import math
         valid = batchify(synthetic_corpus(V, 20 * (4 * T + 1), seed=2222), 20, dev)
         eval_ppl = math.exp(min(engine.evaluate(model, valid, T), 50.0))
 
     chip = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # what THIS chip sustains under matrix load: a bare fp32 MFMA loop (no memory traffic, two waves per SIMD on every CU) timed
         # with HIP events right after the run -- the boxes of the pool differ by up to 10 % here (round 4: 134.8 against 143-147
         # TFLOP/s), and the step follows the clock.  Outside the timed region; context for `roofline` / `step_roofline`, never part of them
@@ -1495,13 +1513,13 @@ def main():
             "kernels_ms": {**{k: round(v["avg_ms"], 4) for k, v in kt_all.items()}, **{k: round(v["avg_ms"], 4) for k, v in kt.items()}},
             "kernels_ms_from": ("sampled_gemm_fwd: HIP events inside the timed region; the others: the last %d warm-up steps" % side_tags)
                                if side_tags else "HIP events inside the timed region",
-            "final_loss": round(final_loss, 4), "eval_ppl": round(eval_ppl, 2),
+            "final_loss": round(final_loss, 4), "eval_ppl": None if eval_ppl is None else round(eval_ppl, 2),
             # rank 0, per step: time the compute stream waited between its last backward kernel and the end of the
             # gradient exchange (bucketed all-reduce + the compact embedding-row exchange); null at N = 1
             "comm_exposed_ms": None if comm_exposed is None else round(comm_exposed, 4),
             "comm": None if world == 1 else comm_block(args, engine, tr.reducer, tr.flat, rccl_env, busbw, diag, replicas_identical, autotune),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(all_cores_live=args.cpu_all_cores)
             except Exception as e:  # noqa: BLE001
@@ -1512,20 +1530,20 @@ def main():
         out["config"]["gemm_mode"] = mode
         if mode != "f32":  # only under an explicit BLM_GEMM_MODE override: say so where the judge looks
             out["dtype"] = "f32 operands split into bf16 parts (%s), fp32 accumulate -- NOT the fp32 parity mode" % mode
-        elif world == 1 and not args.no_opt_in:
+        elif world == 1 and args.full and not args.no_opt_in:
             try:  # an extra: it must never cost the headline line
                 out["opt_in"] = opt_in_modes(model, tr, train, get_batch, steps_total, args, ops, engine)
             except Exception as e:  # noqa: BLE001
                 ops.set_gemm_mode("f32")
                 out["opt_in"] = {"error": repr(e)}
-        if world == 1 and not args.no_extra and mode == "f32":
+        if world == 1 and args.full and not args.no_extra and mode == "f32":
             try:  # extras must never cost the headline line
                 del tr, model
                 torch.cuda.empty_cache()
                 out["extra_configs"] = extra_configs(dev, args, engine, M, ops, out["ms_per_step"])
             except Exception as e:  # noqa: BLE001
                 out["extra_configs"] = {"error": repr(e)}
-    if world > 1 and not args.no_extra:  # configs[4]'s data-parallel legs, every rank
+    if world > 1 and args.full and not args.no_extra:  # configs[4]'s data-parallel legs, every rank
         ex = run_dp_extras(args, _eng, rank, world, out if rank == 0 else None,
                            lambda: dp_extra_configs(dev, args, engine, M, ops, rank, world, tr.reducer))
         if rank == 0:

@@ -46,3 +46,27 @@ def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     assert sum(v.nbytes for v in dump.values()) <= 64 << 20 and dump["params_sample"].shape == dump["grads_sample"].shape
     assert abs(float(dump["loss"][0]) - out["final_loss"]) < 1e-3
     assert out["value"] > 2.0e5  # a silent fallback (vendor / eager path) or a broken kernel shows up here
+
+
+@pytest.mark.skipif(os.environ.get("BLM_GEMM_MODE", "f32") not in ("", "f32"),
+                    reason="the contract line is the fp32 parity mode's; an opt-in GEMM mode relabels dtype / gemm_mode")
+def test_plain_bench_run_measures_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line and nothing that needs runs of its own --
+    no evaluation pass, chip probe, CPU baseline, opt-in modes or extra_configs (those are --full's)."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "train_tokens_per_sec" and out["unit"] == "tokens/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == 3 and out["warmup"] == 2 and out["value"] > 2.0e5
+    assert abs(out["value"] - 3 * 128 * 64 / (out["ms_per_step"] * 3e-3)) < 0.01 * out["value"]
+    assert out["roofline"]["launches"] == 3 and out["step_roofline"]["frac"] > 0
+    assert out["eval_ppl"] is None and out["chip"] is None and out["cpu_baseline"] is None
+    assert "opt_in" not in out and "extra_configs" not in out
+    assert list(out)[-1] == "baseline_configs" and out["baseline_configs"]["configs[2]"]["value"] == out["value"]
+    assert "[bench legend]" not in r.stderr

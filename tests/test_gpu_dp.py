@@ -267,7 +267,7 @@ def test_bench_gpus2_self_launch_rehearsal_on_one_device():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "2", "--batch", "8", "--no-cpu-baseline", "--no-opt-in"],
+                        "--warmup", "2", "--batch", "8", "--no-cpu-baseline", "--no-opt-in", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -318,7 +318,7 @@ def test_bench_four_ranks_on_one_device_agree_on_the_compact_rows():
     for _ in range(2):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(W), "--backend", "gloo", "--steps", str(steps),
                             "--warmup", str(warm), "--batch", str(Bc), "--no-cpu-baseline", "--no-opt-in", "--no-extra", "--comm-ab-steps", "1",
-                            "--deadline-s", "240"], capture_output=True, text=True, timeout=600, env=env)
+                            "--deadline-s", "240", "--full"], capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
         out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
         c = out["comm"]

@@ -317,29 +317,38 @@ def test_bench_under_the_drivers_own_launch_command_with_eight_ranks():
     """The driver does not use `bench.py`'s own launcher: it runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W`.  That command, verbatim, with N = 8 -- the
     world size of BASELINE configs[3], which has never met hardware here -- as a rehearsal on the host (gloo, --rehearse-launch: every
-    stage of the multi-rank run, no GPU work): ONE JSON line from rank 0, all eight ranks through every heartbeat, replicas equal."""
+    stage of the multi-rank run, no GPU work): ONE JSON line from rank 0, all eight ranks through every heartbeat, replicas equal.
+    Both as the plain run (the headline alone) and with --full (+ the stand-alone all-reduce, comm diagnostics, extra legs)."""
     import json
     import subprocess
     import sys
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--rehearse-launch"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1, r.stdout[-3000:]
-    out = json.loads(lines[0])
-    assert out["n_gpus"] == 8 and out["steps"] == 2 and out["warmup"] == 1 and out["value"] is None and "NOT a measurement" in out["rehearsal"]
-    c = out["comm"]
-    assert c["world_seen"] == 8 and c["replicas_identical"] is True and c["autotune"]["picked"] in c["autotune"]["ms"]
-    assert list(out)[-1] == "baseline_configs" and out["extra_configs"][0]["id"] == "rehearsal_extra_leg"  # the post-headline legs ran too
-    err = r.stderr.splitlines()
-    for rank in range(8):
-        for stage in ("rendezvous ok (world 8, backend gloo, timeout 180 s)", "first all-reduce ok", "timed region ok (2 steps)"):
-            assert any(ln.startswith("[blm rank %d +" % rank) and ln.endswith("] " + stage) for ln in err), (rank, stage)
+    for full in (False, True):
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
+               "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
+               "--backend", "gloo", "--rehearse-launch"] + (["--full"] if full else [])
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-3000:]
+        out = json.loads(lines[0])
+        assert out["n_gpus"] == 8 and out["steps"] == 2 and out["warmup"] == 1 and out["value"] is None and "NOT a measurement" in out["rehearsal"]
+        c = out["comm"]
+        assert c["world_seen"] == 8 and c["replicas_identical"] is True and c["autotune"]["picked"] in c["autotune"]["ms"]
+        assert list(out)[-1] == "baseline_configs"
+        if full:
+            assert out["extra_configs"][0]["id"] == "rehearsal_extra_leg"  # the post-headline legs ran too
+            assert len(c["allreduce_standalone"]) == 2 and c["ab_steps"] == 5
+        else:
+            assert "extra_configs" not in out and c["allreduce_standalone"] is None and "buckets_last_step" not in c
+        err = r.stderr.splitlines()
+        for rank in range(8):
+            for stage in ("rendezvous ok (world 8, backend gloo, timeout 180 s)", "first all-reduce ok", "timed region ok (2 steps)"):
+                assert any(ln.startswith("[blm rank %d +" % rank) and ln.endswith("] " + stage) for ln in err), (rank, stage, full)
+            for stage in ("stand-alone all-reduce ok", "comm diagnostics ok", "headline ok; extra legs"):
+                assert any(ln.startswith("[blm rank %d +" % rank) and ln.endswith("] " + stage) for ln in err) == full, (rank, stage, full)
 
 
 def test_bench_self_launches_its_ranks_from_one_process():
@@ -348,7 +357,7 @@ def test_bench_self_launches_its_ranks_from_one_process():
     VERDICT r4 #1: the rehearsal walks every stage of the real multi-rank run (bounded rendezvous, heartbeats, stand-alone
     all-reduce, timed region, replica check, per-bucket brackets, A/B legs) and fills every field of the `comm` block."""
     import json
-    r, _ = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--rehearse-launch", "--dp-autotune", "0"])
+    r, _ = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--rehearse-launch", "--dp-autotune", "0", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -370,7 +379,7 @@ def test_bench_self_launches_its_ranks_from_one_process():
     assert "[blm rank 0 +" in r.stderr and "line printed" in r.stderr
     # --dp-overlap 0: the A/B leg is reported as null, not re-measured under another name
     r, _ = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--rehearse-launch", "--dp-overlap", "0",
-                   "--comm-ab-steps", "2", "--dist-timeout-s", "60"])
+                   "--comm-ab-steps", "2", "--dist-timeout-s", "60", "--full"])
     c = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["comm"]
     assert c["step_ms_no_overlap"] is None and c["ab_steps"] == 2 and c["dist_timeout_s"] == 60.0 and c["overlap"] is False
     # the calibration in front of the timed region (default on): the configured setting and its alternatives timed on every rank with
@@ -378,7 +387,7 @@ def test_bench_self_launches_its_ranks_from_one_process():
     a = c["autotune"]
     assert a["steps_each"] == 3 and set(a["ms"]) == {"as_configured"} and a["picked"] == "as_configured"  # overlap already off, no comm window on the host
     assert c["overlap_in_timed_region"] is False
-    r, _ = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--rehearse-launch", "--comm-ab-steps", "0"])
+    r, _ = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--rehearse-launch", "--comm-ab-steps", "0", "--full"])
     c = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["comm"]
     a = c["autotune"]
     assert set(a["ms"]) == {"as_configured", "overlap_off"} and a["picked"] in a["ms"]
@@ -400,7 +409,7 @@ def test_bench_multi_rank_run_cannot_hang_silently(hang, who_reports):
         deadline + 15 s and prints the line."""
     import json
     r, took = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--rehearse-launch", "--deadline-s", "4",
-                      "--rehearse-hang", hang], timeout=120)
+                      "--rehearse-hang", hang, "--full"], timeout=120)
     assert r.returncode != 0 and took < 60.0, (r.returncode, took)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -427,7 +436,7 @@ def test_bench_extra_legs_of_a_multi_rank_run_cannot_cost_the_headline(hang):
     exit code 0 on every rank -- still exactly one JSON line, with the headline's fields and its `comm` block intact."""
     import json
     argv = ["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--rehearse-launch", "--dp-autotune", "0",
-            "--comm-ab-steps", "0", "--dp-extras-budget-s", "4"]
+            "--comm-ab-steps", "0", "--dp-extras-budget-s", "4", "--full"]
     r, took = _bench(argv + (["--rehearse-hang", hang] if hang else []), timeout=120)
     assert r.returncode == 0 and took < 60.0, (r.returncode, took, r.stderr[-2000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
