@@ -16,7 +16,7 @@ constexpr int TPB = 256;
 // one wave per (t,b) row, 4 rows per block
 __global__ __launch_bounds__(TPB) void embed_fwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ enc,
                                                         const float* __restrict__ pe, float* __restrict__ out, int T,
-                                                        int B, int D, long vocab, float scale, DropKey dk) {
+                                                        int B, int D, long vocab, float scale, DropKey dk, bool vec) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
   if (row >= (long)T * B) return;
@@ -26,7 +26,7 @@ __global__ __launch_bounds__(TPB) void embed_fwd_kernel(const int64_t* __restric
   const float* e = enc + id * D;
   const float* pp = pe ? pe + (long)t * D : nullptr;
   float* o = out + row * D;
-  if ((D & 3) == 0) {
+  if (vec) {  // D % 4 == 0 and enc / pe / out 16-byte aligned (blm_embed_fwd)
     for (int j = lane * 4; j < D; j += 256) {
       float4 v = *reinterpret_cast<const float4*>(e + j);
       float4 q = pp ? *reinterpret_cast<const float4*>(pp + j) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -118,9 +118,9 @@ __global__ __launch_bounds__(TPB) void embed_bwd_det_kernel(const int64_t* __res
 
 // ------------------------------------------------------------------ dropout
 __global__ __launch_bounds__(TPB) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long rows,
-                                                      DropKey dk) {
+                                                      DropKey dk, bool vec) {
   const int B = dk.B, D = dk.D;
-  if ((D & 3) == 0) {
+  if (vec) {  // D % 4 == 0 and x / y 16-byte aligned (blm_dropout, blm_dropout_rows)
     const long d4 = D >> 2, total = rows * B * d4;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
       const long rb = i / d4;
@@ -853,8 +853,10 @@ extern "C" int blm_embed_fwd(const int64_t* ids, const float* enc, const float* 
   if (p > 0.f && !rng) return blm_fail(BLM_ERR_INVALID, "blm_embed_fwd: dropout needs rng");
   if ((long)T * B == 0) return BLM_OK;
   const long rows = (long)T * B;
+  // a view at a storage offset of 1-3 floats has D % 4 == 0 and misaligned rows: the scalar loop (include/bayeslm.h)
+  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(enc) | reinterpret_cast<uintptr_t>(pe) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
   hipLaunchKernelGGL(embed_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(TPB), 0, ST, ids, enc, pe, out, T, B, D,
-                     (long)vocab, scale, make_key(p, rng, B, D, col_offset, global_cols));
+                     (long)vocab, scale, make_key(p, rng, B, D, col_offset, global_cols), vec);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }
@@ -885,8 +887,9 @@ extern "C" int blm_dropout(const float* x, float* y, int rows, int B, int D, flo
   if (p > 0.f && !rng) return blm_fail(BLM_ERR_INVALID, "blm_dropout: dropout needs rng");
   const long n = (long)rows * B * D;
   if (n == 0) return BLM_OK;
+  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, x, y, (long)rows,
-                     make_key(p, rng, B, D, col_offset, global_cols));
+                     make_key(p, rng, B, D, col_offset, global_cols), vec);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }
@@ -899,7 +902,8 @@ extern "C" int blm_dropout_rows(const float* x, float* y, int rows, int row0, in
   if (n == 0) return BLM_OK;
   DropKey dk = make_key(p, rng, B, D, col_offset, global_cols);
   dk.row0 = row0;
-  hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, x, y, (long)rows, dk);
+  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, x, y, (long)rows, dk, vec);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

@@ -27,10 +27,10 @@ static int grid_for(long items) {
 // ------------------------------------------------------------------ out = (p0 a + p1 b) * keep
 __global__ __launch_bounds__(TPB) void mix2_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                        const float* __restrict__ probs, float* __restrict__ out,
-                                                       long rows, DropKey dk) {
+                                                       long rows, DropKey dk, bool vec) {
   const float p0 = probs[0], p1 = probs[1];
   const int B = dk.B, D = dk.D;
-  if ((D & 3) == 0) {
+  if (vec) {  // D % 4 == 0 and every operand 16-byte aligned (mix2_vec)
     const long d4 = D >> 2, total = rows * B * d4;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
       const long rb = i / d4;
@@ -62,12 +62,12 @@ __global__ __launch_bounds__(TPB) void mix2_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ mul_a, float* __restrict__ da,
                                                        float* __restrict__ db, float* __restrict__ partial, long rows,
                                                        DropKey dk, const float* __restrict__ z_b,
-                                                       const float* __restrict__ coef, float* __restrict__ dhk) {
+                                                       const float* __restrict__ coef, float* __restrict__ dhk, bool vec) {
   __shared__ float red[TPB / 64];
   const float p0 = probs[0], p1 = probs[1];
   const int B = dk.B, D = dk.D;
   float sa = 0.f, sb = 0.f;
-  if ((D & 3) == 0) {
+  if (vec) {  // D % 4 == 0 and every operand 16-byte aligned (mix2_vec)
     const long d4 = D >> 2, total = rows * B * d4;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
       const long rb = i / d4;
@@ -215,6 +215,14 @@ __global__ __launch_bounds__(TPB) void adam_kernel(float* __restrict__ p, const 
 using namespace blm;
 #define ST static_cast<hipStream_t>(stream)
 
+// the float4 paths of the mix2 kernels: a contiguous view at a storage offset of 1-3 floats has N % 4 == 0 and misaligned
+// rows, and takes the scalar loops (include/bayeslm.h: misaligned operands are never read as vectors)
+static bool mix2_vec(int N, std::initializer_list<const void*> ps) {
+  uintptr_t bits = 0;
+  for (const void* p : ps) bits |= reinterpret_cast<uintptr_t>(p);
+  return N % 4 == 0 && (bits & 15) == 0;
+}
+
 static int mix_grid(long rows, int B, int N) { return grid_for(((N & 3) == 0 ? (rows * B * N) >> 2 : rows * B * N)); }
 
 extern "C" int64_t blm_mix2_partials(int rows, int B, int N) {
@@ -228,7 +236,7 @@ extern "C" int blm_mix2_fwd(const float* a, const float* b, const float* probs, 
   if (drop_p > 0.f && !rng) return blm_fail(BLM_ERR_INVALID, "blm_mix2_fwd: dropout needs rng");
   if ((long)rows * B * N == 0) return BLM_OK;
   hipLaunchKernelGGL(mix2_fwd_kernel, dim3(mix_grid(rows, B, N)), dim3(TPB), 0, ST, a, b, probs, out, (long)rows,
-                     make_key(drop_p, rng, B, N, col_offset, global_cols));
+                     make_key(drop_p, rng, B, N, col_offset, global_cols), mix2_vec(N, {a, b, out}));
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }
@@ -240,7 +248,8 @@ extern "C" int blm_mix2_bwd(const float* dout, const float* a, const float* b, c
     return blm_fail(BLM_ERR_INVALID, "blm_mix2_bwd: bad arguments");
   if (drop_p > 0.f && !rng) return blm_fail(BLM_ERR_INVALID, "blm_mix2_bwd: dropout needs rng");
   hipLaunchKernelGGL(mix2_bwd_kernel<false>, dim3(mix_grid(rows, B, N)), dim3(TPB), 0, ST, dout, a, b, probs, mul_a, da, db,
-                     partial, (long)rows, make_key(drop_p, rng, B, N, col_offset, global_cols), nullptr, nullptr, nullptr);
+                     partial, (long)rows, make_key(drop_p, rng, B, N, col_offset, global_cols), nullptr, nullptr, nullptr,
+                     mix2_vec(N, {dout, a, b, mul_a, da, db}));
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }
@@ -252,7 +261,8 @@ extern "C" int blm_mix2_gp_bwd(const float* dout, const float* a, const float* b
     return blm_fail(BLM_ERR_INVALID, "blm_mix2_gp_bwd: bad arguments");
   if (drop_p > 0.f && !rng) return blm_fail(BLM_ERR_INVALID, "blm_mix2_gp_bwd: dropout needs rng");
   hipLaunchKernelGGL(mix2_bwd_kernel<true>, dim3(mix_grid(rows, B, N)), dim3(TPB), 0, ST, dout, a, b, probs, mul_a, da, dz_b,
-                     partial, (long)rows, make_key(drop_p, rng, B, N, col_offset, global_cols), z_b, coef, dhk);
+                     partial, (long)rows, make_key(drop_p, rng, B, N, col_offset, global_cols), z_b, coef, dhk,
+                     mix2_vec(N, {dout, a, b, mul_a, da, dz_b, z_b, dhk}));
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

@@ -8,6 +8,11 @@ flat gradient buffer the data-parallel all-reduce works on is filled in place;
 the Functions return ``None`` for parameters.
 
 There is no CPU path: every entry point raises on non-GPU tensors.
+
+What each op accepts: floating operands are fp32 on this process's GPU, anything else raises
+BayesLMError; strided operands are copied, offset ones are read in place through the kernels' scalar loops; a weight that
+is not a contiguous leaf with a contiguous (or no) .grad -- a non-leaf, a strided leaf -- gets its gradient back through
+autograd (`_weight`, `_wgrad_target`), except where an op can only accumulate in place, which then raises at forward.
 """
 import ctypes as C
 import math
@@ -213,17 +218,46 @@ def _init_multi(items):
         check(lib().blm_init_multi(len(part), d, a, b, n, stream()), "blm_init_multi")
 
 
-def _wgrad_target(w):
-    """-> (buffer, accumulate, value_to_return): leaf parameters accumulate in place into .grad and
-    autograd gets None; a non-leaf weight (e.g. a sampled tensor) gets a fresh gradient tensor."""
-    if w.is_leaf:
+def _grad_in_place(w):
+    """May a backward kernel accumulate w's gradient straight into ``w.grad``?  Only when w is the caller's own contiguous
+    leaf and its .grad is absent or a contiguous fp32 GPU tensor.  A non-leaf (``p * 1.0``, a parametrization, the
+    contiguous copy `_weight` made of a strided parameter) would keep a .grad nobody reads, and a strided .grad would be
+    written as if it were contiguous."""
+    if not (w.is_leaf and w.is_contiguous()):
+        return False
+    g = w.grad
+    return g is None or (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous())
+
+
+def _wgrad_target(w, zero=False):
+    """-> (buffer, accumulate, value_to_return): a weight that `_grad_in_place` allows accumulates into .grad and autograd
+    gets None; any other (a sampled tensor, a non-leaf, a copy) gets a fresh gradient tensor that goes back through
+    autograd.  ``zero``: the kernel only accumulates, so the fresh tensor starts at 0."""
+    if _grad_in_place(w):
         return _grad_buf(w), True, None
-    buf = torch.empty_like(w, memory_format=torch.contiguous_format)
+    buf = (torch.zeros if zero else torch.empty)(w.shape, device=w.device, dtype=torch.float32)
     return buf, False, buf
 
 
 def _f32(t, name):
     return dev_tensor(t, name, torch.float32)
+
+
+def _weight(t, name, in_place=False):
+    """The operand guard of a weight-like argument (weights, LayerNorm parameters, positional tables), applied BEFORE the
+    autograd Function sees it: an fp32 tensor on this process's GPU (BayesLMError otherwise: no float64, no host tensor); a
+    non-contiguous one is replaced by its contiguous copy, which autograd links back to the caller's tensor, so the
+    Function's `_wgrad_target` hands the gradient back through autograd.  ``in_place``: the Function can only accumulate
+    into .grad -- a tensor that requires grad and that `_grad_in_place` refuses raises here, before any launch."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        raise BayesLMError("%s must be a tensor, got %s" % (name, type(t).__name__))
+    if in_place and t.requires_grad and torch.is_grad_enabled() and not _grad_in_place(t):
+        raise BayesLMError("%s: this op accumulates its gradient straight into .grad, so it takes a contiguous leaf tensor "
+                           "(whose .grad, if any, is contiguous fp32) only; got a %s" % (
+                               name, "non-leaf tensor" if not t.is_leaf else "strided tensor or .grad"))
+    return _f32(t, name)
 
 
 def _rows2d(t, N, name):
@@ -258,13 +292,28 @@ def _row_chunks(M, ld):
     return [(r, min(M, r + step)) for r in range(0, M, step)]
 
 
+_OWN_PADDED = weakref.WeakValueDictionary()  # storage address -> the storage object of a padded buffer handed out by this module
+
+
 def _padded_rows(lead_shape, N, device):
-    """An (..., N) fp32 tensor whose rows start 16 bytes aligned: a view of a buffer with the row stride rounded up to 4 floats."""
+    """An (..., N) fp32 tensor whose rows start 16 bytes aligned: a view of a buffer with the row stride rounded up to 4 floats.
+    The storage is registered as this module's own: only such storage may have its padding columns written (_Linear)."""
     M = 1
     for d in lead_shape:
         M *= int(d)
     Np = (N + 3) // 4 * 4
-    return torch.empty(M, Np, device=device, dtype=torch.float32)[:, :N].view(*lead_shape, N), Np
+    full = torch.empty(M, Np, device=device, dtype=torch.float32)
+    st = full.untyped_storage()  # torch keeps one Python object per live storage: the weak value dies with the storage
+    _OWN_PADDED[st.data_ptr()] = st
+    return full[:, :N].view(*lead_shape, N), Np
+
+
+def _owns_padded(t):
+    """Is ``t`` a view into a buffer `_padded_rows` allocated?  Any other tensor with the same strides (a narrow view out of
+    torch.cat's backward, say) may hold live data in what looks like padding.  The identity test (not the address alone)
+    keeps a new allocation at a freed buffer's address out."""
+    st = t.untyped_storage()
+    return _OWN_PADDED.get(st.data_ptr()) is st
 
 
 class _P:
@@ -502,7 +551,9 @@ class _Linear(torch.autograd.Function):
         M = x.numel() // K
         dy, ldy = _rows2d(dy, N, "dy")  # the padded rows of an odd vocabulary's logits come back as they went out
         Np = (N + 3) // 4 * 4
-        if (N % 4 and N >= 64 and ldy == Np and ctx.link is None
+        # the padded path writes zeros into dy's padding columns: only for storage this module handed out (its own y, the
+        # gradient buffer of _CrossEntropy(keep=True)), never for a strided gradient whose "padding" is a sibling's data
+        if (N % 4 and N >= 64 and ldy == Np and ctx.link is None and _owns_padded(dy)
                 and (dy.storage_offset() + (M - 1) * Np + Np) * 4 <= dy.untyped_storage().nbytes()):
             return _Linear._backward_padded(ctx, x, w, b, dy, M, N, Np, K)
         dx = None
@@ -523,7 +574,7 @@ class _Linear(torch.autograd.Function):
                 for r0, r1 in _row_chunks(M, ldy):  # one chunk unless dy is 4 GB or more
                     gemm(L.GEMM_NN, dy[r0:r1], w, dx2[r0:r1], r1 - r0, K, N, ldy, K, K)
         dw = db = None
-        fuse_b = w.requires_grad and b is not None and b.requires_grad and b.is_leaf
+        fuse_b = w.requires_grad and b is not None and b.requires_grad and _grad_in_place(b)
         if w.requires_grad:
             buf, acc, dw = _wgrad_target(w)
             x2 = x.view(-1, K)
@@ -560,12 +611,12 @@ class _Linear(torch.autograd.Function):
             x2 = x.view(-1, K)
             for r0, r1 in _row_chunks(M, Np):
                 gemm(L.GEMM_TN, full[r0:r1], x2[r0:r1], dw_p, Np, K, r1 - r0, Np, K, K, accumulate=r0 > 0, colsum_a=db_p)
-            if w.is_leaf:
+            if _grad_in_place(w):
                 _grad_buf(w).add_(dw_p[:N])
             else:
                 dw = dw_p[:N]
             if want_b:
-                if b.is_leaf:
+                if _grad_in_place(b):
                     _grad_buf(b).add_(db_p[:N])
                 else:
                     db = db_p[:N]
@@ -577,7 +628,7 @@ class _Linear(torch.autograd.Function):
 
 
 def linear(x, w, b=None, link=None):
-    w = _f32(w, "weight")
+    w, b = _weight(w, "weight"), _weight(b, "bias")
     if w.dim() != 2 or x.shape[-1] != w.shape[1] or (b is not None and b.numel() != w.shape[0]):
         # the kernels take M = numel / K on trust: a mismatch would read past a buffer instead of raising like F.linear
         raise BayesLMError("linear: input (..., %d) against weight %s%s" % (x.shape[-1], tuple(w.shape),
@@ -621,15 +672,18 @@ class _SampleWeight(torch.autograd.Function):
         rows = mu.shape[0]
         cols = mu.numel() // rows
         v = _variational(lgstd, noise, row_lo, lgstd.shape[0])
-        check(lib().blm_sample_weight_bwd(ptr(dW), rows, cols, C.byref(v), ptr(_grad_buf(mu)) if mu.requires_grad else None,
-                                          ptr(_grad_buf(lgstd)) if lgstd.requires_grad else None, stream()),
-              "blm_sample_weight_bwd")
+        gmu, _, dmu = _wgrad_target(mu, zero=True) if mu.requires_grad else (None, False, None)
+        glg, _, dlg = _wgrad_target(lgstd, zero=True) if lgstd.requires_grad else (None, False, None)
+        check(lib().blm_sample_weight_bwd(ptr(dW), rows, cols, C.byref(v), ptr(gmu), ptr(glg), stream()), "blm_sample_weight_bwd")
         _notify(mu, lgstd)
-        return None, None, None, None
+        return dmu, dlg, None, None
 
 
 def sampled(mu, lgstd, noise, row_lo=0):
     """W = mu with noise on rows [row_lo, row_lo + lgstd.shape[0]); differentiable w.r.t. mu, lgstd."""
+    mu, lgstd = _weight(mu, "mu"), _weight(lgstd, "lgstd")
+    if lgstd.dim() < 1 or mu.dim() < 1 or lgstd.shape[1:] != mu.shape[1:] or not 0 <= row_lo <= mu.shape[0] - lgstd.shape[0]:
+        raise BayesLMError("sampled: lgstd %s does not fit rows [%d, ...) of mu %s" % (tuple(lgstd.shape), row_lo, tuple(mu.shape)))
     return _SampleWeight.apply(mu, lgstd, noise, row_lo)
 
 
@@ -694,6 +748,7 @@ def variational_group(specs):
     over the noisy rows (0 when no item carries a weight).  One launch forward, one backward."""
     if len(specs) > L.VAR_GROUP_MAX or any(sp[0].numel() >= 2 ** 31 or sp[2] is None for sp in specs):
         raise BayesLMError("variational_group: at most %d sampled tensors of < 2^31 elements" % L.VAR_GROUP_MAX)
+    specs = [(_weight(sp[0], "mu", in_place=True), _weight(sp[1], "lgstd", in_place=True)) + tuple(sp[2:]) for sp in specs]
     flat = []
     for sp in specs:
         flat += [sp[0], sp[1]]
@@ -741,19 +796,29 @@ class _BayesLinear(torch.autograd.Function):
                 gemm(L.GEMM_NN, dy, mu, dx, M, K, N, N, K, K, var_b=_variational(lgstd, noise, 0, N))
             else:
                 gemm(L.GEMM_NN, dy, W, dx, M, K, N, N, K, K)
+        dmu = dlg = None
         if mu.requires_grad:
+            gmu, _, dmu = _wgrad_target(mu, zero=True)
             if noise is None:  # eval-mode graph: only the mean gets a gradient
-                gemm(L.GEMM_TN, dy, x, _grad_buf(mu), N, K, M, N, K, K, accumulate=True)
+                gemm(L.GEMM_TN, dy, x, gmu, N, K, M, N, K, K, accumulate=True)
             else:
-                gemm(L.GEMM_TN, dy, x, _grad_buf(mu), N, K, M, N, K, K, accumulate=True,
-                     epilogue=L.EPI_BAYES_WGRAD, C2=_grad_buf(lgstd), wg_mu=mu,
+                glg, _, dlg = _wgrad_target(lgstd, zero=True) if lgstd.requires_grad else (
+                    torch.zeros(lgstd.shape, device=lgstd.device, dtype=torch.float32), False, None)
+                gemm(L.GEMM_TN, dy, x, gmu, N, K, M, N, K, K, accumulate=True,
+                     epilogue=L.EPI_BAYES_WGRAD, C2=glg, wg_mu=mu,
                      var_c=_variational(lgstd, noise, 0, N), kl_lambda=ctx.kl_lambda, kl_inv_n=1.0 / (N * K))
                 _notify(lgstd)
             _notify(mu)
-        return dx, None, None, None, None, None
+        return dx, dmu, dlg, None, None, None
 
 
 def bayes_linear(x, mu, lgstd, noise=None, kl_lambda=0.0, fused=False):
+    mu, lgstd = _weight(mu, "mu"), _weight(lgstd, "lgstd")
+    if x.shape[-1] != mu.shape[-1] or mu.dim() != 2 or lgstd.shape != mu.shape:
+        raise BayesLMError("bayes_linear: input (..., %d) against mu %s and lgstd %s" % (x.shape[-1], tuple(mu.shape), tuple(lgstd.shape)))
+    if fused and (mu.shape[1] % 4 or (mu.data_ptr() | lgstd.data_ptr()) % 16
+                  or (noise is not None and noise.eps is not None and noise.eps.data_ptr() % 16)):
+        fused = False  # the in-loader sampling reads float4s: misaligned operands take the materialising kernels, same numbers
     return _BayesLinear.apply(x, mu, lgstd, noise, kl_lambda, fused)
 
 
@@ -844,6 +909,7 @@ class _FFN(torch.autograd.Function):
 
 
 def ffn(x, w1, b1, w2, b2=None, lgstd2=None, noise=None, kl_lambda=0.0, fused=False, drop=NO_DROP, link=None):
+    w1, b1, w2, b2, lgstd2 = (_weight(t, n, in_place=True) for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2"), (lgstd2, "lgstd2")))
     return _FFN.apply(x, w1, b1, w2, b2, lgstd2, noise, kl_lambda, fused, drop, link)
 
 
@@ -914,6 +980,8 @@ class _FFNGP(torch.autograd.Function):
 
 
 def ffn_gp(x, wg, bg, coef, w2, b2, drop=NO_DROP, link=None):
+    wg, bg, coef = _weight(wg, "wg"), _weight(bg, "bg"), _weight(coef, "coef")  # gradients through _wgrad_target
+    w2, b2 = _weight(w2, "w2", in_place=True), _weight(b2, "b2", in_place=True)
     return _FFNGP.apply(x, wg, bg, coef, w2, b2, drop, link)
 
 
@@ -1033,9 +1101,10 @@ class _AddDropLN(torch.autograd.Function):
         dy = torch.empty_like(s) if drop.on else None
         ws = torch.empty(int(lib().blm_ln_bwd_ws_floats(rows * B, D)), device=s.device, dtype=torch.float32)
         r = drop.rng() if drop.on else None
-        # frozen LayerNorm parameters (architect step): their sums land in a scratch row instead of .grad
-        dgamma = _grad_buf(gamma) if gamma.requires_grad else torch.empty_like(gamma)
-        dbeta = _grad_buf(beta) if beta.requires_grad else torch.empty_like(beta)
+        # frozen LayerNorm parameters (architect step): their sums land in a scratch row instead of .grad; a parameter that is not
+        # the caller's contiguous leaf gets its sums back through autograd (the kernel accumulates: zeroed buffers)
+        dgamma, _, rgamma = _wgrad_target(gamma, zero=True) if gamma.requires_grad else (torch.zeros_like(gamma), False, None)
+        dbeta, _, rbeta = _wgrad_target(beta, zero=True) if beta.requires_grad else (torch.zeros_like(beta), False, None)
         check(lib().blm_add_dropout_ln_bwd(ptr(dout), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dy),
                                            ptr(dgamma), ptr(dbeta), ptr(ws), rows, B, D,
                                            float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
@@ -1045,10 +1114,14 @@ class _AddDropLN(torch.autograd.Function):
         if ctx.link is not None and ctx.needs_input_grad[0]:
             ctx.link.dx = dx  # the branch's first op completes this buffer and returns it as ITS dx (ResidualLink)
             dres = None
-        return dres, (dy if dy is not None else dx), None, None, None, None, None
+        return dres, (dy if dy is not None else dx), rgamma, rbeta, None, None, None
 
 
 def add_dropout_ln(x, y, gamma, beta, eps=1e-5, drop=NO_DROP, link=None):
+    gamma, beta = _weight(gamma, "gamma"), _weight(beta, "beta")
+    if gamma.numel() != x.shape[-1] or beta.numel() != x.shape[-1] or x.shape != y.shape:
+        raise BayesLMError("add_dropout_ln: x %s, y %s, gamma %s, beta %s" % (tuple(x.shape), tuple(y.shape), tuple(gamma.shape),
+                                                                             tuple(beta.shape)))
     return _AddDropLN.apply(x, y, gamma, beta, eps, drop, link)
 
 
@@ -1082,7 +1155,7 @@ class _Embed(torch.autograd.Function):
             T, B = ids.shape
             V, D = weight.shape
             r = drop.rng() if drop.on else None
-            sink = _EMBED_SINK(weight, ids) if (_EMBED_SINK is not None and weight.is_leaf) else None
+            sink = _EMBED_SINK(weight, ids) if (_EMBED_SINK is not None and _grad_in_place(weight)) else None
             if sink is not None:
                 buf, slots, nrows, done = sink
                 check(lib().blm_embed_bwd(ptr(slots), ptr(dy), ptr(buf), T, B, D, int(nrows), float(scale),
@@ -1090,14 +1163,33 @@ class _Embed(torch.autograd.Function):
                                           drop.global_cols or B, stream()), "blm_embed_bwd")
                 done()
                 return None, None, None, None, None
-            check(lib().blm_embed_bwd(ptr(ids), ptr(dy), ptr(_grad_buf(weight)), T, B, D, V, float(scale),
+            gw, _, dw = _wgrad_target(weight, zero=True)
+            check(lib().blm_embed_bwd(ptr(ids), ptr(dy), ptr(gw), T, B, D, V, float(scale),
                                       float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
                                       drop.global_cols or B, stream()), "blm_embed_bwd")
             _notify(weight)
+            return None, dw, None, None, None
         return None, None, None, None, None
 
 
+def _pe_table(pe, D):
+    """The positional table guard: (max_len, D) fp32 on the GPU, and fixed -- its gradient is not computed, so a table that
+    requires grad is refused rather than silently left without one."""
+    if pe is None:
+        return None
+    if pe.requires_grad and torch.is_grad_enabled():
+        raise BayesLMError("the positional table is a fixed buffer here: a pe that requires grad gets no gradient (detach it)")
+    pe = _weight(pe, "pe")
+    if pe.dim() != 2 or pe.shape[1] != D:
+        raise BayesLMError("positional table must be (max_len, %d), got %s" % (D, tuple(pe.shape)))
+    return pe
+
+
 def embed(ids, weight, pe=None, scale=1.0, drop=NO_DROP):
+    weight = _weight(weight, "weight")
+    if weight.dim() != 2:
+        raise BayesLMError("embed: weight must be (V, D), got %s" % (tuple(weight.shape),))
+    pe = _pe_table(pe, weight.shape[1])
     return _Embed.apply(ids, weight, pe, scale, drop)
 
 
@@ -1125,6 +1217,7 @@ class _AddPE(torch.autograd.Function):
 
 def add_pe(x, pe, drop=NO_DROP):
     """drop(x + pe[:T]) with pe a (max_len, D) table (model.py:116-117)."""
+    pe = _pe_table(pe, x.shape[-1])
     return _AddPE.apply(x, pe, drop)
 
 
@@ -1218,6 +1311,11 @@ class _CrossEntropy(torch.autograd.Function):
             return None, None, None, None
         if fuse:
             return logits, None, None, None
+        if not keep:  # the gradient is written over the logits: a second backward would read the first one's gradient
+            if getattr(ctx, "spent", False):
+                raise BayesLMError("cross_entropy: backward ran already and overwrote the logits with their gradient; a second "
+                                   "backward over a retained graph needs keep=True (ops.as_logits + F.cross_entropy)")
+            ctx.spent = True
         g = _f32(g.reshape(1), "g")
         if keep:
             (logits,) = ctx.saved_tensors
@@ -1228,6 +1326,8 @@ class _CrossEntropy(torch.autograd.Function):
             out = logits
         elif ld == V:
             out = torch.empty_like(logits)
+        elif ld == (V + 3) // 4 * 4:  # registered as this module's: ops._Linear may run its padded backward on it
+            out = _padded_rows(logits.shape[:-1], V, logits.device)[0]
         else:
             out = torch.empty(M, ld, device=logits.device, dtype=torch.float32)[:, :V].view(logits.shape)
         check(lib().blm_ce_bwd(ptr(logits), ld, ptr(targets), ptr(lse), ptr(g), 1.0 / M, ptr(out), M, V, stream()),
@@ -1487,16 +1587,22 @@ class _KLMean(torch.autograd.Function):
     def backward(ctx, g):
         mu, lgstd, row_lo, rows, cols, ld, w = ctx.meta
         g = _f32(g.reshape(1), "g")
-        gm, gl = _grad_buf(mu), _grad_buf(lgstd)
+        # the kernel writes both gradients; a tensor that does not require one gets a scratch buffer
+        gm, _, dmu = _wgrad_target(mu, zero=True) if mu.requires_grad else (torch.zeros_like(mu), False, None)
+        gl, _, dlg = _wgrad_target(lgstd, zero=True) if lgstd.requires_grad else (torch.zeros_like(lgstd), False, None)
         check(lib().blm_kl_mean_bwd(mu.data_ptr() + 4 * row_lo * ld, ld, ptr(lgstd), rows, cols, ptr(g), w,
                                     gm.data_ptr() + 4 * row_lo * ld, ld, ptr(gl), stream()), "blm_kl_mean_bwd")
         _notify(mu, lgstd)
-        return None, None, None, None, None
+        return dmu, dlg, None, None, None
 
 
 def kl_mean(mu, lgstd, row_lo=0, minus_one=False, count=None):
     """KL of the rows [row_lo, row_lo+lgstd.shape[0]) of mu against lgstd.  ``count`` replaces the
     element count of the mean (Bayes2LSTM concatenates hh and ih before taking it, model.py:737-740)."""
+    mu, lgstd = _weight(mu, "mu"), _weight(lgstd, "lgstd")
+    if (mu.dim() < 1 or lgstd.dim() < 1 or mu.numel() // max(mu.shape[0], 1) != lgstd.numel() // max(lgstd.shape[0], 1)
+            or not 0 <= row_lo <= mu.shape[0] - lgstd.shape[0]):
+        raise BayesLMError("kl_mean: lgstd %s does not fit rows [%d, ...) of mu %s" % (tuple(lgstd.shape), row_lo, tuple(mu.shape)))
     return _KLMean.apply(mu, lgstd, row_lo, minus_one, count)
 
 
@@ -2563,6 +2669,7 @@ class _GPNN2Steps(torch.autograd.Function):
 
 def gpnn2_steps(x, coef_w, coef_b, fmean, flgstd, noises, acts):
     """(T,B,E) -> (T,B,NO): GPNN2_t(x[t]) with the noise of calls 0..T-1 (``noises`` as for lstm_recurrent_gpnn2)."""
+    fmean, flgstd = _weight(fmean, "fmean", in_place=True), _weight(flgstd, "flgstd", in_place=True)
     return _GPNN2Steps.apply(x, coef_w, coef_b, fmean, flgstd, noises, int(acts))
 
 
@@ -2573,6 +2680,7 @@ def lstm_recurrent_gpnn2_supported(H, n_mc):
 def lstm_recurrent_gpnn2(xw, h0, c0, w_hh, coef_w, coef_b, fmean, flgstd, noises, gate, acts, mode=0):
     """-> (y (T,B,H), hT, cT).  ``noises``: list of T NoiseSpec (training) or None (mean frequencies); ``acts``: bit set of the
     GPNN2's activations in the mixture's slot order (1 tanh, 2 sigmoid, 4 relu, 8 gelu); ``mode``: see _LSTMRecurrentGPNN2."""
+    fmean, flgstd = _weight(fmean, "fmean", in_place=True), _weight(flgstd, "flgstd", in_place=True)
     return _LSTMRecurrentGPNN2.apply(xw, h0, c0, w_hh, coef_w, coef_b, fmean, flgstd, noises, int(gate), int(acts), int(mode))
 
 
@@ -2901,6 +3009,8 @@ class _SearchFFN(torch.autograd.Function):
 
 
 def search_ffn(x, w1, b1, wg, bg, coef, probs, w2, b2, drop=NO_DROP):
+    wg, bg, coef = _weight(wg, "wg"), _weight(bg, "bg"), _weight(coef, "coef")  # gradients through _wgrad_target
+    w1, b1, w2, b2 = (_weight(t, n, in_place=True) for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")))
     return _SearchFFN.apply(x, w1, b1, wg, bg, coef, probs, w2, b2, drop)
 
 
