@@ -1,0 +1,91 @@
+"""Text generation from a trained language model (the word_language_model example's generate.py, which the reference dropped),
+on the incremental key/value-cache path (bayeslms_amd/incremental.py): each new word costs one decode step, not a forward over
+the whole history.
+
+    python -m bayeslms_amd.generate --model-path model.pt --vocabulary words.txt --model Transformer --emsize 512 --nhid 2048 \
+        --nlayers 6 --nhead 8 --words 50 --temperature 1.0 --streams 4 --prompt "the meeting" --outf generated.txt
+
+The model is built from the scorer's flags (compute_sentence_scores.build_models) and loaded as the scorer loads it.  Every stream
+starts from the sentence boundary ``<s>`` followed by the prompt (OOV words map to ``<unk>``); ``--words`` new words are drawn per
+stream (``--temperature 0``: greedy) and written space-separated, one stream per line."""
+import argparse
+import sys
+
+import torch
+
+from . import compute_sentence_scores as S
+from . import ops
+from .incremental import IncrementalLM
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Generate text with a trained neural LM (MI355X engine, incremental decoding).")
+    p.add_argument('--model-path', type=str, required=True)
+    p.add_argument('--vocabulary', type=str, required=True, help='words.txt (word id per line)')
+    p.add_argument('--model', type=str, default='LSTM')
+    p.add_argument('--emsize', type=int, default=1024)
+    p.add_argument('--nhid', type=int, default=1024)
+    p.add_argument('--nlayers', type=int, default=2)
+    p.add_argument('--nhead', type=int, default=8)
+    p.add_argument('--uncertainty', type=str, default='none')
+    p.add_argument('--T_bayes_pos', type=str, default='none')
+    p.add_argument('--L_bayes_pos', type=int, default=0)
+    p.add_argument('--L_gauss_pos', type=str, default='00')
+    p.add_argument('--T_gauss_pos', type=int, default=3)
+    p.add_argument('--L_v_pos', type=str, default='11')
+    p.add_argument('--T_v_pos', type=int, default=0)
+    p.add_argument('--words', type=int, default=100, help='words to generate per stream')
+    p.add_argument('--temperature', type=float, default=1.0, help='0: greedy (argmax, lowest id on ties)')
+    p.add_argument('--seed', type=int, default=1111, help='key of the sampling noise: the same seed gives the same text')
+    p.add_argument('--streams', type=int, default=1, help='independent samples, generated in one batch')
+    p.add_argument('--prompt', type=str, default='', help='words every stream starts from (after <s>)')
+    p.add_argument('--outf', type=str, default='generated.txt', help="output file ('-': stdout)")
+    return p
+
+
+def generate(model, vocab, words, streams=1, temperature=1.0, seed=1111, prompt=""):
+    """-> list of `streams` lists of generated word ids (prompt excluded)."""
+    unk = vocab.get('<unk>')
+    ctx = [vocab['<s>']]
+    for w in prompt.split():
+        if w not in vocab and unk is None:
+            raise SystemExit("prompt word %r is not in the vocabulary, which has no <unk>" % w)
+        ctx.append(vocab.get(w, unk))
+    lm = IncrementalLM(model, max_streams=streams, max_len=len(ctx) + max(words, 1))
+    st = lm.start(streams)
+    dev = lm.device
+    ids = torch.tensor(ctx, dtype=torch.int64).view(-1, 1).expand(-1, streams).contiguous().to(dev)
+    out = torch.empty(max(words, 0), streams, dtype=torch.int64, device=dev)
+    for i in range(words):
+        lp = lm.step(st, ids)
+        nxt = ops.sample_rows(lp, temperature, seed, 0, i)  # shift-invariant: log-probs sample as the logits would
+        out[i] = nxt
+        ids = nxt.view(1, streams)
+    return out.t().cpu().tolist()
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.words < 0 or args.streams < 1 or args.temperature < 0:
+        raise SystemExit("--words >= 0, --streams >= 1 and --temperature >= 0 expected")
+    if not torch.cuda.is_available():
+        raise SystemExit("bayeslms_amd generation needs an MI355X: there is no CPU path")
+    vocab = S.read_vocab(args.vocabulary)
+    if '<s>' not in vocab:
+        raise SystemExit("the vocabulary has no <s>")
+    args.interpolation_flag = 0
+    model, _ = S.build_models(args, len(vocab))
+    S.load_partial(model, args.model_path)
+    model = model.to(torch.device("cuda", torch.cuda.current_device())).eval()
+    ids = generate(model, vocab, args.words, args.streams, args.temperature, args.seed, args.prompt)
+    inv = {i: w for w, i in vocab.items()}
+    text = "".join(" ".join(inv[i] for i in row) + "\n" for row in ids)
+    if args.outf == '-':
+        sys.stdout.write(text)
+    else:
+        with open(args.outf, 'w', encoding='utf-8') as f:
+            f.write(text)
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,311 @@
+"""Incremental next-word scoring and generation: the distribution of the word after each of N word histories without running
+the histories through the model again.
+
+    lm = IncrementalLM(model, max_streams=64, max_len=1024)   # model.eval(), on the GPU
+    st = lm.start(n)                                           # n empty streams
+    lp = lm.step(st, ids)                     # ids (Tq, n) or (n,) int64 -> (n, V) log-probs of the word after each stream
+    lp = lm.step(st, ids, n_new=k)            # ragged chunk: stream j takes its first k[j] rows (prompts of different lengths;
+                                              # 0: the stream takes no part and its row is NaN)
+    lp = lm.step(st, ids, all_positions=True) # (Tq, n, V) (NaN on the padding rows of a ragged chunk)
+    nll = lm.step(st, ids, targets=t)         # NLL of the given next words, no logits stored
+    st = lm.reorder(st, idx)                  # beam prune / fork: new stream j continues old stream idx[j]; `st` is consumed
+    st.lengths                                # host mirror of the per-stream lengths
+
+Transformers (TransformerModel, BayesTransformerModel none / EMB / FFN / MHA, GaussTransformerModel, VTransformerModel) keep a
+key/value cache: the model's own forward runs under ops.cached_tokens, where every attention core appends the chunk's K / V rows
+and attends the cache (blm_kv_append + blm_attn_decode) and the positional encoding starts at each stream's length
+(blm_embed_at).  The decoder product runs on the returned rows only.  The LSTM families carry (h, c) through their ordinary
+fused step kernels.  reorder gathers either state in one launch (blm_kv_gather).
+
+Every length is known on the host (each append is), so a step checks its arguments before any launch and needs no
+host-device synchronisation of its own; the lengths the kernels read stay on the device.  Eval mode is deterministic in every
+family (mean weights; no dropout), which is what makes a cached continuation equal to the full forward over the history.
+Not covered: Monte-Carlo weight samples, two-model interpolation, the architecture-search super-nets.
+"""
+import numpy as np
+import torch
+
+from . import model as M
+from . import ops
+from ._lib import BayesLMError
+
+_TRANSFORMERS = (M.TransformerModel, M.BayesTransformerModel, M.GaussTransformerModel, M.VTransformerModel)
+_LSTMS = (M.RNNModel, M.BayesRNNModel, M.GaussRNNModel, M.VariationalRNNModel)
+_ATTENTION = (M.MultiheadAttention, M.BayesMultiheadAttention, M._TorchMHAParams)
+# a single step() runs at most this many query rows per stream through the attention at once (bounds the split-K workspace);
+# longer chunks are fed in pieces
+_MAX_CHUNK = 256
+
+
+def _host_ints(v, n, what):
+    """A host-side integer vector of length n from an int, a sequence, a numpy array or a CPU tensor (a device tensor would
+    need a synchronising copy: refused)."""
+    if isinstance(v, torch.Tensor):
+        if v.is_cuda:
+            raise BayesLMError("%s must be known on the host (an int, a list or a CPU tensor), not a device tensor" % what)
+        v = v.numpy()
+    a = np.full(n, int(v), dtype=np.int64) if np.isscalar(v) else np.asarray(v, dtype=np.int64).reshape(-1)
+    if a.shape[0] != n:
+        raise BayesLMError("%s: %d entries for %d streams" % (what, a.shape[0], n))
+    return a
+
+
+def _upload(a, device, dtype):
+    """Host array -> device tensor by an asynchronous copy from pinned memory (no host-device synchronisation)."""
+    return _to_device(torch.as_tensor(np.ascontiguousarray(a)), device, dtype)
+
+
+def _to_device(t, device, dtype):
+    """A tensor on the device as ``dtype``; a host tensor goes through pinned memory, so the copy is asynchronous (from pageable
+    memory it would wait for the copy to finish)."""
+    if t.is_cuda:
+        return t.to(device, dtype)
+    return t.to(dtype).pin_memory().to(device, non_blocking=True)
+
+
+class IncrementalState:
+    """N streams of one IncrementalLM.  ``lengths`` is the exact host mirror of the tokens each stream holds."""
+
+    def __init__(self, lm, n, buf):
+        self._lm, self.n, self._buf = lm, int(n), buf
+        self.lengths = [0] * self.n
+
+    def _live(self, lm):
+        if self._lm is not lm:
+            raise BayesLMError("this state belongs to another IncrementalLM")
+        if self._buf is None:
+            raise BayesLMError("this state was consumed by reorder(); continue with the state it returned")
+        return self._buf
+
+
+class IncrementalLM:
+    """Incremental scoring over an eval-mode language model on the GPU (see the module docstring)."""
+
+    def __init__(self, model, max_streams=64, max_len=1024):
+        name = type(model).__name__
+        if type(model).__module__.endswith("model_search_bayes"):
+            raise BayesLMError("IncrementalLM: %s is an architecture-search super-net; derive the searched model first" % name)
+        if isinstance(model, _TRANSFORMERS):
+            self.kind = "transformer"
+        elif isinstance(model, _LSTMS):
+            self.kind = "lstm"
+        else:
+            raise BayesLMError("IncrementalLM: %s is not one of the Transformer or LSTM language model families" % name)
+        if model.training:
+            raise BayesLMError("IncrementalLM: the model is in training mode (call model.eval(): incremental scoring uses mean "
+                               "weights and no dropout)")
+        self.max_streams, self.max_len = int(max_streams), int(max_len)
+        if self.max_streams < 1 or self.max_len < 1:
+            raise BayesLMError("IncrementalLM: max_streams and max_len must be positive")
+        self.model = model
+        self.vocab = model.decoder.weight.shape[0]
+        if self.kind == "transformer":
+            attn = [m for m in model.modules() if isinstance(m, _ATTENTION)]
+            pe_rows = model.pos_encoder.pe.shape[0]
+            if self.max_len > pe_rows:
+                raise BayesLMError("IncrementalLM: max_len %d exceeds the positional table (%d rows)" % (self.max_len, pe_rows))
+            self.layers = len(attn)
+            self.nhead = attn[0].num_heads if attn else 1
+            self.head_dim = model.ninp // self.nhead if attn else 1  # a stack without layers (VTransformerModel v_pos 11) caches nothing
+            if self.head_dim > 128:
+                raise BayesLMError("IncrementalLM: head size %d is not supported by the decode attention (<= 128)" % self.head_dim)
+        else:
+            self.layers, self.hidden = model.nlayers, model.nhid
+        p = next(model.parameters())
+        if not p.is_cuda:
+            raise BayesLMError("IncrementalLM: the model must live on the GPU: bayeslms_amd has no CPU path")
+        self.device = p.device
+        self._spare = None
+
+    # ---------------------------------------------------------------- states
+    def _new_buf(self):
+        b, self._spare = self._spare, None
+        if b is not None:
+            return b
+        if self.kind == "transformer":
+            return ops.KVCache(max(self.layers, 1), self.max_streams, self.nhead, self.max_len, self.head_dim, self.device)
+        return torch.empty(2, self.layers, self.max_streams, self.hidden, device=self.device, dtype=torch.float32)
+
+    def start(self, n):
+        """n empty streams."""
+        n = int(n)
+        if not 1 <= n <= self.max_streams:
+            raise BayesLMError("IncrementalLM.start: %d streams, max_streams is %d" % (n, self.max_streams))
+        buf = self._new_buf()
+        if self.kind == "transformer":
+            buf.past.zero_()
+        else:
+            buf.zero_()  # init_hidden
+        return IncrementalState(self, n, buf)
+
+    def reorder(self, st, idx):
+        """Beam prune / fork: new stream j continues stream idx[j] of ``st`` (idx (m,) int64: host, or one copy to the host;
+        entries may repeat, m <= max_streams).  One gather launch of every layer's state; ``st`` is consumed."""
+        src = st._live(self)
+        if isinstance(idx, torch.Tensor) and idx.is_cuda:
+            idx = idx.cpu()
+        ih = np.asarray(idx.numpy() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64).reshape(-1)
+        m = ih.shape[0]
+        if not 1 <= m <= self.max_streams:
+            raise BayesLMError("IncrementalLM.reorder: %d streams, max_streams is %d" % (m, self.max_streams))
+        if ih.min() < 0 or ih.max() >= st.n:
+            raise BayesLMError("IncrementalLM.reorder: idx out of range [0, %d)" % st.n)
+        dst = self._new_buf()
+        idev = _upload(ih, self.device, torch.int64)
+        with torch.no_grad():
+            if self.kind == "transformer":
+                ops.kv_gather(src.kv, dst.kv, idev, st.n, 2 * src.layers, self.nhead, self.max_len, self.head_dim,
+                              src.past, dst.past)
+            else:
+                ops.kv_gather(src, dst, idev, st.n, 2 * self.layers, 1, 1, self.hidden)
+        out = IncrementalState(self, m, dst)
+        out.lengths = [st.lengths[i] for i in ih]
+        st._buf = None
+        self._spare = src
+        return out
+
+    # ---------------------------------------------------------------- stepping
+    def step(self, st, ids, n_new=None, all_positions=False, targets=None):
+        """Feed ``ids`` (Tq, n) (or (n,): one word per stream) and return the log-probabilities of the next word: (n, V) after each
+        stream's last new token, or (Tq, n, V) with all_positions.  ``n_new``: stream j takes only its first n_new[j] rows
+        (0 <= n_new[j] <= Tq, host-known; a stream with 0 keeps its state and gets NaN rows).  ``targets``: (n,) next words (or (Tq, n) with all_positions) -> their NLL instead."""
+        buf = st._live(self)
+        if self.model.training:
+            raise BayesLMError("IncrementalLM.step: the model is in training mode (call model.eval())")
+        if ids.dim() == 1:
+            ids = ids.unsqueeze(0)
+        if ids.dim() != 2 or ids.shape[1] != st.n:
+            raise BayesLMError("IncrementalLM.step: ids must be (Tq, %d) or (%d,)" % (st.n, st.n))
+        Tq, N = ids.shape
+        if Tq < 1:
+            raise BayesLMError("IncrementalLM.step: empty chunk")
+        k = _host_ints(Tq if n_new is None else n_new, N, "n_new")
+        if k.min() < 0 or k.max() > Tq or k.max() < 1:
+            raise BayesLMError("IncrementalLM.step: n_new must lie in [0, %d], and some stream must take a row" % Tq)
+        after = [a + int(b) for a, b in zip(st.lengths, k)]
+        if max(after) > self.max_len:
+            raise BayesLMError("IncrementalLM.step: a stream would hold %d tokens, max_len is %d" % (max(after), self.max_len))
+        if targets is not None and tuple(targets.shape) != ((Tq, N) if all_positions else (N,)):
+            raise BayesLMError("IncrementalLM.step: targets must be %s" % (((Tq, N),) if all_positions else ((N,),)))
+        ids = _to_device(ids, self.device, torch.int64)
+        ragged = bool((k < Tq).any())
+        with torch.no_grad():
+            rows = []  # (Tq, N, d) hidden rows of the chunk, or packed real rows with their flat indices
+            if self.kind == "transformer":
+                for t0 in range(0, Tq, _MAX_CHUNK):
+                    kk = np.clip(k - t0, 0, min(_MAX_CHUNK, Tq - t0))
+                    if kk.max() == 0:  # only padding left in this piece
+                        break
+                    rows.append((t0, kk, self._transformer_chunk(st, buf, ids[t0:t0 + _MAX_CHUNK], kk)))
+            else:
+                rows.append((0, k, self._lstm_chunk(st, buf, ids, k, ragged)))
+            return self._decode(rows, Tq, N, k, all_positions, targets)
+
+    def _transformer_chunk(self, st, cache, ids, k):
+        """One piece of a chunk through the model under ops.cached_tokens -> (flat row indices t * N + n or None, hidden rows).
+        k[n] may be 0 here (a stream whose rows ended in an earlier piece): it takes no part."""
+        Tq, N = ids.shape
+        ragged = bool((k < Tq).any())
+        sel_h = None
+        if ragged:
+            t = np.arange(Tq)[:, None]
+            sel_h = np.nonzero((t < k[None, :]).reshape(-1))[0]
+        ctx_max = max(a + int(b) for a, b in zip(st.lengths, k))
+        n_new = _upload(k, self.device, torch.int32) if ragged else None
+        sel = _upload(sel_h, self.device, torch.int64) if ragged else None
+        dec = self.model.decoder
+        with ops.cached_tokens(cache, Tq, N, ctx_max, n_new, sel) as ctx:
+            dec.return_input = True
+            try:
+                h = self.model(ids)
+            finally:
+                dec.return_input = False
+            if ctx.layer != self.layers:
+                raise BayesLMError("IncrementalLM: %d attention layers ran, %d expected" % (ctx.layer, self.layers))
+        # the lengths move on only after every layer has appended at the old ones
+        if ragged:
+            cache.past[:N] += n_new
+        else:
+            cache.past[:N] += Tq
+        st.lengths = [a + int(b) for a, b in zip(st.lengths, k)]
+        return sel_h, h.reshape(-1, h.shape[-1])
+
+    def _lstm_chunk(self, st, hc, ids, k, ragged):
+        """(h, c) carried through the model's own fused LSTM kernels: the rows every stream takes (min n_new) as one chunk, then a
+        ragged tail step by step on the streams that still have rows (their states gathered, advanced and scattered back)."""
+        Tq, N = ids.shape
+        h, c = hc[0, :, :N], hc[1, :, :N]
+        p = int(k.min())
+        dec = self.model.decoder
+        dec.return_input = True
+        try:
+            if p > 0:
+                y0, (h2, c2) = self.model(ids[:p], (h.contiguous(), c.contiguous()))
+                h.copy_(h2)
+                c.copy_(c2)
+            if not ragged:
+                out = (None, y0.reshape(-1, y0.shape[-1]))
+            else:
+                y = torch.full((Tq, N, self.hidden), float("nan"), device=self.device)
+                if p > 0:
+                    y[:p] = y0
+                for t in range(p, Tq):
+                    act = np.nonzero(k > t)[0]
+                    if act.shape[0] == 0:
+                        break
+                    a = _upload(act, self.device, torch.int64)
+                    ys, (h2, c2) = self.model(ids[t:t + 1].index_select(1, a), (h.index_select(1, a), c.index_select(1, a)))
+                    h.index_copy_(1, a, h2)
+                    c.index_copy_(1, a, c2)
+                    y[t].index_copy_(0, a, ys.reshape(-1, ys.shape[-1]))
+                out = (None, y.reshape(-1, self.hidden))
+        finally:
+            dec.return_input = False
+        st.lengths = [a + int(b) for a, b in zip(st.lengths, k)]
+        return out
+
+    def _decode(self, pieces, Tq, N, k, all_positions, targets):
+        """Decoder product on the rows that are returned only, then the log-softmax (blm_log_softmax_rows) or the NLL of the
+        targets without logits (blm_linear_nll).  Returned slots without a row (padding, streams with n_new 0) are NaN."""
+        # host map: (t, n) -> row of the concatenated hidden rows (-1: padding)
+        rowof = np.full(Tq * N, -1, dtype=np.int64)
+        xs, base = [], 0
+        for t0, kk, (sel_h, x) in pieces:
+            tp = x.shape[0] // N if sel_h is None else None
+            flat = np.arange(tp * N) if sel_h is None else sel_h
+            rowof[t0 * N + flat] = base + np.arange(flat.shape[0])
+            xs.append(x)
+            base += flat.shape[0]
+        x = xs[0] if len(xs) == 1 else torch.cat(xs, 0)
+        # slots: the returned rows -- (t, n) flat positions with all_positions, else streams; `want` the slots that have a row
+        nslot = Tq * N if all_positions else N
+        if all_positions:
+            want = np.nonzero(rowof >= 0)[0]
+            src = rowof[want]
+        else:
+            want = np.nonzero(k > 0)[0]
+            src = rowof[(k[want] - 1) * N + want]
+        every = want.shape[0] == nslot
+        if np.array_equal(src, np.arange(src[0], src[0] + src.shape[0])):  # full chunks: a slice, no index upload
+            xr = x[int(src[0]):int(src[0]) + src.shape[0]]
+        else:
+            xr = x.index_select(0, _upload(src, self.device, torch.int64))
+        W, b = self.model.decoder.weight, self.model.decoder.bias
+        V = self.vocab
+        widx = None if every else _upload(want, self.device, torch.int64)
+        if targets is not None:
+            tg = _to_device(targets, self.device, torch.int64).reshape(-1)
+            if not every:
+                tg = tg.index_select(0, widx)
+            if ops.linear_nll_supported(W, b):
+                r = ops.linear_nll(xr, W, b, tg)
+            else:
+                lp = ops.log_softmax_rows(ops.linear(xr, W, b), V)
+                r = -lp.gather(1, tg.unsqueeze(1)).squeeze(1)
+            if not every:
+                r = torch.full((nslot,), float("nan"), device=self.device).index_copy_(0, widx, r)
+            return r.view(Tq, N) if all_positions else r
+        lp = ops.log_softmax_rows(ops.linear(xr, W, b), V)
+        if not every:
+            lp = torch.full((nslot, V), float("nan"), device=self.device).index_copy_(0, widx, lp)
+        return lp.view(Tq, N, V) if all_positions else lp

@@ -190,12 +190,18 @@ class PositionalEncoding(_Site):
         return self.pe.view(self.pe.shape[0], self.pe.shape[2])
 
     def forward(self, x):
+        pos = getattr(ops.packing(), "positions", None)  # ops.cached_tokens (incremental decoding): per-stream start offsets
+        if pos is not None:
+            return ops.embed_at(None, None, self.table(), 1.0, pos, x=x)
         if self._torch_drop(self.p):
             return self._dropout(ops.add_pe(x, self.table(), ops.NO_DROP), self.p)
         return ops.add_pe(x, self.table(), self._drop(self.p))
 
     def embed(self, src, weight, scale):
         """drop(embedding(src) * scale + pe): one launch, or -- torch's masks -- the launch without dropout, then the mask."""
+        pos = getattr(ops.packing(), "positions", None)
+        if pos is not None:
+            return ops.embed_at(src, weight, self.table(), scale, pos)
         if self._torch_drop(self.p):
             return self._dropout(ops.embed(src, weight, self.table(), scale, ops.NO_DROP), self.p)
         return ops.embed(src, weight, self.table(), scale, self._drop(self.p))
@@ -821,6 +827,8 @@ class VTransformerModel(_LMHead):
         if not has_mask:
             raise BayesLMError("has_mask=False: the fused attention kernel is causal only")
         x = self.pos_encoder.embed(src, self.encoder.weight, math.sqrt(self.ninp))
+        if ops.packing() is not None:  # only ops.cached_tokens reaches here: the scorer packs supports_packed models only
+            x = ops.packing().pack(x)
         for layer in self.transformerlayers:
             x = layer(x, src_mask=True)
         return self.decoder(x)

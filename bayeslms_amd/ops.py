@@ -1789,6 +1789,152 @@ def packing():
     return getattr(_PACK, "cur", None)
 
 
+# ----------------------------------------------------------------------------
+# incremental decoding: key/value cache, embedding at per-stream positions, log-softmax and sampling of decoder rows
+# (csrc/decode.hip; the public API is bayeslms_amd/incremental.py)
+# ----------------------------------------------------------------------------
+class KVCache:
+    """The device side of an incremental state: ``kv`` (layers, 2, n_cap, nhead, max_len, head_dim) fp32 -- the layout of
+    blm_attn_decode -- and ``past`` (n_cap,) int32, the tokens each stream holds (the first N entries are live)."""
+
+    def __init__(self, layers, n_cap, nhead, max_len, head_dim, device):
+        self.layers, self.n_cap, self.nhead, self.max_len, self.head_dim = layers, n_cap, nhead, max_len, head_dim
+        self.kv = torch.empty(layers, 2, n_cap, nhead, max_len, head_dim, device=device, dtype=torch.float32)
+        self.past = torch.zeros(n_cap, device=device, dtype=torch.int32)
+
+
+class cached_tokens:
+    """Inference helper (bayeslms_amd/incremental.py): inside the context a Transformer forward over ``ids`` (Tq, N) is the
+    continuation of N streams whose earlier tokens are in ``cache`` (a KVCache).  Layers are numbered by the order in which they
+    call ``attention``; each appends its K / V rows at the streams' current lengths (blm_kv_append) and attends the cache
+    (blm_attn_decode).  ``PositionalEncoding`` reads ``positions`` (the streams' start offsets) and embeds there (blm_embed_at).
+    ``n_new`` ((N,) int32 device tensor, or None): a ragged chunk -- rows t >= n_new[n] are padding; ``sel`` ((R,) int64, the
+    flat indices t * N + n of the real rows, ascending) then drops them after the embedding, so no token-wise op runs on padding;
+    the attention core scatters into and gathers from the padded layout.  ``ctx_max``: the host-known largest stream length
+    after this chunk.  The cache's lengths are not advanced here: the caller owns them."""
+
+    def __init__(self, cache, Tq, N, ctx_max, n_new=None, sel=None):
+        self.cache, self.T, self.N, self.ctx_max = cache, int(Tq), int(N), int(ctx_max)
+        self.n_new, self.sel = n_new, sel
+        self.positions = cache.past
+        self.layer = 0
+
+    def __enter__(self):
+        if torch.is_grad_enabled():
+            raise BayesLMError("ops.cached_tokens is an inference-only layout")
+        if getattr(_PACK, "cur", None) is not None:
+            raise BayesLMError("ops.cached_tokens does not nest")
+        _PACK.cur = self
+        return self
+
+    def __exit__(self, *exc):
+        _PACK.cur = None
+        return False
+
+    def pack(self, x):
+        """(Tq, N, W) -> (R, 1, W) real rows of a ragged chunk; a full chunk keeps its (Tq, N, W) shape"""
+        if self.sel is None:
+            return x
+        return x.reshape(self.T * self.N, x.shape[-1]).index_select(0, self.sel).unsqueeze(1)
+
+    def unpack(self, xc):
+        if self.sel is None:
+            return xc
+        out = xc.new_zeros(self.T * self.N, xc.shape[-1])
+        out.index_copy_(0, self.sel, xc.reshape(-1, xc.shape[-1]))
+        return out.view(self.T, self.N, -1)
+
+    def attention(self, q, k, v, nhead):
+        """q / k / v (packed rows, or q = the fused [q|k|v] projection and k = v = None) -> attention output, same row layout."""
+        c = self.cache
+        if self.layer >= c.layers:
+            raise BayesLMError("cached_tokens: the model called attention %d times, the cache holds %d layers" % (self.layer + 1, c.layers))
+        if k is None:
+            qkv = _f32(self.unpack(q), "qkv").contiguous()
+            d = qkv.shape[-1] // 3
+            qq, kk, vv, ld = qkv, qkv[..., d:], qkv[..., 2 * d:], 3 * d
+        else:
+            qq, kk, vv = (_f32(self.unpack(t), n).contiguous() for t, n in ((q, "q"), (k, "k"), (v, "v")))
+            d = ld = qq.shape[-1]
+        if nhead != c.nhead or d != nhead * c.head_dim:
+            raise BayesLMError("cached_tokens: layer %d has %d heads of %d, the cache %d of %d" % (self.layer, nhead, d // nhead, c.nhead,
+                                                                                                  c.head_dim))
+        kv = c.kv[self.layer]
+        self.layer += 1
+        L.require_gfx950()
+        T, N, hd = self.T, self.N, c.head_dim
+        check(lib().blm_kv_append(kk.data_ptr(), vv.data_ptr(), ld, ptr(kv), ptr(c.past), ptr(self.n_new), T, N, c.n_cap, nhead,
+                                  c.max_len, hd, stream()), "blm_kv_append")
+        nws = int(lib().blm_attn_decode_ws_floats(T, N, nhead, self.ctx_max, hd))
+        ws = torch.empty(max(nws, 1), device=qq.device, dtype=torch.float32)
+        out = torch.empty(T, N, d, device=qq.device, dtype=torch.float32)
+        check(lib().blm_attn_decode(qq.data_ptr(), ld, ptr(kv), ptr(c.past), ptr(self.n_new), ptr(out), ptr(ws), nws, T, N, c.n_cap,
+                                    nhead, c.max_len, hd, self.ctx_max, stream()), "blm_attn_decode")
+        return self.pack(out)
+
+
+def embed_at(ids, weight, pe, scale, pos0, x=None):
+    """Inference only: out[t, n] = (ids ? weight[ids[t, n]] * scale : x[t, n]) + pe[pos0[n] + t] (blm_embed_at) -- the embedding
+    and positional encoding of PositionalEncoding.embed / .forward at per-stream offsets ``pos0`` ((N,) int32 device)."""
+    pe = _pe_table(pe, weight.shape[1] if weight is not None else x.shape[-1])
+    if ids is not None:
+        weight = _weight(weight, "weight")
+        ids = dev_tensor(ids, "ids", torch.int64)
+        T, N = ids.shape
+        D, V = weight.shape[1], weight.shape[0]
+    else:
+        x = _f32(x, "x").contiguous()
+        T, N, D = x.shape
+        V = 0
+    if pos0 is None or pos0.dtype != torch.int32 or pos0.numel() < N:
+        raise BayesLMError("embed_at: pos0 must be (N,) int32")
+    out = torch.empty(T, N, D, device=pe.device, dtype=torch.float32)
+    L.require_gfx950()
+    check(lib().blm_embed_at(ptr(ids), ptr(weight) if ids is not None else None, V, float(scale), ptr(x), ptr(pe), pe.shape[0],
+                             ptr(pos0), ptr(out), T, N, D, stream()), "blm_embed_at")
+    return out
+
+
+def log_softmax_rows(x, V=None, out=None):
+    """Row-wise log-softmax of the first V columns of the (R, >= V) matrix x (row stride honoured: padded logit rows) ->
+    (R, V), or in place into ``out`` (blm_log_softmax_rows)."""
+    x = _f32(x, "x")
+    if x.dim() != 2 or x.stride(-1) != 1:
+        raise BayesLMError("log_softmax_rows: a row-major (R, V) matrix expected")
+    R, V = x.shape[0], int(V if V is not None else x.shape[1])
+    out = torch.empty(R, V, device=x.device, dtype=torch.float32) if out is None else out
+    L.require_gfx950()
+    check(lib().blm_log_softmax_rows(ptr(x), x.stride(0), ptr(out), out.stride(0), R, V, stream()), "blm_log_softmax_rows")
+    return out
+
+
+def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0):
+    """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
+    with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64"""
+    x = _f32(x, "x")
+    if x.dim() != 2 or x.stride(-1) != 1:
+        raise BayesLMError("sample_rows: a row-major (R, V) matrix expected")
+    out = torch.empty(x.shape[0], device=x.device, dtype=torch.int64)
+    r = L.rng(seed, stream_id, step)
+    L.require_gfx950()
+    check(lib().blm_sample_rows(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), C.byref(r), ptr(out), stream()),
+          "blm_sample_rows")
+    return out
+
+
+def kv_gather(src, dst, idx, n_src, outer, nhead, max_len, head_dim, len_src=None, len_dst=None):
+    """Beam prune / fork of a state laid out [outer][n_cap][nhead][max_len][head_dim] (blm_kv_gather, one launch): stream j of
+    ``dst`` continues stream idx[j] of ``src``; with lengths, only each panel's live prefix is copied and len_dst[j] = len_src[idx[j]]."""
+    n_cap = src.numel() // (outer * nhead * max_len * head_dim)
+    if dst.numel() != src.numel() or n_cap * outer * nhead * max_len * head_dim != src.numel():
+        raise BayesLMError("kv_gather: source and destination must be two states of the same shape")
+    idx = dev_tensor(idx, "idx", torch.int64)
+    L.require_gfx950()
+    check(lib().blm_kv_gather(ptr(src), ptr(dst), ptr(idx), ptr(len_src), ptr(len_dst), idx.numel(), int(n_src), n_cap, outer, nhead,
+                              max_len, head_dim, stream()), "blm_kv_gather")
+    return dst
+
+
 class state_tap:
     """Inference helper: inside the context every fused LSTM layer forward also records its (h, c) AFTER the time
     steps ``idx`` (int64 device tensor) -- the scorer walks the carry chain of a whole n-best file as one long B = 1

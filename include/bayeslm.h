@@ -449,6 +449,50 @@ int blm_attn_bwd_keep(const float* q, const float* k, const float* v, int64_t ld
                       const float* lse, float* dq, float* dk, float* dv, int64_t ld_dqkv, int T, int B, int nhead, int head_dim,
                       const float* keep, int col_offset, int global_cols, void* stream);
 
+/* --------------------------------------------------------------------------
+ * Incremental decoding with a key/value cache (bayeslms_amd/incremental.py; csrc/decode.hip).  New: the reference rescoring and
+ * training scripts have no such path.  Inference only, no dropout, vector ALU throughout.
+ *
+ * Cache layout, one fp32 allocation per state: [layer][k|v][stream < n_cap][head][t < max_len][head_dim] -- each (stream, head)
+ * owns a contiguous max_len x head_dim panel.  `kv` below is one layer's block (K panels, then the V panels
+ * n_cap * nhead * max_len * head_dim floats later).  `past` (N,) int32: tokens already in each stream's panels.  `n_new` (N,)
+ * int32 (NULL: Tq for every stream): the real rows of a ragged chunk, rows t >= n_new[n] are padding.
+ * ------------------------------------------------------------------------ */
+
+/* Causal attention of Tq new query rows per stream over the cache: row (t, n) attends cache positions [0, past[n] + t], its own
+ * key included (blm_kv_append it first).  q is (Tq, N, ld_q) -- head h at columns [h * head_dim, (h + 1) * head_dim), so the fused
+ * [q|k|v] projection passes as it is; out is (Tq, N, nhead * head_dim), zeros on padding rows.  Scaling and softmax of
+ * blm_attn_fwd without dropout.  Split-K flash decoding: workgroups over (key chunk of 64, stream * head, 16 query rows) leave
+ * per-chunk (max, sum, P.V) partials in ws, a second launch combines them in chunk order (no atomics: bitwise repeatable).
+ * ctx_max: an upper bound of past[n] + n_new[n] over the streams (the caller's host mirror of the lengths); it sizes the grid and
+ * the workspace, keys at positions >= ctx_max are never read.  ws: blm_attn_decode_ws_floats(Tq, N, nhead, ctx_max, head_dim)
+ * floats (0: out of range).  head_dim 1..128 (BLM_ERR_UNSUPPORTED beyond). */
+int64_t blm_attn_decode_ws_floats(int Tq, int N, int nhead, int ctx_max, int head_dim);
+int blm_attn_decode(const float* q, int64_t ld_q, const float* kv, const int32_t* past, const int32_t* n_new, float* out, float* ws,
+                    int64_t ws_floats, int Tq, int N, int n_cap, int nhead, int max_len, int head_dim, int ctx_max, void* stream);
+/* kv[k|v][n][h][past[n] + t][:] = k / v[t, n, h * head_dim : (h + 1) * head_dim] for t < n_new[n] (positions >= max_len are not
+ * written); k / v are (Tq, N, ld_kv) strided views (of the fused projection).  `past` is not advanced: the caller owns it. */
+int blm_kv_append(const float* k, const float* v, int64_t ld_kv, float* kv, const int32_t* past, const int32_t* n_new, int Tq, int N,
+                  int n_cap, int nhead, int max_len, int head_dim, void* stream);
+/* Beam prune / fork, every layer and both K and V in ONE launch: new stream j continues old stream idx[j] (int64, may repeat;
+ * entries outside [0, n_src) copy nothing).  State = `outer` blocks of [stream < n_cap][head][max_len][head_dim]; only the live
+ * prefix len[idx[j]] of each panel is copied (len NULL: whole panels), and len_out[j] = len[idx[j]] when len_out is given.
+ * KV caches: outer = 2 * layers.  LSTM (h, c) rows: outer = 2 * layers, nhead = max_len = 1, head_dim = H, len NULL.  Source and
+ * destination states may not overlap (BLM_ERR_INVALID: double-buffer the state). */
+int blm_kv_gather(const float* src, float* dst, const int64_t* idx, const int32_t* len, int32_t* len_out, int M, int n_src, int n_cap,
+                  int outer, int nhead, int max_len, int head_dim, void* stream);
+/* out[t, n, :] = (ids ? enc[ids[t, n]] * scale : x[t, n, :]) + (pe ? pe[pos0[n] + t] : 0) -- PositionalEncoding.embed / .forward
+ * (model.py:1284,116-117) at per-stream offsets, eval mode.  A row whose id or position is out of range is NaN. */
+int blm_embed_at(const int64_t* ids, const float* enc, int64_t vocab, float scale, const float* x, const float* pe, int pe_rows,
+                 const int32_t* pos0, float* out, int Tq, int N, int D, void* stream);
+/* out[r, :V] = x[r, :V] - logsumexp(x[r, :V]); row strides ldx / ldo >= V (padded vocabulary rows); in place when out == x and
+ * ldo == ldx, any other overlap of x and out is refused. */
+int blm_log_softmax_rows(const float* x, int64_t ldx, float* out, int64_t ldo, int R, int V, void* stream);
+/* One id per row of x (R, V; row stride ldx).  temperature 0: argmax, lowest index on ties.  Otherwise Gumbel-max over
+ * x / temperature with u from Philox: counter (column, row, rng->stream, rng->step), key rng->seed, first word;
+ * u = ((w >> 8) + 0.5) * 2^-24, noise -log(-log u).  The same rng gives the same ids. */
+int blm_sample_rows(const float* x, int64_t ldx, int R, int V, float temperature, const blm_rng* rng, int64_t* out, void* stream);
+
 /* Cross entropy over materialised logits (M, V) (train.py:233,332;
  * compute_sentence_scores_bayes_jianwei.py:168):
  *   nll[m] = logsumexp(logits[m,:]) - logits[m,tgt[m]]
