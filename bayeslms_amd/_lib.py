@@ -130,6 +130,8 @@ SIGNATURES = {
     "blm_linear_nll": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "blm_linear_mc_stats_ws_floats": (_i64, [_i, _i, _i]),
     "blm_linear_mc_stats": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "blm_linear_mc_logprobs_ws_floats": (_i64, [_i, _i, _i]),
+    "blm_linear_mc_logprobs": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "blm_linear_nll2_wcat_floats": (_i64, [_i, _i, _i]),
     "blm_linear_nll2_ws_floats": (_i64, [_i, _i, _i, _i]),
     "blm_linear_nll2": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),

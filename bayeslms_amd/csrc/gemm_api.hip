@@ -85,6 +85,7 @@ extern "C" int blm_gemm(const blm_gemm_args* a, void* stream) {
       break;
     case BLM_EPI_CE_PART: return blm_fail(BLM_ERR_INVALID, "blm_gemm: BLM_EPI_CE_PART is internal to blm_linear_nll");
     case BLM_EPI_MC_PART: return blm_fail(BLM_ERR_INVALID, "blm_gemm: BLM_EPI_MC_PART is internal to blm_linear_mc_stats");
+    case BLM_EPI_MC_LOGP: return blm_fail(BLM_ERR_INVALID, "blm_gemm: BLM_EPI_MC_LOGP is internal to blm_linear_mc_logprobs");
     default: return blm_fail(BLM_ERR_INVALID, "blm_gemm: unknown epilogue");
   }
   const bool samp = a->var_b.lgstd != nullptr;
@@ -243,10 +244,10 @@ __global__ __launch_bounds__(256) void mc_stats_finish_kernel(const float* __res
   if (nll_s && lane < S) nll_s[(long)tok * S + lane] = nl;
   const float a = wave_max(lane < S ? -nl : -INFINITY);
   const float e = wave_sum(lane < S ? __expf(-nl - a) : 0.f);
-  if (lane == 0) {
-    bma[tok] = -(a + (__logf(e) - __logf((float)S)));
-    h_pred[tok] = -hs;
-    mi[tok] = ms / (float)S;
+  if (lane == 0) {  // blm_linear_mc_logprobs may leave any of the three out
+    if (bma) bma[tok] = -(a + (__logf(e) - __logf((float)S)));
+    if (h_pred) h_pred[tok] = -hs;
+    if (mi) mi[tok] = ms / (float)S;
   }
 }
 }  // namespace blm
@@ -295,6 +296,65 @@ extern "C" int blm_linear_mc_stats(const float* x, int64_t ldx, const float* w, 
   if (rc) return rc;
   hipLaunchKernelGGL(mc_stats_finish_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ws, nll_rows, nll_s, bma_nll, h_pred, mi, M, S, sh, gn);
   BLM_HIP(hipGetLastError());
+  return BLM_OK;
+}
+
+// The model average's next-word distribution, kept (include/bayeslm.h): blm_linear_mc_stats with the MC_LOGP epilogue in pass 2,
+// which also stores log pbar.  Pass 1 needs a target per token; without tgt it reads M zeros from the end of the workspace (its
+// per-row NLLs are then not handed out), so the CE_PART launch is the one blm_linear_mc_stats runs.
+extern "C" int64_t blm_linear_mc_logprobs_ws_floats(int M, int S, int V) {
+  const int64_t st = blm_linear_mc_stats_ws_floats(M, S, V);
+  return st ? (st + 3) / 4 * 4 + 2 * (int64_t)M : 0;  // + M int64 zero targets, 16-byte aligned
+}
+
+extern "C" int blm_linear_mc_logprobs(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
+                                      int S, float* logp, int64_t ldo, float* nll_s, float* bma_nll, float* h_pred, float* mi,
+                                      float* ws, int M, int V, int K, void* stream) {
+  if (M < 0 || V <= 0 || K <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: bad shape");
+  if (S < 1 || S > 64) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: S must be in 1..64");
+  if (!logp) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: null output");
+  if (!x || !w || !ws) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: null operand");
+  if (tgt ? !bma_nll : (bma_nll || nll_s))
+    return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: bma_nll goes with tgt (nll_s is optional), neither without it");
+  if (ldx < K || ldw < K) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: leading dimension too small");
+  if (ldo < V) return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_mc_logprobs: ldo < V");
+  if (ldo % 4 != 0 || !aligned16(logp)) return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_mc_logprobs: needs ldo %% 4 == 0 and 16-byte aligned logp");
+  int sh = 0;
+  while ((1 << sh) < S) ++sh;
+  const long R = (long)M << sh;
+  const int Np = (V + 3) / 4 * 4;
+  if (!blm::extents_ok({R, ldx}) || !blm::extents_ok({Np, ldw}) || !blm::extents_ok({R, Np}) || !blm::extents_ok({M, ldo}))
+    return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: extents too large");
+  if (!aligned16(ws) || (bias && !aligned16(bias)))
+    return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_mc_logprobs: needs 16-byte aligned bias / workspace");
+  if (M == 0) return BLM_OK;
+  const int64_t ws_stats = blm_linear_mc_stats_ws_floats(M, S, V);
+  if (!ws_stats) return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: extents too large");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rows = (int)R;
+  float* nll_rows = ws + blm_linear_nll_ws_floats(rows, Np);
+  float* lse_rows = nll_rows + R;
+  if (!tgt) {
+    int64_t* zeros = reinterpret_cast<int64_t*>(ws + (ws_stats + 3) / 4 * 4);
+    BLM_HIP(hipMemsetAsync(zeros, 0, (size_t)M * sizeof(int64_t), st));
+    tgt = zeros;
+  }
+  int rc = linear_nll_launch(x, ldx, w, ldw, bias, tgt, sh, V, nll_rows, lse_rows, ws, rows, Np, K, st);
+  if (rc) return rc;
+  int gn = 0;
+  GemmP p = decoder_params(x, ldx, w, ldw, bias, ws, rows, Np, K, &gn);
+  p.epi = BLM_EPI_MC_LOGP;
+  p.C = logp; p.ldc = ldo;
+  p.ce_nv = V;
+  p.ce_row_shift = sh;
+  p.mc_lse = lse_rows;
+  p.mc_s = S;
+  rc = launch_op<BLM_GEMM_NT, false>(p, st);
+  if (rc) return rc;
+  if (bma_nll || h_pred || mi) {
+    hipLaunchKernelGGL(mc_stats_finish_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ws, nll_rows, nll_s, bma_nll, h_pred, mi, M, S, sh, gn);
+    BLM_HIP(hipGetLastError());
+  }
   return BLM_OK;
 }
 

@@ -54,6 +54,7 @@ struct GemmP {
   float* ce_tlogit;
   int ce_nv;         // CE_PART / MC_PART: columns >= ce_nv are vocabulary padding and enter no statistic (= N for blm_linear_nll)
   int ce_row_shift;  // CE_PART: row r's target is ce_tgt[r >> ce_row_shift]; MC_PART: rows come in token groups of 1 << ce_row_shift
+  // BLM_EPI_MC_LOGP (blm_linear_mc_logprobs) runs MC_PART's body (epi is read there) and also keeps log pbar: C[token * ldc + v]
   // BLM_EPI_MC_PART (blm_linear_mc_stats): per (token group, column tile) sum_v pbar log pbar and sum_s sum_v p (log p - log pbar)
   // go to aux[(token * gn + tile) * 2 + {0, 1}]; mc_lse = the log-sum-exp of every row (the CE_PART pass), mc_s = real samples
   const float* mc_lse;
@@ -645,7 +646,10 @@ __device__ __forceinline__ void epilogue_rows(const GemmP& p, f32x16 (&acc)[WTM]
       // u = 0, W = S, L = 0: exactly zero.  Padding samples (s >= mc_s) and padding columns (>= ce_nv) are never read / masked.
       // From Sp = 16 on there are fewer groups (64 >> sh) than row slots (RPS): the idle slots wait on the busy ones, pass 2 / pass 1
       // = 0.95 / 0.96 / 1.02 / 1.12 at S = 8 / 16 / 32 / 64 (profiles/r06_mc_uncertainty_probe.txt); not split across slots.
+      // MC_LOGP (uniform over the launch): the lane also stores its four log pbar = r + L, which MC_PART only sums -- one
+      // 16-byte store into row `token` of C; the quad holding the last of ce_nv % 4 != 0 columns stores its real ones singly.
       const int sh = p.ce_row_shift, S = p.mc_s;
+      const bool keep = p.epi == BLM_EPI_MC_LOGP;
       const float logS = __logf((float)S);
       const bool valid = col < p.ce_nv;
       const bool in1 = col + 1 < p.ce_nv, in2 = col + 2 < p.ce_nv, in3 = col + 3 < p.ce_nv;
@@ -679,11 +683,23 @@ __device__ __forceinline__ void epilogue_rows(const GemmP& p, f32x16 (&acc)[WTM]
               hs = fmaf(er * W * invS, rr + L, hs);
               ms = fmaf(er, fmaf(-L, W, U), ms);
             }
+            return rr + L;
           };
-          col_terms(r.x, sw.x, su.x, true);
-          col_terms(r.y, sw.y, su.y, in1);
-          col_terms(r.z, sw.z, su.z, in2);
-          col_terms(r.w, sw.w, su.w, in3);
+          float4 lp;
+          lp.x = col_terms(r.x, sw.x, su.x, true);
+          lp.y = col_terms(r.y, sw.y, su.y, in1);
+          lp.z = col_terms(r.z, sw.z, su.z, in2);
+          lp.w = col_terms(r.w, sw.w, su.w, in3);
+          if (keep) {
+            float* d = p.C + (long)(row0 >> sh) * p.ldc + col;
+            if (in3) {
+              store4(d, lp);
+            } else {
+              d[0] = lp.x;
+              if (in1) d[1] = lp.y;
+              if (in2) d[2] = lp.z;
+            }
+          }
         }
 #pragma unroll
         for (int o = TPRW / 2; o > 0; o >>= 1) {
@@ -1350,7 +1366,7 @@ __global__ __launch_bounds__(128 * WGN, WGN == 2 ? 2 : 1) void gemm_f32_kernel(c
       case BLM_EPI_GP_MIX: epilogue_rows<BLM_EPI_GP_MIX, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return;
       case BLM_EPI_MUL_DGP_MIX: epilogue_rows<BLM_EPI_MUL_DGP_MIX, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return;
       case BLM_EPI_CE_PART: epilogue_rows<BLM_EPI_CE_PART, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return;
-      case BLM_EPI_MC_PART:  // blm_linear_mc_stats launches NT products only
+      case BLM_EPI_MC_PART: case BLM_EPI_MC_LOGP:  // blm_linear_mc_stats / _logprobs launch NT products only (one body: MC_LOGP stores more)
         if constexpr (OP == BLM_GEMM_NT) { epilogue_rows<BLM_EPI_MC_PART, WTM, WTN, WGN>(p, acc, smem, m0, n0, wm, wn, li, lh); return; }
         break;
       default: break;
@@ -1413,8 +1429,9 @@ static int launch_cfg(const GemmP& p, hipStream_t st) {
     const bool al = ((reinterpret_cast<uintptr_t>(p.C) | reinterpret_cast<uintptr_t>(p.aux) | reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.C2)) & 15) == 0;
     q.vec_epi = (!q.atomic || q.tail_from > 0) && al && p.N % 4 == 0 && p.ldc % 4 == 0 &&
                 (p.epi == BLM_EPI_NONE || p.epi == BLM_EPI_BIAS || p.epi == BLM_EPI_BIAS_GELU || p.epi == BLM_EPI_MUL_DGELU ||
-                 p.epi == BLM_EPI_GP_MIX || p.epi == BLM_EPI_MUL_DGP_MIX || p.epi == BLM_EPI_CE_PART || p.epi == BLM_EPI_MC_PART);
-    if ((p.epi == BLM_EPI_CE_PART || p.epi == BLM_EPI_MC_PART) && !q.vec_epi)
+                 p.epi == BLM_EPI_GP_MIX || p.epi == BLM_EPI_MUL_DGP_MIX || p.epi == BLM_EPI_CE_PART || p.epi == BLM_EPI_MC_PART ||
+                 p.epi == BLM_EPI_MC_LOGP);
+    if ((p.epi == BLM_EPI_CE_PART || p.epi == BLM_EPI_MC_PART || p.epi == BLM_EPI_MC_LOGP) && !q.vec_epi)
       return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll: needs N % 4 == 0 and 16-byte aligned bias / workspace");
   }
   if (q.atomic && !(p.flags & BLM_GEMM_ACCUMULATE))

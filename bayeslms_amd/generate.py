@@ -7,7 +7,12 @@ the whole history.
 
 The model is built from the scorer's flags (compute_sentence_scores.build_models) and loaded as the scorer loads it.  Every stream
 starts from the sentence boundary ``<s>`` followed by the prompt (OOV words map to ``<unk>``); ``--words`` new words are drawn per
-stream (``--temperature 0``: greedy) and written space-separated, one stream per line."""
+stream (``--temperature 0``: greedy) and written space-separated, one stream per line.
+
+``--mc-samples S`` draws every word from the average of S Monte-Carlo weight samples of a Bayesian / GP model (the distribution
+the n-best scorer's ``--mc-samples`` scores with; ``--mc-seed`` keys the weights, ``--seed`` the sampling noise), and
+``--write-uncertainty PATH`` then writes, per generated word, the predictive entropy of that average and the mutual information
+between the word and the weights."""
 import argparse
 import sys
 
@@ -40,34 +45,62 @@ def build_parser():
     p.add_argument('--streams', type=int, default=1, help='independent samples, generated in one batch')
     p.add_argument('--prompt', type=str, default='', help='words every stream starts from (after <s>)')
     p.add_argument('--outf', type=str, default='generated.txt', help="output file ('-': stdout)")
+    p.add_argument('--mc-samples', type=int, default=0,
+                   help='S > 0: draw every word from the average of S Monte-Carlo weight samples (0: mean weights)')
+    p.add_argument('--mc-seed', type=int, default=1111, help='key of the weight samples (the n-best scorer\'s default)')
+    p.add_argument('--write-uncertainty', type=str, default='', metavar='PATH',
+                   help='with --mc-samples >= 2: one line per stream, in the order of --outf, holding for each generated word '
+                        'the three space-separated fields "word h_pred mi" (3 x --words fields per line, single spaces, no '
+                        'header): the word as written to --outf, then %%.6g of the predictive entropy of the model average and of '
+                        'the mutual information between the word and the weights (nats; the distribution the word was drawn from)')
     return p
 
 
-def generate(model, vocab, words, streams=1, temperature=1.0, seed=1111, prompt=""):
-    """-> list of `streams` lists of generated word ids (prompt excluded)."""
+def generate(model, vocab, words, streams=1, temperature=1.0, seed=1111, prompt="", mc_samples=0, mc_seed=1111, uncertainty=False):
+    """-> list of `streams` lists of generated word ids (prompt excluded); with ``uncertainty`` (mc_samples >= 2) the pair
+    (that, (h_pred, mi)): two (streams, words) float arrays of the distributions the words were drawn from."""
     unk = vocab.get('<unk>')
     ctx = [vocab['<s>']]
     for w in prompt.split():
         if w not in vocab and unk is None:
             raise SystemExit("prompt word %r is not in the vocabulary, which has no <unk>" % w)
         ctx.append(vocab.get(w, unk))
-    lm = IncrementalLM(model, max_streams=streams, max_len=len(ctx) + max(words, 1))
+    lm = IncrementalLM(model, max_streams=streams, max_len=len(ctx) + max(words, 1), mc_samples=mc_samples, seed=mc_seed)
     st = lm.start(streams)
     dev = lm.device
     ids = torch.tensor(ctx, dtype=torch.int64).view(-1, 1).expand(-1, streams).contiguous().to(dev)
     out = torch.empty(max(words, 0), streams, dtype=torch.int64, device=dev)
+    unc = torch.empty(2, max(words, 0), streams, dtype=torch.float32, device=dev)
     for i in range(words):
-        lp = lm.step(st, ids)
+        if uncertainty:
+            lp, u = lm.step(st, ids, return_uncertainty=True)
+            unc[0, i], unc[1, i] = u.h_pred, u.mi
+        else:
+            lp = lm.step(st, ids)  # with mc_samples: log pbar, the model average
         nxt = ops.sample_rows(lp, temperature, seed, 0, i)  # shift-invariant: log-probs sample as the logits would
         out[i] = nxt
         ids = nxt.view(1, streams)
+    if uncertainty:
+        h, mi = unc.cpu().numpy()
+        return out.t().cpu().tolist(), (h.T, mi.T)
     return out.t().cpu().tolist()
+
+
+def write_uncertainty(rows, h_pred, mi, path):
+    """--write-uncertainty: one line per stream, "word h_pred mi" per generated word (%.6g), single spaces, no header."""
+    with open(path, 'w', encoding='utf-8') as f:
+        for r, hs, ms in zip(rows, h_pred, mi):
+            f.write(" ".join("%s %.6g %.6g" % (w, float(a), float(b)) for w, a, b in zip(r, hs, ms)) + "\n")
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.words < 0 or args.streams < 1 or args.temperature < 0:
         raise SystemExit("--words >= 0, --streams >= 1 and --temperature >= 0 expected")
+    if args.mc_samples < 0 or args.mc_samples > 64:
+        raise SystemExit("--mc-samples must lie in 0..64 (got %d)" % args.mc_samples)
+    if args.write_uncertainty and args.mc_samples < 2:  # before the input paths, the model or a device are looked at
+        raise SystemExit("--write-uncertainty needs --mc-samples >= 2 (got --mc-samples %d)" % args.mc_samples)
     if not torch.cuda.is_available():
         raise SystemExit("bayeslms_amd generation needs an MI355X: there is no CPU path")
     vocab = S.read_vocab(args.vocabulary)
@@ -77,8 +110,12 @@ def main(argv=None):
     model, _ = S.build_models(args, len(vocab))
     S.load_partial(model, args.model_path)
     model = model.to(torch.device("cuda", torch.cuda.current_device())).eval()
-    ids = generate(model, vocab, args.words, args.streams, args.temperature, args.seed, args.prompt)
+    ids = generate(model, vocab, args.words, args.streams, args.temperature, args.seed, args.prompt, args.mc_samples, args.mc_seed,
+                   bool(args.write_uncertainty))
     inv = {i: w for w, i in vocab.items()}
+    if args.write_uncertainty:
+        ids, (h_pred, mi) = ids
+        write_uncertainty([[inv[i] for i in row] for row in ids], h_pred, mi, args.write_uncertainty)
     text = "".join(" ".join(inv[i] for i in row) + "\n" for row in ids)
     if args.outf == '-':
         sys.stdout.write(text)

@@ -11,6 +11,10 @@ the histories through the model again.
     st = lm.reorder(st, idx)                  # beam prune / fork: new stream j continues old stream idx[j]; `st` is consumed
     st.lengths                                # host mirror of the per-stream lengths
 
+    lm = IncrementalLM(model, max_streams=64, max_len=1024, mc_samples=8, seed=1111)   # the model average over 8 weight samples
+    lp = lm.step(st, ids)                                   # log pbar, the distribution the n-best scorer's --mc-samples scores with
+    lp, unc = lm.step(st, ids, return_uncertainty=True)     # + McUncertainty(h_pred, mi, nll_s) per returned row
+
 Transformers (TransformerModel, BayesTransformerModel none / EMB / FFN / MHA, GaussTransformerModel, VTransformerModel) keep a
 key/value cache: the model's own forward runs under ops.cached_tokens, where every attention core appends the chunk's K / V rows
 and attends the cache (blm_kv_append + blm_attn_decode) and the positional encoding starts at each stream's length
@@ -20,8 +24,22 @@ fused step kernels.  reorder gathers either state in one launch (blm_kv_gather).
 Every length is known on the host (each append is), so a step checks its arguments before any launch and needs no
 host-device synchronisation of its own; the lengths the kernels read stay on the device.  Eval mode is deterministic in every
 family (mean weights; no dropout), which is what makes a cached continuation equal to the full forward over the history.
-Not covered: Monte-Carlo weight samples, two-model interpolation, the architecture-search super-nets.
+
+mc_samples = S > 0 (default 0: everything above, unchanged): every stream is S streams, one per Monte-Carlo weight sample.  Sample s
+is the model in the n-best scorer's sampling state (train(), dropout off, the GPNN sample flags raised, set_seed(seed),
+set_step(s)): its weights are a pure function of (seed, s), so they are the SAME at every step of a stream and a cached
+continuation still equals the full forward over the history.  step runs the S passes one after the other, each on its own slice
+of the state, and one decoder launch over all S of them returns log pbar = log mean_s p_s (blm_linear_mc_logprobs; many rows
+of a wide model compose it from the logits instead, _MC_FUSED_MAX_ROWS_K), or with targets their NLL under pbar
+(blm_linear_mc_stats).  The sampling state is entered and left inside step: the model is in eval
+mode whenever the caller holds it.  Not covered: two-model interpolation, the architecture-search super-nets, Monte-Carlo
+perplexity in engine.evaluate, and under mc_samples the LSTM cells that draw fresh noise at every time step of a CALL (the
+Variational LSTM's noise rows, the GP-LSTM's random frequencies: such a sample is not one model over a stream).
 """
+import contextlib
+import math
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
@@ -35,6 +53,13 @@ _ATTENTION = (M.MultiheadAttention, M.BayesMultiheadAttention, M._TorchMHAParams
 # a single step() runs at most this many query rows per stream through the attention at once (bounds the split-K workspace);
 # longer chunks are fed in pieces
 _MAX_CHUNK = 256
+# mc_samples: the fused launch (blm_linear_mc_logprobs) runs the decoder product twice and stores no logit; composing ops.linear,
+# ops.log_softmax_rows and torch.logsumexp runs it once and passes S x rows x V floats through memory.  Measured at V 33,000
+# (tools/decode_probe.py --mc-samples, profiles/r06_decode_mc_probe.txt, composed / fused): 512 rows x K 512 1.11, 256 x 1024
+# 1.00, 512 x 1024 0.84 -- the second product outweighs the saved traffic beyond rows x K = 2^18, so the distribution alone is
+# composed from there on (with return_uncertainty the fused launch stays: h_pred and mi cost it 1 % and the composed path
+# several more passes over the logits).
+_MC_FUSED_MAX_ROWS_K = 1 << 18
 
 
 def _host_ints(v, n, what):
@@ -63,8 +88,38 @@ def _to_device(t, device, dtype):
     return t.to(dtype).pin_memory().to(device, non_blocking=True)
 
 
+class McUncertainty(NamedTuple):
+    """Token-level uncertainty of a step with mc_samples (definitions: include/bayeslm.h, blm_linear_mc_stats), shaped like the
+    step's main result -- (n,) or (Tq, n) -- and NaN where that is."""
+    h_pred: torch.Tensor           # predictive entropy of the model average, H[pbar]
+    mi: torch.Tensor               # mutual information between the next word and the weights, mean_s KL(p_s || pbar)
+    nll_s: Optional[torch.Tensor]  # (..., S) NLL of the target under each sample; None without targets
+
+
+class _SampleCache:
+    """Sample s of a KVCache that holds S x n streams sample-major (slot s * n + j): the same allocation entered at slot s * n.
+    The K-to-V distance stays the whole cache's n_cap, so the decode kernels address it as they address the whole."""
+
+    def __init__(self, full, first):
+        self.layers, self.n_cap, self.nhead, self.max_len, self.head_dim = full.layers, full.n_cap, full.nhead, full.max_len, full.head_dim
+        self.kv = full.kv[:, :, first:]
+        self.past = full.past[first:]
+
+
+def _redraws_per_time_step(model):
+    """Name of the first LSTM cell of ``model`` whose training-mode noise is keyed by the time step inside ONE call (the
+    Variational LSTM's noise rows, the GP-LSTM's random frequencies), or None: the other sites are keyed by (seed, step) alone."""
+    for m in model.modules():
+        if isinstance(m, M.VLSTMCell) and m.draws_noise():
+            return type(m).__name__
+        if isinstance(m, M.GPLSTMCell) and isinstance(getattr(m, "gpnn", None), M.GPNN2) and m.gpnn.draws_noise():
+            return type(m).__name__
+    return None
+
+
 class IncrementalState:
-    """N streams of one IncrementalLM.  ``lengths`` is the exact host mirror of the tokens each stream holds."""
+    """N streams of one IncrementalLM.  ``lengths`` is the exact host mirror of the tokens each stream holds.  With mc_samples = S
+    the state holds S x N streams sample-major: sample s of stream j lives in slot s * N + j."""
 
     def __init__(self, lm, n, buf):
         self._lm, self.n, self._buf = lm, int(n), buf
@@ -81,7 +136,16 @@ class IncrementalState:
 class IncrementalLM:
     """Incremental scoring over an eval-mode language model on the GPU (see the module docstring)."""
 
-    def __init__(self, model, max_streams=64, max_len=1024):
+    def __init__(self, model, max_streams=64, max_len=1024, mc_samples=0, seed=1111):
+        """``mc_samples`` = S (0..64; 0: mean weights): score with the average of S Monte-Carlo weight samples keyed by ``seed``
+        (module docstring).  The state is S times the mean-weight one -- per state buffer, of which reorder keeps two:
+            Transformer  max(S, 1) * max_streams * layers * 2 * nhead * max_len * head_dim * 4 bytes
+            LSTM         max(S, 1) * max_streams * layers * 2 * hidden * 4 bytes
+        and a step runs S forward passes one after the other."""
+        self.mc_samples = int(mc_samples)
+        if not 0 <= self.mc_samples <= 64:
+            raise BayesLMError("IncrementalLM: mc_samples must lie in 0..64 (0: mean weights), got %d" % self.mc_samples)
+        self.seed = int(seed)
         name = type(model).__name__
         if type(model).__module__.endswith("model_search_bayes"):
             raise BayesLMError("IncrementalLM: %s is an architecture-search super-net; derive the searched model first" % name)
@@ -116,15 +180,27 @@ class IncrementalLM:
             raise BayesLMError("IncrementalLM: the model must live on the GPU: bayeslms_amd has no CPU path")
         self.device = p.device
         self._spare = None
+        self._mc_dec = None
+        if self.mc_samples > 0:
+            if not M.variational_sites(model):  # the scorer's refusal (compute_sentence_scores.py): S identical passes at S times the cost
+                raise BayesLMError("--mc-samples %d: %s has no variational tensor to sample (mean-weight scoring is "
+                                   "--mc-samples 0)" % (self.mc_samples, name))
+            cell = _redraws_per_time_step(model) if self.kind == "lstm" else None
+            if cell:
+                raise BayesLMError("IncrementalLM: mc_samples on %s: %s draws fresh noise at every time step of a call, so a "
+                                   "sample is not one model over a stream" % (name, cell))
+            # the decoder padded once (an odd vocabulary is copied onto zero rows): weights changed later need a new IncrementalLM
+            self._mc_dec = ops.McDecoder(model.decoder.weight, model.decoder.bias)
 
     # ---------------------------------------------------------------- states
     def _new_buf(self):
         b, self._spare = self._spare, None
         if b is not None:
             return b
+        cap = max(self.mc_samples, 1) * self.max_streams
         if self.kind == "transformer":
-            return ops.KVCache(max(self.layers, 1), self.max_streams, self.nhead, self.max_len, self.head_dim, self.device)
-        return torch.empty(2, self.layers, self.max_streams, self.hidden, device=self.device, dtype=torch.float32)
+            return ops.KVCache(max(self.layers, 1), cap, self.nhead, self.max_len, self.head_dim, self.device)
+        return torch.empty(2, self.layers, cap, self.hidden, device=self.device, dtype=torch.float32)
 
     def start(self, n):
         """n empty streams."""
@@ -151,13 +227,16 @@ class IncrementalLM:
         if ih.min() < 0 or ih.max() >= st.n:
             raise BayesLMError("IncrementalLM.reorder: idx out of range [0, %d)" % st.n)
         dst = self._new_buf()
-        idev = _upload(ih, self.device, torch.int64)
+        S = max(self.mc_samples, 1)
+        # every sample's slice in the one launch: new slot s * m + j continues old slot s * n + idx[j]
+        iall = ih if S == 1 else (np.arange(S, dtype=np.int64)[:, None] * st.n + ih[None, :]).reshape(-1)
+        idev = _upload(iall, self.device, torch.int64)
         with torch.no_grad():
             if self.kind == "transformer":
-                ops.kv_gather(src.kv, dst.kv, idev, st.n, 2 * src.layers, self.nhead, self.max_len, self.head_dim,
+                ops.kv_gather(src.kv, dst.kv, idev, S * st.n, 2 * src.layers, self.nhead, self.max_len, self.head_dim,
                               src.past, dst.past)
             else:
-                ops.kv_gather(src, dst, idev, st.n, 2 * self.layers, 1, 1, self.hidden)
+                ops.kv_gather(src, dst, idev, S * st.n, 2 * self.layers, 1, 1, self.hidden)
         out = IncrementalState(self, m, dst)
         out.lengths = [st.lengths[i] for i in ih]
         st._buf = None
@@ -165,11 +244,15 @@ class IncrementalLM:
         return out
 
     # ---------------------------------------------------------------- stepping
-    def step(self, st, ids, n_new=None, all_positions=False, targets=None):
+    def step(self, st, ids, n_new=None, all_positions=False, targets=None, return_uncertainty=False):
         """Feed ``ids`` (Tq, n) (or (n,): one word per stream) and return the log-probabilities of the next word: (n, V) after each
         stream's last new token, or (Tq, n, V) with all_positions.  ``n_new``: stream j takes only its first n_new[j] rows
-        (0 <= n_new[j] <= Tq, host-known; a stream with 0 keeps its state and gets NaN rows).  ``targets``: (n,) next words (or (Tq, n) with all_positions) -> their NLL instead."""
+        (0 <= n_new[j] <= Tq, host-known; a stream with 0 keeps its state and gets NaN rows).  ``targets``: (n,) next words (or (Tq, n) with all_positions) -> their NLL instead.
+        With mc_samples the distribution is the model average pbar (log pbar; the targets' NLL under pbar), and
+        ``return_uncertainty`` makes the result a pair (that, McUncertainty)."""
         buf = st._live(self)
+        if return_uncertainty and self.mc_samples < 2:
+            raise BayesLMError("IncrementalLM.step: return_uncertainty needs mc_samples >= 2 (got %d)" % self.mc_samples)
         if self.model.training:
             raise BayesLMError("IncrementalLM.step: the model is in training mode (call model.eval())")
         if ids.dim() == 1:
@@ -190,16 +273,55 @@ class IncrementalLM:
         ids = _to_device(ids, self.device, torch.int64)
         ragged = bool((k < Tq).any())
         with torch.no_grad():
-            rows = []  # (Tq, N, d) hidden rows of the chunk, or packed real rows with their flat indices
-            if self.kind == "transformer":
-                for t0 in range(0, Tq, _MAX_CHUNK):
-                    kk = np.clip(k - t0, 0, min(_MAX_CHUNK, Tq - t0))
-                    if kk.max() == 0:  # only padding left in this piece
-                        break
-                    rows.append((t0, kk, self._transformer_chunk(st, buf, ids[t0:t0 + _MAX_CHUNK], kk)))
-            else:
-                rows.append((0, k, self._lstm_chunk(st, buf, ids, k, ragged)))
-            return self._decode(rows, Tq, N, k, all_positions, targets)
+            if self.mc_samples == 0:
+                return self._decode(self._hidden_rows(st, buf, ids, k, ragged), Tq, N, k, all_positions, targets)
+            # S passes, sample s on slots [s * n, (s + 1) * n) of the state; the host lengths move once
+            before, passes = st.lengths, []
+            with self._sampling():
+                for s in range(self.mc_samples):
+                    self.model.set_step(s)
+                    st.lengths = before
+                    if self.kind == "transformer":
+                        part = _SampleCache(buf, s * N)
+                    else:
+                        part = buf[:, :, s * N:]
+                    passes.append(self._hidden_rows(st, part, ids, k, ragged))
+            return self._decode_mc(passes, Tq, N, k, all_positions, targets, return_uncertainty)
+
+    @contextlib.contextmanager
+    def _sampling(self):
+        """The n-best scorer's sampling state (compute_sentence_scores.py): training mode with dropout off, optional sampling
+        flags raised, the weights keyed by this object's seed.  Left as it was entered: eval mode, the caller's seed and step."""
+        model, ns = self.model, self.model.noise_state
+        raised = [m for m in M.variational_sites(model) if getattr(m, "sample", True) is False]
+        saved = (ns.seed, ns.step, ns.auto_step)
+        for m in raised:
+            m.sample = True
+        model.train()
+        ns.dropout_off = True
+        model.set_seed(self.seed)
+        try:
+            yield
+        finally:
+            ns.dropout_off = False
+            model.eval()
+            for m in raised:
+                m.sample = False
+            ns.seed, ns.step, ns.auto_step = saved
+
+    def _hidden_rows(self, st, buf, ids, k, ragged):
+        """One forward over the chunk on the state ``buf`` -> [(first row, rows per stream, (flat indices or None, hidden rows))]"""
+        Tq = ids.shape[0]
+        rows = []  # (Tq, N, d) hidden rows of the chunk, or packed real rows with their flat indices
+        if self.kind == "transformer":
+            for t0 in range(0, Tq, _MAX_CHUNK):
+                kk = np.clip(k - t0, 0, min(_MAX_CHUNK, Tq - t0))
+                if kk.max() == 0:  # only padding left in this piece
+                    break
+                rows.append((t0, kk, self._transformer_chunk(st, buf, ids[t0:t0 + _MAX_CHUNK], kk)))
+        else:
+            rows.append((0, k, self._lstm_chunk(st, buf, ids, k, ragged)))
+        return rows
 
     def _transformer_chunk(self, st, cache, ids, k):
         """One piece of a chunk through the model under ops.cached_tokens -> (flat row indices t * N + n or None, hidden rows).
@@ -264,19 +386,18 @@ class IncrementalLM:
         st.lengths = [a + int(b) for a, b in zip(st.lengths, k)]
         return out
 
-    def _decode(self, pieces, Tq, N, k, all_positions, targets):
-        """Decoder product on the rows that are returned only, then the log-softmax (blm_log_softmax_rows) or the NLL of the
-        targets without logits (blm_linear_nll).  Returned slots without a row (padding, streams with n_new 0) are NaN."""
+    def _returned(self, passes, Tq, N, k, all_positions):
+        """The hidden rows a step returns, of every pass in ``passes`` (all over the same chunk) -> ([rows per pass], slots, slots
+        that have a row, their device indices or None when every slot has one)."""
         # host map: (t, n) -> row of the concatenated hidden rows (-1: padding)
         rowof = np.full(Tq * N, -1, dtype=np.int64)
-        xs, base = [], 0
-        for t0, kk, (sel_h, x) in pieces:
+        base = 0
+        for t0, kk, (sel_h, x) in passes[0]:
             tp = x.shape[0] // N if sel_h is None else None
             flat = np.arange(tp * N) if sel_h is None else sel_h
             rowof[t0 * N + flat] = base + np.arange(flat.shape[0])
-            xs.append(x)
             base += flat.shape[0]
-        x = xs[0] if len(xs) == 1 else torch.cat(xs, 0)
+        xcat = [ps[0][2][1] if len(ps) == 1 else torch.cat([x for _, _, (_, x) in ps], 0) for ps in passes]
         # slots: the returned rows -- (t, n) flat positions with all_positions, else streams; `want` the slots that have a row
         nslot = Tq * N if all_positions else N
         if all_positions:
@@ -287,12 +408,19 @@ class IncrementalLM:
             src = rowof[(k[want] - 1) * N + want]
         every = want.shape[0] == nslot
         if np.array_equal(src, np.arange(src[0], src[0] + src.shape[0])):  # full chunks: a slice, no index upload
-            xr = x[int(src[0]):int(src[0]) + src.shape[0]]
+            xr = [x[int(src[0]):int(src[0]) + src.shape[0]] for x in xcat]
         else:
-            xr = x.index_select(0, _upload(src, self.device, torch.int64))
+            sidx = _upload(src, self.device, torch.int64)
+            xr = [x.index_select(0, sidx) for x in xcat]
+        widx = None if every else _upload(want, self.device, torch.int64)
+        return xr, nslot, every, widx
+
+    def _decode(self, pieces, Tq, N, k, all_positions, targets):
+        """Decoder product on the rows that are returned only, then the log-softmax (blm_log_softmax_rows) or the NLL of the
+        targets without logits (blm_linear_nll).  Returned slots without a row (padding, streams with n_new 0) are NaN."""
+        (xr,), nslot, every, widx = self._returned([pieces], Tq, N, k, all_positions)
         W, b = self.model.decoder.weight, self.model.decoder.bias
         V = self.vocab
-        widx = None if every else _upload(want, self.device, torch.int64)
         if targets is not None:
             tg = _to_device(targets, self.device, torch.int64).reshape(-1)
             if not every:
@@ -309,3 +437,35 @@ class IncrementalLM:
         if not every:
             lp = torch.full((nslot, V), float("nan"), device=self.device).index_copy_(0, widx, lp)
         return lp.view(Tq, N, V) if all_positions else lp
+
+    def _decode_mc(self, passes, Tq, N, k, all_positions, targets, uncertainty):
+        """One decoder launch over the S passes' returned rows: log pbar (blm_linear_mc_logprobs), or with targets their NLL under
+        pbar with no (rows, V) buffer (blm_linear_mc_stats); NaN in the slots without a row, in every array."""
+        xr, nslot, every, widx = self._returned(passes, Tq, N, k, all_positions)
+        W, b = self.model.decoder.weight, self.model.decoder.bias
+        x = torch.stack(xr)
+        S = self.mc_samples
+        lead = (Tq, N) if all_positions else (N,)
+
+        def slots(r):  # (rows, ...) -> the step's shape, NaN where no row is
+            if r is None:
+                return None
+            if not every:
+                r = torch.full((nslot,) + tuple(r.shape[1:]), float("nan"), device=self.device).index_copy_(0, widx, r)
+            return r.view(*lead, *r.shape[1:])
+
+        if targets is not None:
+            tg = _to_device(targets, self.device, torch.int64).reshape(-1)
+            if not every:
+                tg = tg.index_select(0, widx)
+            r = ops.linear_mc_stats(x, W, b, tg, dec=self._mc_dec)
+            main, rec = slots(r.bma_nll), (r.h_pred, r.mi, r.nll_s)
+        elif not uncertainty and (x.shape[1] << (S - 1).bit_length()) * x.shape[2] > _MC_FUSED_MAX_ROWS_K:
+            lp = ops.log_softmax_rows(ops.linear(x.reshape(-1, x.shape[2]), W, b), self.vocab)
+            main, rec = slots(torch.logsumexp(lp.view(S, -1, self.vocab), 0).sub_(math.log(S))), None
+        else:
+            r = ops.linear_mc_logprobs(x, W, b, dec=self._mc_dec, stats=uncertainty)
+            main, rec = slots(r.logp), (r.h_pred, r.mi, None)
+        if not uncertainty:
+            return main
+        return main, McUncertainty(*(slots(t) for t in rec))

@@ -20,7 +20,7 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -1512,6 +1512,70 @@ def linear_mc_stats(x, weight, bias, targets, S=None, dec=None):
         check(lib().blm_linear_mc_stats(ptr(xt), K, ptr(wp), K, ptr(bp), ptr(tgt[a:b]), S, ptr(nll_s[a:b]), ptr(bma[a:b]),
                                         ptr(h[a:b]), ptr(mi[a:b]), ptr(ws), b - a, V, K, stream()), "blm_linear_mc_stats")
     return McStats(nll_s, bma, h, mi)
+
+
+class McLogProbs(NamedTuple):
+    """The model average's next-word distribution over S Monte-Carlo weight samples (include/bayeslm.h, blm_linear_mc_logprobs);
+    the statistics are those of McStats, None where they were not asked for."""
+    logp: torch.Tensor               # (M, V) log pbar: a view of rows padded to 4 floats
+    h_pred: Optional[torch.Tensor]   # (M,) with stats
+    mi: Optional[torch.Tensor]       # (M,) with stats
+    nll_s: Optional[torch.Tensor]    # (M, S) with targets
+    bma_nll: Optional[torch.Tensor]  # (M,) with targets: -logp[m, targets[m]]
+
+
+def linear_mc_logprobs(x, weight, bias, tgt=None, S=None, dec=None, stats=True):
+    """Inference only: log of the sample-averaged next-word distribution, log pbar = log mean_s softmax(x[s] @ weight.T + bias),
+    for every token -- the (M, V) matrix a caller samples from or ranks -- without materialising the S x M x V logits
+    (blm_linear_mc_logprobs: linear_mc_stats' two decoder products, the second one also storing log pbar from its epilogue).
+    ``x``: (S, M, K) as linear_mc_stats takes it; ``dec``: the run's McDecoder; ``stats``: also h_pred and mi; ``tgt`` (M,): also
+    nll_s and bma_nll.  -> McLogProbs; S = 1 gives the log-softmax."""
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        raise BayesLMError("linear_mc_logprobs is an inference-only path (no backward): call it under torch.no_grad()")
+    if dec is not None and (dec.weight is not weight or dec.bias is not bias):
+        raise ValueError("linear_mc_logprobs: dec was built for another decoder")
+    x = _f32(x, "x")
+    if x.dim() != 3:
+        raise ValueError("linear_mc_logprobs: x must be (S, M, K)")
+    S_, M, K = x.shape
+    if S is not None and int(S) != S_:
+        raise ValueError("linear_mc_logprobs: S = %d but x holds %d samples" % (S, S_))
+    S = S_
+    if not 1 <= S <= 64:
+        raise BayesLMError("linear_mc_logprobs: 1..64 samples, got %d" % S)
+    weight = _f32(weight, "weight")
+    if weight.dim() != 2 or weight.shape[1] != K or (tgt is not None and tgt.numel() != M) or (
+            bias is not None and bias.numel() != weight.shape[0]):
+        raise ValueError("linear_mc_logprobs: x (S, M, K), weight (V, K), bias (V,) and M targets expected")
+    if bias is not None:
+        bias = _f32(bias, "bias")
+    L.require_gfx950()
+    V = weight.shape[0]
+    wp, bp = (dec.wp, dec.bp) if dec is not None else _mc_pad(weight, bias)
+    dev = x.device
+    logp, Np = _padded_rows((M,), V, dev)
+    h, mi = ((torch.empty(M, device=dev, dtype=torch.float32) for _ in range(2)) if stats else (None, None))
+    nll_s = bma = None
+    if tgt is not None:
+        tgt = dev_tensor(tgt.reshape(-1), "targets", torch.int64)
+        nll_s = torch.empty(M, S, device=dev, dtype=torch.float32)
+        bma = torch.empty(M, device=dev, dtype=torch.float32)
+    if M == 0:
+        return McLogProbs(logp, h, mi, nll_s, bma)
+    Sp = 1 << (S - 1).bit_length()
+    chunks = _row_chunks(M, Sp * K)  # token chunks whose M * Sp * K * 4 bytes stay under the LDS-DMA loaders' 2^32
+    ws = torch.empty(int(lib().blm_linear_mc_logprobs_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
+    for a, b in chunks:
+        o_tgt, o_nll, o_bma, o_h, o_mi = (None if t is None else ptr(t[a:b]) for t in (tgt, nll_s, bma, h, mi))
+        if S == Sp:
+            xt = x[:, a:b].transpose(0, 1).contiguous()  # token-major
+        else:
+            xt = torch.zeros(b - a, Sp, K, device=dev, dtype=torch.float32)  # samples padded to Sp rows
+            xt[:, :S] = x[:, a:b].transpose(0, 1)
+        check(lib().blm_linear_mc_logprobs(ptr(xt), K, ptr(wp), K, ptr(bp), o_tgt, S, ptr(logp[a:b]), Np, o_nll, o_bma, o_h, o_mi,
+                                           ptr(ws), b - a, V, K, stream()),
+              "blm_linear_mc_logprobs")
+    return McLogProbs(logp, h, mi, nll_s, bma)
 
 
 class InterpDecoder:

@@ -151,7 +151,8 @@ typedef enum blm_epilogue {
   BLM_EPI_GP_MIX = 5,      /* z = acc + bias; aux = z; C = sum_i act_i(z) coef[i,n]     */
   BLM_EPI_MUL_DGP_MIX = 6, /* C = acc * sum_i act_i'(aux) coef[i,n]; C2 (optional) = acc (after dropout) */
   BLM_EPI_CE_PART = 7,     /* internal to blm_linear_nll (blm_gemm refuses it): no C, per-tile softmax partials instead */
-  BLM_EPI_MC_PART = 8      /* internal to blm_linear_mc_stats (blm_gemm refuses it): no C, per-tile uncertainty partials */
+  BLM_EPI_MC_PART = 8,     /* internal to blm_linear_mc_stats (blm_gemm refuses it): no C, per-tile uncertainty partials */
+  BLM_EPI_MC_LOGP = 9      /* internal to blm_linear_mc_logprobs (blm_gemm refuses it): MC_PART, and C = log pbar per token */
 } blm_epilogue;
 
 #define BLM_GEMM_ACCUMULATE 1u /* C (+= C2) accumulate into existing contents */
@@ -249,6 +250,24 @@ int blm_linear_nll(const float* x, int64_t ldx, const float* w, int64_t ldw, con
 int64_t blm_linear_mc_stats_ws_floats(int M, int S, int V);
 int blm_linear_mc_stats(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
                         int S, float* nll_s, float* bma_nll, float* h_pred, float* mi, float* ws, int M, int V, int K, void* stream);
+/* The next-word distribution of the model average, kept: the definitions and the operand layout of blm_linear_mc_stats (x
+ * token-major with Sp rows per token, 1 <= S <= 64, w / bias of Np = V rounded up to 4 rows, columns >= V enter nothing, bias
+ * may be NULL), and for token m
+ *   logp[m,v] = log pbar[v] = log((1/S) sum_s exp(z[s,v] - lse_s)),  v < V      (S = 1: the log-softmax of the row)
+ * into the (M, ldo) fp32 buffer logp: ldo >= V, ldo % 4 == 0, 16-byte aligned (BLM_ERR_UNSUPPORTED otherwise); columns >= V of
+ * a row (padding) are left unwritten.  h_pred and mi (M each) are optional (NULL: not stored).  tgt is optional too: when given,
+ * bma_nll (M, required then) and nll_s (M x S, may be NULL) are filled as blm_linear_mc_stats fills them -- a target outside
+ * [0, V) gives NaN for that token's two values only; without tgt both must be NULL.
+ * blm_linear_mc_stats' two launches with one more store: pass 2's epilogue forms log pbar = r + L for every (token, column) in
+ * registers for the two partial sums anyway, and here each lane also writes its four columns of it (one 16-byte store; the
+ * quad that holds column V - 1 of an odd vocabulary stores its real columns one by one).  One K slice, fixed-order folds:
+ * bit-identical run to run in every mode.  S * M * V logits are never stored; the M * V result is what a caller samples from,
+ * ranks or keeps (bayeslms_amd/incremental.py with mc_samples).
+ * ws: blm_linear_mc_logprobs_ws_floats(M, S, V) floats (0: extents out of range), 16-byte aligned, owned by the caller. */
+int64_t blm_linear_mc_logprobs_ws_floats(int M, int S, int V);
+int blm_linear_mc_logprobs(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const int64_t* tgt,
+                           int S, float* logp, int64_t ldo, float* nll_s, float* bma_nll, float* h_pred, float* mi, float* ws,
+                           int M, int V, int K, void* stream);
 /* Two-model scoring, reference compute_sentence_scores_bayes_jianwei.py:157-168: per-row NLL of the INTERPOLATED logits
  * alpha * (x1 w1^T + b1) + (1 - alpha) * (x2 w2^T + b2) against tgt, as ONE decoder + cross-entropy launch over the packed
  * operands [alpha x1 | (1 - alpha) x2] (M x (K1 + K2)) and [w1 | w2] (N x (K1 + K2)): neither model's (M x N) logits are stored.
