@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BLM_LIB") or os.path.join(_HERE, "libbayeslm_hip.so")
 
 ABI_VERSION = 1
+TOPK_MAX = 256  # BLM_TOPK_MAX (include/bayeslm.h)
 OK = 0
 ERR_INVALID, ERR_ABI, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4  # blm_status (include/bayeslm.h)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -124,6 +125,9 @@ SIGNATURES = {
     "blm_embed_at": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "blm_log_softmax_rows": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp]),
     "blm_sample_rows": (_i, [_vp, _i64, _i, _i, _f, _rngp, _vp, _vp]),
+    "blm_topk_rows": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    "blm_beam_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "blm_sample_rows_filtered": (_i, [_vp, _i64, _i, _i, _f, _i, _f, _rngp, _vp, _vp]),
     "blm_ce_fwd_bwd": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
     "blm_ce_interp_fwd": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _i, _i, _vp]),
     "blm_linear_nll_ws_floats": (_i64, [_i, _i]),

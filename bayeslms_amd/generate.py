@@ -12,7 +12,14 @@ stream (``--temperature 0``: greedy) and written space-separated, one stream per
 ``--mc-samples S`` draws every word from the average of S Monte-Carlo weight samples of a Bayesian / GP model (the distribution
 the n-best scorer's ``--mc-samples`` scores with; ``--mc-seed`` keys the weights, ``--seed`` the sampling noise), and
 ``--write-uncertainty PATH`` then writes, per generated word, the predictive entropy of that average and the mutual information
-between the word and the weights."""
+between the word and the weights.
+
+``--top-k K`` / ``--top-p P`` restrict every draw to the K most probable words and / or to the smallest set of most probable
+words whose probability reaches P (blm_sample_rows_filtered; the same noise as the unrestricted draw).  ``--beam B`` searches
+instead of sampling (IncrementalLM.beam_search; a hypothesis ends at the sentence boundary ``<s>``): the ``--nbest`` N (default 1)
+best continuations of the prompt are written best first, one per line, ranked by score / length ** ``--length-penalty``, and
+``--write-scores PATH`` writes one "rank score length" line per hypothesis.  With ``--mc-samples`` the search runs under the
+model average."""
 import argparse
 import sys
 
@@ -40,7 +47,18 @@ def build_parser():
     p.add_argument('--L_v_pos', type=str, default='11')
     p.add_argument('--T_v_pos', type=int, default=0)
     p.add_argument('--words', type=int, default=100, help='words to generate per stream')
-    p.add_argument('--temperature', type=float, default=1.0, help='0: greedy (argmax, lowest id on ties)')
+    p.add_argument('--temperature', type=float, default=None, help='default 1.0; 0: greedy (argmax, lowest id on ties)')
+    p.add_argument('--top-k', type=int, default=None, metavar='K', help='sample among the K most probable words only (0: all)')
+    p.add_argument('--top-p', type=float, default=None, metavar='P',
+                   help='sample among the smallest set of most probable words whose probability reaches P, in (0, 1] (1: all)')
+    p.add_argument('--beam', type=int, default=0, metavar='B',
+                   help='B > 0: beam search with B beams instead of sampling; at most --words words per hypothesis, ended by <s>')
+    p.add_argument('--nbest', type=int, default=1, metavar='N', help='with --beam: write the N best hypotheses (N <= B)')
+    p.add_argument('--length-penalty', type=float, default=0.0, metavar='A',
+                   help='with --beam: the final ranking is by score / length ** A (the search itself is by raw score)')
+    p.add_argument('--write-scores', type=str, default='', metavar='PATH',
+                   help='with --beam: one line "rank score length" per written hypothesis (rank from 1, score %%.6f: its '
+                        'cumulative log-probability including the closing <s>, length in words including it)')
     p.add_argument('--seed', type=int, default=1111, help='key of the sampling noise: the same seed gives the same text')
     p.add_argument('--streams', type=int, default=1, help='independent samples, generated in one batch')
     p.add_argument('--prompt', type=str, default='', help='words every stream starts from (after <s>)')
@@ -56,15 +74,30 @@ def build_parser():
     return p
 
 
-def generate(model, vocab, words, streams=1, temperature=1.0, seed=1111, prompt="", mc_samples=0, mc_seed=1111, uncertainty=False):
-    """-> list of `streams` lists of generated word ids (prompt excluded); with ``uncertainty`` (mc_samples >= 2) the pair
-    (that, (h_pred, mi)): two (streams, words) float arrays of the distributions the words were drawn from."""
+def _context(vocab, prompt):
+    """<s> followed by the prompt's word ids (OOV -> <unk>)"""
     unk = vocab.get('<unk>')
     ctx = [vocab['<s>']]
     for w in prompt.split():
         if w not in vocab and unk is None:
             raise SystemExit("prompt word %r is not in the vocabulary, which has no <unk>" % w)
         ctx.append(vocab.get(w, unk))
+    return ctx
+
+
+def beam_generate(model, vocab, words, beam, nbest=1, prompt="", length_penalty=0.0, mc_samples=0, mc_seed=1111):
+    """-> the ``nbest`` best BeamHypothesis of a ``beam``-wide search for at most ``words`` words after <s> + prompt, best first;
+    a hypothesis ends at the sentence boundary <s>."""
+    ctx = _context(vocab, prompt)
+    lm = IncrementalLM(model, max_streams=beam, max_len=len(ctx) + words, mc_samples=mc_samples, seed=mc_seed)
+    return lm.beam_search([ctx], beam, words, vocab['<s>'], length_penalty)[0][:nbest]
+
+
+def generate(model, vocab, words, streams=1, temperature=1.0, seed=1111, prompt="", mc_samples=0, mc_seed=1111, uncertainty=False,
+             top_k=0, top_p=1.0):
+    """-> list of `streams` lists of generated word ids (prompt excluded); with ``uncertainty`` (mc_samples >= 2) the pair
+    (that, (h_pred, mi)): two (streams, words) float arrays of the distributions the words were drawn from."""
+    ctx = _context(vocab, prompt)
     lm = IncrementalLM(model, max_streams=streams, max_len=len(ctx) + max(words, 1), mc_samples=mc_samples, seed=mc_seed)
     st = lm.start(streams)
     dev = lm.device
@@ -77,7 +110,7 @@ def generate(model, vocab, words, streams=1, temperature=1.0, seed=1111, prompt=
             unc[0, i], unc[1, i] = u.h_pred, u.mi
         else:
             lp = lm.step(st, ids)  # with mc_samples: log pbar, the model average
-        nxt = ops.sample_rows(lp, temperature, seed, 0, i)  # shift-invariant: log-probs sample as the logits would
+        nxt = ops.sample_rows(lp, temperature, seed, 0, i, top_k, top_p)  # shift-invariant: log-probs sample as the logits would
         out[i] = nxt
         ids = nxt.view(1, streams)
     if uncertainty:
@@ -95,6 +128,23 @@ def write_uncertainty(rows, h_pred, mi, path):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.beam:  # before the input paths, the model or a device are looked at
+        given = [f for f, v in (("--temperature", args.temperature), ("--top-k", args.top_k), ("--top-p", args.top_p)) if v is not None]
+        if given:
+            raise SystemExit("--beam searches, it does not sample: %s cannot be given with it" % ", ".join(given))
+        if args.streams != 1:
+            raise SystemExit("--beam writes the hypotheses of ONE search: --streams %d cannot be given with it" % args.streams)
+        if args.write_uncertainty:
+            raise SystemExit("--write-uncertainty belongs to sampling; --beam has --write-scores")
+        if args.beam < 0 or not 1 <= args.nbest <= args.beam or args.words < 1:
+            raise SystemExit("--beam >= 1, 1 <= --nbest <= --beam and --words >= 1 expected")
+    elif args.nbest != 1 or args.length_penalty != 0.0 or args.write_scores:
+        raise SystemExit("--nbest, --length-penalty and --write-scores need --beam")
+    args.temperature = 1.0 if args.temperature is None else args.temperature
+    args.top_k = 0 if args.top_k is None else args.top_k
+    args.top_p = 1.0 if args.top_p is None else args.top_p
+    if args.top_k < 0 or not 0.0 < args.top_p <= 1.0:
+        raise SystemExit("--top-k >= 0 and --top-p in (0, 1] expected")
     if args.words < 0 or args.streams < 1 or args.temperature < 0:
         raise SystemExit("--words >= 0, --streams >= 1 and --temperature >= 0 expected")
     if args.mc_samples < 0 or args.mc_samples > 64:
@@ -110,9 +160,17 @@ def main(argv=None):
     model, _ = S.build_models(args, len(vocab))
     S.load_partial(model, args.model_path)
     model = model.to(torch.device("cuda", torch.cuda.current_device())).eval()
-    ids = generate(model, vocab, args.words, args.streams, args.temperature, args.seed, args.prompt, args.mc_samples, args.mc_seed,
-                   bool(args.write_uncertainty))
     inv = {i: w for w, i in vocab.items()}
+    if args.beam:
+        hyps = beam_generate(model, vocab, args.words, args.beam, args.nbest, args.prompt, args.length_penalty, args.mc_samples,
+                             args.mc_seed)
+        ids = [h.tokens for h in hyps]
+        if args.write_scores:
+            with open(args.write_scores, 'w', encoding='utf-8') as f:
+                f.write("".join("%d %.6f %d\n" % (r + 1, h.score, h.length) for r, h in enumerate(hyps)))
+    else:
+        ids = generate(model, vocab, args.words, args.streams, args.temperature, args.seed, args.prompt, args.mc_samples,
+                       args.mc_seed, bool(args.write_uncertainty), args.top_k, args.top_p)
     if args.write_uncertainty:
         ids, (h_pred, mi) = ids
         write_uncertainty([[inv[i] for i in row] for row in ids], h_pred, mi, args.write_uncertainty)

@@ -10,6 +10,9 @@ the histories through the model again.
     nll = lm.step(st, ids, targets=t)         # NLL of the given next words, no logits stored
     st = lm.reorder(st, idx)                  # beam prune / fork: new stream j continues old stream idx[j]; `st` is consumed
     st.lengths                                # host mirror of the per-stream lengths
+    vals, ids = lm.step_topk(st, ids, k=8)    # the 8 best next words of each stream, best first (blm_topk_rows)
+    st = lm.reorder_device(st, idx)           # the same gather with a DEVICE index and no copy to the host (equal lengths promised)
+    nbest = lm.beam_search([[bos, w1, w2]], beam=8, max_words=30, eos=bos)   # -> [[BeamHypothesis(tokens, score, length), ...]]
 
     lm = IncrementalLM(model, max_streams=64, max_len=1024, mc_samples=8, seed=1111)   # the model average over 8 weight samples
     lp = lm.step(st, ids)                                   # log pbar, the distribution the n-best scorer's --mc-samples scores with
@@ -45,6 +48,7 @@ import torch
 
 from . import model as M
 from . import ops
+from ._lib import TOPK_MAX as L_TOPK_MAX
 from ._lib import BayesLMError
 
 _TRANSFORMERS = (M.TransformerModel, M.BayesTransformerModel, M.GaussTransformerModel, M.VTransformerModel)
@@ -94,6 +98,13 @@ class McUncertainty(NamedTuple):
     h_pred: torch.Tensor           # predictive entropy of the model average, H[pbar]
     mi: torch.Tensor               # mutual information between the next word and the weights, mean_s KL(p_s || pbar)
     nll_s: Optional[torch.Tensor]  # (..., S) NLL of the target under each sample; None without targets
+
+
+class BeamHypothesis(NamedTuple):
+    """One result of IncrementalLM.beam_search."""
+    tokens: list   # generated word ids (prompt excluded), cut after the first eos
+    score: float   # raw fp32 cumulative log-probability of `tokens`, the eos included
+    length: int    # len(tokens)
 
 
 class _SampleCache:
@@ -242,6 +253,119 @@ class IncrementalLM:
         st._buf = None
         self._spare = src
         return out
+
+    def reorder_device(self, st, idx):
+        """reorder with a device index and no copy to the host: new stream j continues stream idx[j], idx an (st.n,) int64
+        DEVICE tensor.  The caller promises what the host cannot check without a synchronise: every idx[j] lies in [0, st.n)
+        (the gather copies nothing for an entry outside) and stream idx[j] holds as many tokens as stream j did, so
+        ``lengths`` stays as it is, position by position (beam search: parents stay inside their group, whose beams have one
+        length).  The device lengths follow the index exactly.  The same single gather launch; ``st`` is consumed."""
+        src = st._live(self)
+        if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1):
+            raise BayesLMError("IncrementalLM.reorder_device: idx must be a 1-D int64 tensor on the device (reorder takes a host index)")
+        if idx.shape[0] != st.n:
+            raise BayesLMError("IncrementalLM.reorder_device: %d entries for %d streams (the stream count is kept)" % (idx.shape[0], st.n))
+        dst = self._new_buf()
+        S = max(self.mc_samples, 1)
+        with torch.no_grad():
+            # every sample's slice in the one launch: new slot s * n + j continues old slot s * n + idx[j]
+            iall = idx if S == 1 else (torch.arange(S, device=idx.device).view(S, 1) * st.n + idx.view(1, -1)).reshape(-1)
+            if self.kind == "transformer":
+                ops.kv_gather(src.kv, dst.kv, iall, S * st.n, 2 * src.layers, self.nhead, self.max_len, self.head_dim,
+                              src.past, dst.past)
+            else:
+                ops.kv_gather(src, dst, iall, S * st.n, 2 * self.layers, 1, 1, self.hidden)
+        out = IncrementalState(self, st.n, dst)
+        out.lengths = list(st.lengths)
+        st._buf = None
+        self._spare = src
+        return out
+
+    # ---------------------------------------------------------------- search
+    def step_topk(self, st, ids, k, n_new=None):
+        """step, then the k best next words of every stream, best first (blm_topk_rows: value descending, lowest id on ties)
+        -> (log-probs (n, k) float32, ids (n, k) int64).  With mc_samples: the top k of log pbar."""
+        k = int(k)
+        if not 1 <= k <= min(self.vocab, L_TOPK_MAX):
+            raise BayesLMError("IncrementalLM.step_topk: k = %d outside [1, min(V = %d, %d)]" % (k, self.vocab, L_TOPK_MAX))
+        return ops.topk_rows(self.step(st, ids, n_new=n_new), k)
+
+    def beam_search(self, prompts, beam, max_words, eos, length_penalty=0.0, sync_every=16):
+        """Beam search over G prompts at once -> list (per prompt) of ``beam`` BeamHypothesis, best first.
+
+        ``prompts``: G non-empty lists of word ids (ragged allowed), G * beam <= max_streams and
+        max(len(prompt)) + max_words <= max_len, both checked before any launch.  Per word: step -> blm_topk_rows(k = beam) ->
+        blm_beam_select -> reorder_device; parents and tokens of every step stay on the device and are read once at the end.
+        Selection inside the loop is by RAW cumulative log-probability only (exact top ``beam`` of all beam x V continuations,
+        lowest candidate index on ties); ``length_penalty`` a enters only the final ranking, on the host in float64, by
+        score / length ** a (ties by beam index).  A beam that produced ``eos`` is finished: it keeps its slot and score, is
+        fed eos like any other stream (its rows are ignored), so every launch keeps its shape.  The host reads one "all
+        finished" flag every ``sync_every`` words (0: never) and stops early when it is set; results do not depend on it.
+        With mc_samples the search runs under log pbar, the model average."""
+        P, T, score = self._beam_trace(prompts, beam, max_words, eos, sync_every)
+        G, B = len(prompts), int(beam)
+        out = []
+        for g in range(G):
+            hyps = []
+            for b in range(B):
+                cur, toks = g * B + b, []
+                for w in range(P.shape[0] - 1, -1, -1):
+                    toks.append(int(T[w, cur]))
+                    cur = int(P[w, cur])
+                toks.reverse()
+                if eos in toks:
+                    toks = toks[:toks.index(eos) + 1]
+                hyps.append(BeamHypothesis(toks, float(score[g * B + b]), len(toks)))
+            rank = sorted(range(B), key=lambda b: (-(float(np.float64(hyps[b].score) / np.float64(hyps[b].length) ** float(length_penalty))), b))
+            out.append([hyps[b] for b in rank])
+        return out
+
+    def _beam_trace(self, prompts, beam, max_words, eos, sync_every=16):
+        """The search loop of beam_search -> host arrays (parents (W, G * beam) int64, tokens (W, G * beam) int64, final scores
+        (G * beam,) float32), W <= max_words the words generated before every beam was seen finished."""
+        G, B, W, eos = len(prompts), int(beam), int(max_words), int(eos)
+        if G < 1 or any(len(p) < 1 for p in prompts):
+            raise BayesLMError("IncrementalLM.beam_search: at least one prompt, and at least one word (the sentence start) in each")
+        if not 1 <= B <= min(self.vocab, L_TOPK_MAX):
+            raise BayesLMError("IncrementalLM.beam_search: beam = %d outside [1, min(V = %d, BLM_TOPK_MAX = %d)]"
+                               % (B, self.vocab, L_TOPK_MAX))
+        if W < 1 or int(sync_every) < 0:
+            raise BayesLMError("IncrementalLM.beam_search: max_words >= 1 and sync_every >= 0 expected")
+        if G * B > self.max_streams:
+            raise BayesLMError("IncrementalLM.beam_search: %d prompts x %d beams, max_streams is %d" % (G, B, self.max_streams))
+        lens = [len(p) for p in prompts]
+        if max(lens) + W > self.max_len:
+            raise BayesLMError("IncrementalLM.beam_search: prompt of %d words + %d new words, max_len is %d" % (max(lens), W, self.max_len))
+        if not 0 <= eos < self.vocab:
+            raise BayesLMError("IncrementalLM.beam_search: eos %d outside the vocabulary" % eos)
+        n = G * B
+        ids = np.zeros((max(lens), G), dtype=np.int64)
+        for g, p in enumerate(prompts):
+            ids[:lens[g], g] = p
+        with torch.no_grad():
+            # every prompt through the model once, then forked into its group of beams
+            st = self.start(G)
+            lp = self.step(st, _upload(ids, self.device, torch.int64), n_new=lens)
+            fork = np.repeat(np.arange(G, dtype=np.int64), B)
+            st = self.reorder(st, fork)
+            lp = lp.index_select(0, _upload(fork, self.device, torch.int64))
+            s0 = np.full(n, -np.inf, dtype=np.float32)
+            s0[::B] = 0.0  # one live beam per group, or the first step picks `beam` copies of one word
+            score = _upload(s0, self.device, torch.float32)
+            finished = torch.zeros(n, dtype=torch.uint8, device=self.device)
+            parents, tokens = [], []
+            for w in range(W):
+                vals, cand = ops.topk_rows(lp, B)
+                score, finished, parent, token = ops.beam_select(vals, cand, score, finished, B, eos)
+                parents.append(parent)
+                tokens.append(token)
+                if w + 1 == W:
+                    break
+                if sync_every and (w + 1) % int(sync_every) == 0 and bool(finished.all()):  # the loop's only host read
+                    break
+                st = self.reorder_device(st, parent)
+                lp = self.step(st, token)
+            return torch.stack(parents).cpu().numpy(), torch.stack(tokens).cpu().numpy(), score.cpu().numpy()
 
     # ---------------------------------------------------------------- stepping
     def step(self, st, ids, n_new=None, all_positions=False, targets=None, return_uncertainty=False):

@@ -1972,18 +1972,65 @@ def log_softmax_rows(x, V=None, out=None):
     return out
 
 
-def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0):
+def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=1.0):
     """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
-    with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64"""
+    with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64
+    ``top_k`` > 0 and / or ``top_p`` < 1 restrict the draw to the top_k best entries and to the shortest prefix of the order
+    (value descending, index ascending) whose softmax(x / temperature) mass reaches top_p (blm_sample_rows_filtered: the same
+    noise, so the draw is unchanged whenever it falls inside the allowed set)."""
     x = _f32(x, "x")
     if x.dim() != 2 or x.stride(-1) != 1:
         raise BayesLMError("sample_rows: a row-major (R, V) matrix expected")
+    top_k, top_p = int(top_k), float(top_p)
+    if top_k < 0 or not 0.0 < top_p <= 1.0:
+        raise BayesLMError("sample_rows: top_k >= 0 (0: no limit) and top_p in (0, 1] expected, got %d and %g" % (top_k, top_p))
     out = torch.empty(x.shape[0], device=x.device, dtype=torch.int64)
     r = L.rng(seed, stream_id, step)
     L.require_gfx950()
-    check(lib().blm_sample_rows(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), C.byref(r), ptr(out), stream()),
-          "blm_sample_rows")
+    if top_k == 0 and top_p == 1.0:
+        check(lib().blm_sample_rows(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), C.byref(r), ptr(out), stream()),
+              "blm_sample_rows")
+    else:
+        check(lib().blm_sample_rows_filtered(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), top_k, top_p,
+                                             C.byref(r), ptr(out), stream()), "blm_sample_rows_filtered")
     return out
+
+
+def topk_rows(x, k):
+    """The k best entries of every row of the (R, V) matrix x, best first (blm_topk_rows): value descending, then index
+    ascending, NaN below -inf; values are copied bit for bit.  1 <= k <= min(V, _lib.TOPK_MAX).
+    -> (vals (R, k) float32, ids (R, k) int64)"""
+    x = _f32(x, "x")
+    if x.dim() != 2 or x.stride(-1) != 1:
+        raise BayesLMError("topk_rows: a row-major (R, V) matrix expected")
+    R, V = x.shape
+    k = int(k)
+    vals = torch.empty(R, k, device=x.device, dtype=torch.float32)
+    ids = torch.empty(R, k, device=x.device, dtype=torch.int64)
+    L.require_gfx950()
+    check(lib().blm_topk_rows(ptr(x), x.stride(0), R, V, k, ptr(vals), ptr(ids), stream()), "blm_topk_rows")
+    return vals, ids
+
+
+def beam_select(cand_vals, cand_ids, score, finished, beams, eos):
+    """One beam-search step over groups of ``beams`` streams (blm_beam_select): cand_vals / cand_ids (G * beams, k) from
+    topk_rows, score (G * beams,) float32 and finished (G * beams,) uint8 before the step.
+    -> (score, finished, parent (global stream index), token) after it, each (G * beams,)"""
+    cand_vals = dev_tensor(cand_vals, "cand_vals")
+    cand_ids = dev_tensor(cand_ids, "cand_ids", torch.int64)
+    score = dev_tensor(score, "score")
+    finished = dev_tensor(finished, "finished", torch.uint8)
+    n, B = score.numel(), int(beams)
+    if cand_vals.dim() != 2 or cand_vals.shape != cand_ids.shape or cand_vals.shape[0] != n or finished.numel() != n or \
+            B < 1 or n % B:
+        raise BayesLMError("beam_select: (G * beams, k) candidates and (G * beams,) score / finished expected")
+    score_out, fin_out = torch.empty_like(score), torch.empty_like(finished)
+    parent = torch.empty(n, device=score.device, dtype=torch.int64)
+    token = torch.empty(n, device=score.device, dtype=torch.int64)
+    L.require_gfx950()
+    check(lib().blm_beam_select(ptr(cand_vals), ptr(cand_ids), ptr(score), ptr(finished), n // B, B, cand_vals.shape[1], int(eos),
+                                ptr(score_out), ptr(fin_out), ptr(parent), ptr(token), stream()), "blm_beam_select")
+    return score_out, fin_out, parent, token
 
 
 def kv_gather(src, dst, idx, n_src, outer, nhead, max_len, head_dim, len_src=None, len_dst=None):

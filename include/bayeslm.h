@@ -512,6 +512,36 @@ int blm_log_softmax_rows(const float* x, int64_t ldx, float* out, int64_t ldo, i
  * u = ((w >> 8) + 0.5) * 2^-24, noise -log(-log u).  The same rng gives the same ids. */
 int blm_sample_rows(const float* x, int64_t ldx, int R, int V, float temperature, const blm_rng* rng, int64_t* out, void* stream);
 
+/* --------------------------------------------------------------------------
+ * Search on the incremental path (csrc/beam.hip): the k best next words, beam selection, top-k / nucleus sampling.
+ *
+ * One total order of a row's entries is used throughout: value descending, then index ascending; -0 equals +0 and every NaN
+ * ranks below -inf (a stream that took no token has an all-NaN row).  Values are copied, never recomputed, and the selection
+ * uses integer atomics only: results are exact and the same in every run, deterministic mode or not.
+ * ------------------------------------------------------------------------ */
+#define BLM_TOPK_MAX 256
+/* vals / ids (R, k) contiguous: the k first entries of x[r, :V] (row stride ldx >= V) in the order above, best first.
+ * 1 <= k <= min(V, BLM_TOPK_MAX).  No workspace. */
+int blm_topk_rows(const float* x, int64_t ldx, int R, int V, int k, float* vals, int64_t* ids, void* stream);
+/* One beam-search step for G groups of B beams (stream g * B + b), one workgroup per group.  cand_vals / cand_ids (G * B, k):
+ * the candidates of every beam (blm_topk_rows of its next-word log-probabilities); score / finished (G * B,): the state before
+ * the step.  A live beam b offers (score[b] + cand_vals[b, j], token cand_ids[b, j]) -- one fp32 add each; a finished beam
+ * offers itself alone (score unchanged, token eos).  The new beams of a group are its B best candidates by score descending
+ * (NaN last), then flat candidate index b_local * k + j ascending.  parent is the GLOBAL stream index of the beam continued
+ * (always inside the group); finished_out = parent finished or token == eos.  1 <= B <= BLM_TOPK_MAX, k >= 1; with k >= B the
+ * result is the exact top B of all B x V continuations.  score_out / finished_out must not alias score / finished.
+ * Start a search from scores [0, -inf, ..., -inf] per group, or the first step picks B copies of one word. */
+int blm_beam_select(const float* cand_vals, const int64_t* cand_ids, const float* score, const uint8_t* finished, int G, int B, int k,
+                    int64_t eos, float* score_out, uint8_t* finished_out, int64_t* parent, int64_t* token, void* stream);
+/* blm_sample_rows restricted to an allowed set: with q = softmax(x / temperature), the first top_k entries of the order above
+ * (0: all; not capped by BLM_TOPK_MAX) intersected with the shortest prefix of that order whose q-mass reaches top_p (in (0, 1];
+ * 1: all; never empty).  The draw is the arg-max over the allowed set of x / temperature + the SAME Philox Gumbel noise as
+ * blm_sample_rows (same counter and key): top_k = 0, top_p = 1 returns what blm_sample_rows returns.  temperature 0: argmax.
+ * The cuts are found by radix selection over the row (entry counts, and for top_p per-bin mass in integer fixed point, so
+ * no floating-point sum depends on an order), not by sorting it. */
+int blm_sample_rows_filtered(const float* x, int64_t ldx, int R, int V, float temperature, int top_k, float top_p, const blm_rng* rng,
+                             int64_t* out, void* stream);
+
 /* Cross entropy over materialised logits (M, V) (train.py:233,332;
  * compute_sentence_scores_bayes_jianwei.py:168):
  *   nll[m] = logsumexp(logits[m,:]) - logits[m,tgt[m]]
