@@ -7,6 +7,8 @@ interpolation with a second model (:157-168), LSTM hidden state carried to the n
 the FIRST hypothesis of the previous one (:271-274).
 """
 import argparse
+import contextlib
+import functools
 import math
 import os
 from collections import OrderedDict
@@ -15,7 +17,9 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from . import ops
 from ._lib import BayesLMError
+from .model import inference_decoder, mc_sampling
 from .prefix_trie import build_trie
 
 
@@ -100,7 +104,6 @@ def load_partial(model, path):
 
 
 def sentence_score(model, ids, tgt, model_type, hidden, device, model_2=None, hidden_2=None, alpha=0.0):
-    from . import ops
     data = torch.tensor(ids, dtype=torch.int64, device=device).view(-1, 1)
     target = torch.tensor(tgt, dtype=torch.int64, device=device)
     with torch.no_grad():
@@ -148,7 +151,6 @@ _INTERP = {}  # (id(model), id(model_2), alpha) -> ops.InterpDecoder of the scor
 
 
 def _interp_decoder(model, model_2, alpha):
-    from . import ops
     key = (id(model), id(model_2), float(alpha))
     dec = _INTERP.get(key)
     d1, d2 = model.decoder, model_2.decoder
@@ -158,65 +160,59 @@ def _interp_decoder(model, model_2, alpha):
     return dec
 
 
+def _enter_decoders(stack, models, **modes):
+    """Put the decoder of every model into the given inference modes (model._ProjHolder.inference) until ``stack`` closes;
+    one scope for a decoder that two entries share (a model interpolated with itself)."""
+    seen = []
+    for m in models:
+        dec = inference_decoder(m)
+        if dec is not None and not any(dec is d for d in seen):
+            seen.append(dec)
+            stack.enter_context(dec.inference(**modes))
+
+
 def _batch_nll(model, data, target_flat, model_type, hidden, model_2, hidden_2, alpha, rows=None, decoder_input=False):
     """Per-token NLL of a padded batch of hypotheses (all columns start from the same state): (T, N), or -- with
     ``rows`` (flat indices t*N + n of the real tokens) -- one value per selected row, the decoder being applied to those
     rows only (model._ProjHolder.rows).  ``decoder_input`` (one model, with ``rows``): the decoder's input rows (R, K)
     instead, for a decoder launch over several passes at once (ops.linear_mc_stats)."""
-    from . import ops
-    import contextlib
     # Transformers whose operations outside the attention core are all token-wise keep ONLY the real tokens' rows through
     # the whole stack (ops.packed_tokens): the rows arrive at the decoder already selected, in the order of ``rows``
     packed = (rows is not None and model_type == 'Transformer' and _PACKED and getattr(model, "supports_packed", False)
               and (model_2 is None or getattr(model_2, "supports_packed", False)))
-    for m in (model, model_2):
-        if m is not None:
-            m.decoder.rows = None if packed else rows
+    models = [m for m in (model, model_2) if m is not None]
+    can_fuse = _FUSED_NLL and not torch.is_grad_enabled() and all(inference_decoder(m) is not None for m in models)
     # one model: the decoder returns the NLL itself, its (rows, V) logits are never stored (ops.linear_nll); two models
     # interpolate LOGITS (reference :163) and keep the materialised pair + the two-input CE kernel
-    fused = (model_2 is None and _FUSED_NLL and not torch.is_grad_enabled() and hasattr(model.decoder, "nll_targets")
-             and ops.linear_nll_supported(model.decoder.weight, model.decoder.bias) and not decoder_input)
+    fused = (model_2 is None and can_fuse and ops.linear_nll_supported(model.decoder.weight, model.decoder.bias)
+             and not decoder_input)
     # two models: the reference interpolates LOGITS (:163); alpha (x1 W1^T + b1) + (1 - alpha) (x2 W2^T + b2) is one product
     # over packed operands, so one decoder + cross-entropy launch takes both and no logits are stored (ops.linear_nll_interp)
-    fused2 = (model_2 is not None and _FUSED_NLL and not torch.is_grad_enabled()
-              and all(hasattr(m.decoder, "return_input") for m in (model, model_2))
+    fused2 = (model_2 is not None and can_fuse
               and ops.linear_nll_interp_supported(model.decoder.weight, model.decoder.bias, model_2.decoder.weight,
                                                   model_2.decoder.bias))
-    if fused:
-        model.decoder.nll_targets = target_flat
-    if decoder_input:
-        model.decoder.return_input = True
-    if fused2:
-        model.decoder.return_input = model_2.decoder.return_input = True
-    try:
-        with (ops.packed_tokens(rows, data.shape[0], data.shape[1]) if packed else contextlib.nullcontext()):
-            if model_type == 'Transformer':
-                out = model(data)
-            else:
-                out, _ = model(data, hidden)
-            out2 = None
-            if model_2 is not None:
-                out2 = model_2(data) if model_type == 'Transformer' else model_2(data, hidden_2)[0]
-        if decoder_input:
-            return out.reshape(-1, out.shape[-1])
-        if fused:
-            nll = out
-        elif fused2:
-            nll = ops.linear_nll_interp(out, out2, _interp_decoder(model, model_2, alpha), target_flat)
-        elif model_2 is not None:
-            _, nll = ops.cross_entropy_interp(out.view(-1, out.shape[-1]), out2.view(-1, out2.shape[-1]), alpha, target_flat)
+    with contextlib.ExitStack() as modes:
+        _enter_decoders(modes, models, rows=None if packed else rows, targets=target_flat if fused else None,
+                        input_rows=decoder_input or fused2)
+        if packed:
+            modes.enter_context(ops.packed_tokens(rows, data.shape[0], data.shape[1]))
+        if model_type == 'Transformer':
+            out = model(data)
         else:
-            _, nll = ops.cross_entropy(out.view(-1, out.shape[-1]), target_flat)
-    finally:
-        for m in (model, model_2):
-            if m is not None:
-                m.decoder.rows = None
-        if fused:
-            model.decoder.nll_targets = None
-        if decoder_input:
-            model.decoder.return_input = False
-        if fused2:
-            model.decoder.return_input = model_2.decoder.return_input = False
+            out, _ = model(data, hidden)
+        out2 = None
+        if model_2 is not None:
+            out2 = model_2(data) if model_type == 'Transformer' else model_2(data, hidden_2)[0]
+    if decoder_input:
+        return out.reshape(-1, out.shape[-1])
+    if fused:
+        nll = out
+    elif fused2:
+        nll = ops.linear_nll_interp(out, out2, _interp_decoder(model, model_2, alpha), target_flat)
+    elif model_2 is not None:
+        _, nll = ops.cross_entropy_interp(out.view(-1, out.shape[-1]), out2.view(-1, out2.shape[-1]), alpha, target_flat)
+    else:
+        _, nll = ops.cross_entropy(out.view(-1, out.shape[-1]), target_flat)
     return nll if rows is not None else nll.view(data.shape[0], data.shape[1])
 
 
@@ -226,29 +222,21 @@ def _tree_nll(model, data, model_type, hidden, model_2, hidden_2, alpha, tree, d
     layer on the M node rows, attention over each node's path); LSTMs run the recurrence over the padded batch as _batch_nll does
     and only the decoder moves to the node rows.  The decoders hand back their input rows; ONE edge launch gives the NLLs
     (ops.linear_nll_edges, or ops.linear_nll_interp_edges for two models).  ``dec``: the run's McDecoder (one model)."""
-    from . import ops
-    import contextlib
     sel, end, lo, en, et = tree
     models = [m for m in (model, model_2) if m is not None]
     for m in models:
-        if not hasattr(m.decoder, "return_input"):
+        if inference_decoder(m) is None:
             raise BayesLMError("share_prefixes: %s's decoder cannot hand back its input rows" % type(m).__name__)
     is_tf = model_type == 'Transformer'
-    try:
-        for m in models:
-            m.decoder.return_input = True
-            m.decoder.rows = None if is_tf else sel
-        with (ops.tree_tokens(sel, data.shape[0], data.shape[1], end, lo, model) if is_tf else contextlib.nullcontext()):
-            if is_tf:
-                x = model(data)
-                x2 = model_2(data) if model_2 is not None else None
-            else:
-                x = model(data, hidden)[0]
-                x2 = model_2(data, hidden_2)[0] if model_2 is not None else None
-    finally:
-        for m in models:
-            m.decoder.return_input = False
-            m.decoder.rows = None
+    with contextlib.ExitStack() as modes:
+        _enter_decoders(modes, models, rows=None if is_tf else sel, input_rows=True)
+        if is_tf:
+            modes.enter_context(ops.tree_tokens(sel, data.shape[0], data.shape[1], end, lo, model))
+            x = model(data)
+            x2 = model_2(data) if model_2 is not None else None
+        else:
+            x = model(data, hidden)[0]
+            x2 = model_2(data, hidden_2)[0] if model_2 is not None else None
     x = x.reshape(-1, x.shape[-1])
     if model_2 is None:
         return ops.linear_nll_edges(x, dec, en, et)
@@ -259,7 +247,6 @@ def _carry(model, x0, hidden):
     """State after running x0 (T,1) from ``hidden`` in eval mode: the recurrent stack only -- every LSTM family here is
     embedding -> self.rnn -> dropout -> decoder (model.py:217-229 and its siblings), and the decoder's (T,V) logits
     are not needed for the state."""
-    from . import ops
     if hasattr(model, "rnn") and hasattr(model, "encoder") and not model.training:
         emb = ops.embed(x0, model.encoder.weight, None, 1.0, ops.NO_DROP)
         return model.rnn(emb, hidden)[1]
@@ -272,7 +259,6 @@ def _carry_chain(model, stream_ids, offs, hidden, max_tokens=8192):
     tokens) through the recurrent stack, and the states at the utterance boundaries are tapped out of the fused LSTM
     layers (ops.state_tap) -- one call per segment instead of one per utterance.  Cells that run step-wise do not
     report their states: those models walk the chain utterance by utterance."""
-    from . import ops
     n = len(offs) - 1
     carries = []
     u = 0
@@ -378,22 +364,8 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
     hidden = model.init_hidden(1) if is_rnn else None
     hidden_2 = model_2.init_hidden(1) if (model_2 is not None and is_rnn) else None
     S = max(1, int(mc_samples))
-    raised = []
-    if mc_samples > 0:
-        from .model import variational_sites
-        sites = variational_sites(model)
-        if not sites:
-            # e.g. --uncertainty none, Gaussian type 0, Variational '00', VTransformer (whose noise branch cannot run,
-            # model.py:2800): S passes would be S identical mean-weight passes at S times the cost
-            raise BayesLMError("--mc-samples %d: %s has no variational tensor to sample (mean-weight scoring is "
-                               "--mc-samples 0)" % (mc_samples, type(model).__name__))
-        for m in sites:  # optional sampling flags (GPNN.sample, model.py:1799: False unless somebody raises it)
-            if getattr(m, "sample", True) is False:
-                m.sample = True
-                raised.append(m)
-        model.train()
-        model.noise_state.dropout_off = True
-        model.set_seed(seed)
+    # the decoder padded once for this scoring run (its weights do not change during it), on first use, and dropped with it
+    mc_decoder = functools.lru_cache(maxsize=None)(lambda: ops.McDecoder(model.decoder.weight, model.decoder.bias))
 
     def score_group(group, hidden, hidden_2):
         """group = [(key, hyps, pairs)]; one padded batch over all their hypotheses."""
@@ -440,9 +412,6 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
             data = dev_buf[:Tm * N].view(Tm, N)
             d_sel = d_tsel = None
             d_ends = dev_buf[o + 2 * E + R:]
-            if model_2 is None and not tree_dec:  # the decoder padded once for this scoring run (its weights do not change during it)
-                from . import ops
-                tree_dec.append(ops.McDecoder(model.decoder.weight, model.decoder.bias))
         else:
             dev_buf = torch.from_numpy(host).to(device, non_blocking=True)
             data = dev_buf[:Tm * N].view(Tm, N)
@@ -463,7 +432,7 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
                 xs.append(_batch_nll(model, data, d_tsel, model_type, hN, None, None, alpha, rows=d_sel, decoder_input=True))
                 continue
             if share_prefixes:  # per edge -> per real token, n-major as the padded path orders them
-                nll = _tree_nll(model, data, model_type, hN, model_2, h2N, alpha, tree, tree_dec[0] if tree_dec else None)[d_tok_edge]
+                nll = _tree_nll(model, data, model_type, hN, model_2, h2N, alpha, tree, mc_decoder() if model_2 is None else None)[d_tok_edge]
             else:
                 nll = _batch_nll(model, data, d_tsel, model_type, hN, model_2, h2N, alpha, rows=d_sel)  # (R,)
             run = torch.cumsum(nll.double(), 0)
@@ -471,10 +440,7 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
             sent.append((hi - torch.cat([hi.new_zeros(1), hi[:-1]])).float())
         stats = None
         if uncertainty:  # one decoder launch over the S passes' rows: per-sample NLLs and the token-level uncertainty
-            from . import ops
-            if not mc_dec:  # the decoder padded once for this scoring run (its weights do not change during it)
-                mc_dec.append(ops.McDecoder(model.decoder.weight, model.decoder.bias))
-            st = ops.linear_mc_stats(torch.stack(xs), model.decoder.weight, model.decoder.bias, d_tsel, dec=mc_dec[0])
+            st = ops.linear_mc_stats(torch.stack(xs), model.decoder.weight, model.decoder.bias, d_tsel, dec=mc_decoder())
             del xs
             for smp in range(S):
                 run = torch.cumsum(st.nll_s[:, smp].double(), 0)
@@ -492,8 +458,6 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
             flush()
 
     pending = []
-    mc_dec = []  # uncertainty: ops.McDecoder of this run, dropped with it
-    tree_dec = []  # share_prefixes, one model: the same
 
     def flush():
         if not pending:
@@ -519,14 +483,10 @@ def _compute_scores_batched(nbest, model, vocab, model_type, device, model_2, al
         pending.clear()
 
     try:
-        _score_all(nbest, model, model_2, vocab, device, is_rnn, hidden, hidden_2, batch_tokens, score_group, flush)
+        with (mc_sampling(model, seed, mc_samples) if mc_samples > 0 else contextlib.nullcontext()):
+            _score_all(nbest, model, model_2, vocab, device, is_rnn, hidden, hidden_2, batch_tokens, score_group, flush)
     finally:
         _INTERP.clear()  # the packed [W1 | W2] belongs to this scoring run
-        if mc_samples > 0:
-            model.noise_state.dropout_off = False
-            model.eval()
-            for m in raised:
-                m.sample = False
     return (scores, unc) if uncertainty else scores
 
 
@@ -691,7 +651,6 @@ def main(argv=None):
     device = torch.device("cuda", job_device_index(args.job, torch.cuda.device_count(), os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)  # one process per GPU: kernels go to the current device's stream
     if args.gemm_mode != 'f32':
-        from . import ops
         ops.set_gemm_mode(args.gemm_mode)
     vocab = read_vocab(args.vocabulary)
     model_1, model_2 = build_models(args, len(vocab))

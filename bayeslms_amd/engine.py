@@ -647,7 +647,7 @@ def evaluate(model, source, seq_len, eval_batch_size=None, rank=0, world=1, grou
     that does not scale (it is ~1 % of a one-GPU epoch of the AMI recipe, ~10 % of an 8-GPU one).  Every rank returns the
     same value up to the all-reduce (callers that branch on it take rank 0's: train.ValidationSchedule)."""
     from .data import get_batch
-    from .model import repackage_hidden
+    from .model import inference_decoder, repackage_hidden
     model.eval()
     cols = source.shape[1]
     lo, hi = (rank * cols) // world, ((rank + 1) * cols) // world
@@ -656,8 +656,8 @@ def evaluate(model, source, seq_len, eval_batch_size=None, rank=0, world=1, grou
     hidden = model.init_hidden(mine.shape[1]) if (hasattr(model, "init_hidden") and hi > lo) else None
     # the decoder returns the per-token NLL itself when it can (ops.linear_nll: the (T*B, V) logits are never stored);
     # BLM_EVAL_FUSED_NLL=0 keeps decoder + cross-entropy kernel
-    dec = getattr(model, "decoder", None)
-    fused = (os.environ.get("BLM_EVAL_FUSED_NLL", "1") != "0" and dec is not None and hasattr(dec, "nll_targets")
+    dec = inference_decoder(model)
+    fused = (os.environ.get("BLM_EVAL_FUSED_NLL", "1") != "0" and dec is not None
              and ops.linear_nll_supported(dec.weight, dec.bias))
     # A model without carried state (the Transformers) sees every window on its own: G full windows are evaluated as ONE batch of
     # G x columns independent columns (same positions, same causal mask per column) -- the reference's eval batch of 10-20 columns
@@ -674,36 +674,32 @@ def evaluate(model, source, seq_len, eval_batch_size=None, rank=0, world=1, grou
     # language models' evaluation batch gives them 700 rows per window) and the layer wavefront over a longer stretch
     # (configs[1]'s model, 12 windows of 20 x 35: 668 k tokens/s window by window, 765 k in threes; no better and host-bound beyond).
     stride = seq_len * (n_win if hidden is not None else 1)
-    with torch.no_grad():
-        try:
-            i, left = 0, n_full
-            while hidden is None and n_win > 1 and left > 1 and hi > lo:
-                g = min(n_win, left)
-                starts = range(i, i + g * seq_len, seq_len)
-                data = torch.cat([mine[k:k + seq_len] for k in starts], 1)
-                targets = torch.cat([mine[k + 1:k + 1 + seq_len] for k in starts], 1).reshape(-1)
-                if fused:
-                    dec.nll_targets = targets
-                out = model(data)
-                loss = out.mean() if fused else ops.cross_entropy(out.view(-1, out.shape[-1]), targets)[0]
-                total += (g * seq_len) * loss.double()  # equally sized windows: sum_k len * mean_k = G len * mean of all
-                i, left = i + g * seq_len, left - g
-            for i in range(i, source.size(0) - 1, stride):
-                if hi <= lo:
-                    break  # more ranks than columns: nothing of this stream is mine
-                data, targets = get_batch(mine, i, stride)
-                if fused:
-                    dec.nll_targets = targets
-                if hidden is None:
-                    out = model(data)
-                else:
-                    out, hidden = model(data, hidden)
-                    hidden = repackage_hidden(hidden)
-                loss = out.mean() if fused else ops.cross_entropy(out.view(-1, out.shape[-1]), targets)[0]
-                total += len(data) * loss.double()
-        finally:
+    with torch.no_grad(), (dec.inference() if fused else contextlib.nullcontext()):
+        i, left = 0, n_full
+        while hidden is None and n_win > 1 and left > 1 and hi > lo:
+            g = min(n_win, left)
+            starts = range(i, i + g * seq_len, seq_len)
+            data = torch.cat([mine[k:k + seq_len] for k in starts], 1)
+            targets = torch.cat([mine[k + 1:k + 1 + seq_len] for k in starts], 1).reshape(-1)
             if fused:
-                dec.nll_targets = None
+                dec.set_nll_targets(targets)
+            out = model(data)
+            loss = out.mean() if fused else ops.cross_entropy(out.view(-1, out.shape[-1]), targets)[0]
+            total += (g * seq_len) * loss.double()  # equally sized windows: sum_k len * mean_k = G len * mean of all
+            i, left = i + g * seq_len, left - g
+        for i in range(i, source.size(0) - 1, stride):
+            if hi <= lo:
+                break  # more ranks than columns: nothing of this stream is mine
+            data, targets = get_batch(mine, i, stride)
+            if fused:
+                dec.set_nll_targets(targets)
+            if hidden is None:
+                out = model(data)
+            else:
+                out, hidden = model(data, hidden)
+                hidden = repackage_hidden(hidden)
+            loss = out.mean() if fused else ops.cross_entropy(out.view(-1, out.shape[-1]), targets)[0]
+            total += len(data) * loss.double()
     if world > 1:  # sum_r (columns of r) * (its per-window means, summed) / all columns = the whole batch's per-window means, summed
         total = total * float(hi - lo) / float(cols)
         on_dev = dist.get_backend(group) == "nccl"

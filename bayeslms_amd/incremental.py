@@ -39,7 +39,6 @@ mode whenever the caller holds it.  Not covered: two-model interpolation, the ar
 perplexity in engine.evaluate, and under mc_samples the LSTM cells that draw fresh noise at every time step of a CALL (the
 Variational LSTM's noise rows, the GP-LSTM's random frequencies: such a sample is not one model over a stream).
 """
-import contextlib
 import math
 from typing import NamedTuple, Optional
 
@@ -193,9 +192,7 @@ class IncrementalLM:
         self._spare = None
         self._mc_dec = None
         if self.mc_samples > 0:
-            if not M.variational_sites(model):  # the scorer's refusal (compute_sentence_scores.py): S identical passes at S times the cost
-                raise BayesLMError("--mc-samples %d: %s has no variational tensor to sample (mean-weight scoring is "
-                                   "--mc-samples 0)" % (self.mc_samples, name))
+            M.require_variational_sites(model, self.mc_samples)  # the scorer's refusal, before any launch
             cell = _redraws_per_time_step(model) if self.kind == "lstm" else None
             if cell:
                 raise BayesLMError("IncrementalLM: mc_samples on %s: %s draws fresh noise at every time step of a call, so a "
@@ -228,7 +225,7 @@ class IncrementalLM:
     def reorder(self, st, idx):
         """Beam prune / fork: new stream j continues stream idx[j] of ``st`` (idx (m,) int64: host, or one copy to the host;
         entries may repeat, m <= max_streams).  One gather launch of every layer's state; ``st`` is consumed."""
-        src = st._live(self)
+        st._live(self)
         if isinstance(idx, torch.Tensor) and idx.is_cuda:
             idx = idx.cpu()
         ih = np.asarray(idx.numpy() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64).reshape(-1)
@@ -237,22 +234,10 @@ class IncrementalLM:
             raise BayesLMError("IncrementalLM.reorder: %d streams, max_streams is %d" % (m, self.max_streams))
         if ih.min() < 0 or ih.max() >= st.n:
             raise BayesLMError("IncrementalLM.reorder: idx out of range [0, %d)" % st.n)
-        dst = self._new_buf()
         S = max(self.mc_samples, 1)
         # every sample's slice in the one launch: new slot s * m + j continues old slot s * n + idx[j]
         iall = ih if S == 1 else (np.arange(S, dtype=np.int64)[:, None] * st.n + ih[None, :]).reshape(-1)
-        idev = _upload(iall, self.device, torch.int64)
-        with torch.no_grad():
-            if self.kind == "transformer":
-                ops.kv_gather(src.kv, dst.kv, idev, S * st.n, 2 * src.layers, self.nhead, self.max_len, self.head_dim,
-                              src.past, dst.past)
-            else:
-                ops.kv_gather(src, dst, idev, S * st.n, 2 * self.layers, 1, 1, self.hidden)
-        out = IncrementalState(self, m, dst)
-        out.lengths = [st.lengths[i] for i in ih]
-        st._buf = None
-        self._spare = src
-        return out
+        return self._gather(st, _upload(iall, self.device, torch.int64), m, [st.lengths[i] for i in ih])
 
     def reorder_device(self, st, idx):
         """reorder with a device index and no copy to the host: new stream j continues stream idx[j], idx an (st.n,) int64
@@ -260,23 +245,29 @@ class IncrementalLM:
         (the gather copies nothing for an entry outside) and stream idx[j] holds as many tokens as stream j did, so
         ``lengths`` stays as it is, position by position (beam search: parents stay inside their group, whose beams have one
         length).  The device lengths follow the index exactly.  The same single gather launch; ``st`` is consumed."""
-        src = st._live(self)
+        st._live(self)
         if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1):
             raise BayesLMError("IncrementalLM.reorder_device: idx must be a 1-D int64 tensor on the device (reorder takes a host index)")
         if idx.shape[0] != st.n:
             raise BayesLMError("IncrementalLM.reorder_device: %d entries for %d streams (the stream count is kept)" % (idx.shape[0], st.n))
-        dst = self._new_buf()
         S = max(self.mc_samples, 1)
         with torch.no_grad():
             # every sample's slice in the one launch: new slot s * n + j continues old slot s * n + idx[j]
             iall = idx if S == 1 else (torch.arange(S, device=idx.device).view(S, 1) * st.n + idx.view(1, -1)).reshape(-1)
+        return self._gather(st, iall, st.n, list(st.lengths))
+
+    def _gather(self, st, iall, m, lengths):
+        """The gather of reorder / reorder_device: every layer's state of ``st`` through the per-sample slot index ``iall`` (device)
+        into the spare buffer -> the state of ``m`` streams; ``st`` is consumed and its buffer becomes the spare one."""
+        src, dst = st._live(self), self._new_buf()
+        n_src = max(self.mc_samples, 1) * st.n
+        with torch.no_grad():
             if self.kind == "transformer":
-                ops.kv_gather(src.kv, dst.kv, iall, S * st.n, 2 * src.layers, self.nhead, self.max_len, self.head_dim,
-                              src.past, dst.past)
+                ops.kv_gather(src.kv, dst.kv, iall, n_src, 2 * src.layers, self.nhead, self.max_len, self.head_dim, src.past, dst.past)
             else:
-                ops.kv_gather(src, dst, iall, S * st.n, 2 * self.layers, 1, 1, self.hidden)
-        out = IncrementalState(self, st.n, dst)
-        out.lengths = list(st.lengths)
+                ops.kv_gather(src, dst, iall, n_src, 2 * self.layers, 1, 1, self.hidden)
+        out = IncrementalState(self, m, dst)
+        out.lengths = lengths
         st._buf = None
         self._spare = src
         return out
@@ -401,7 +392,7 @@ class IncrementalLM:
                 return self._decode(self._hidden_rows(st, buf, ids, k, ragged), Tq, N, k, all_positions, targets)
             # S passes, sample s on slots [s * n, (s + 1) * n) of the state; the host lengths move once
             before, passes = st.lengths, []
-            with self._sampling():
+            with M.mc_sampling(self.model, self.seed, self.mc_samples):
                 for s in range(self.mc_samples):
                     self.model.set_step(s)
                     st.lengths = before
@@ -411,27 +402,6 @@ class IncrementalLM:
                         part = buf[:, :, s * N:]
                     passes.append(self._hidden_rows(st, part, ids, k, ragged))
             return self._decode_mc(passes, Tq, N, k, all_positions, targets, return_uncertainty)
-
-    @contextlib.contextmanager
-    def _sampling(self):
-        """The n-best scorer's sampling state (compute_sentence_scores.py): training mode with dropout off, optional sampling
-        flags raised, the weights keyed by this object's seed.  Left as it was entered: eval mode, the caller's seed and step."""
-        model, ns = self.model, self.model.noise_state
-        raised = [m for m in M.variational_sites(model) if getattr(m, "sample", True) is False]
-        saved = (ns.seed, ns.step, ns.auto_step)
-        for m in raised:
-            m.sample = True
-        model.train()
-        ns.dropout_off = True
-        model.set_seed(self.seed)
-        try:
-            yield
-        finally:
-            ns.dropout_off = False
-            model.eval()
-            for m in raised:
-                m.sample = False
-            ns.seed, ns.step, ns.auto_step = saved
 
     def _hidden_rows(self, st, buf, ids, k, ragged):
         """One forward over the chunk on the state ``buf`` -> [(first row, rows per stream, (flat indices or None, hidden rows))]"""
@@ -459,13 +429,8 @@ class IncrementalLM:
         ctx_max = max(a + int(b) for a, b in zip(st.lengths, k))
         n_new = _upload(k, self.device, torch.int32) if ragged else None
         sel = _upload(sel_h, self.device, torch.int64) if ragged else None
-        dec = self.model.decoder
-        with ops.cached_tokens(cache, Tq, N, ctx_max, n_new, sel) as ctx:
-            dec.return_input = True
-            try:
-                h = self.model(ids)
-            finally:
-                dec.return_input = False
+        with ops.cached_tokens(cache, Tq, N, ctx_max, n_new, sel) as ctx, self.model.decoder.inference(input_rows=True):
+            h = self.model(ids)
             if ctx.layer != self.layers:
                 raise BayesLMError("IncrementalLM: %d attention layers ran, %d expected" % (ctx.layer, self.layers))
         # the lengths move on only after every layer has appended at the old ones
@@ -482,9 +447,7 @@ class IncrementalLM:
         Tq, N = ids.shape
         h, c = hc[0, :, :N], hc[1, :, :N]
         p = int(k.min())
-        dec = self.model.decoder
-        dec.return_input = True
-        try:
+        with self.model.decoder.inference(input_rows=True):
             if p > 0:
                 y0, (h2, c2) = self.model(ids[:p], (h.contiguous(), c.contiguous()))
                 h.copy_(h2)
@@ -505,8 +468,6 @@ class IncrementalLM:
                     c.index_copy_(1, a, c2)
                     y[t].index_copy_(0, a, ys.reshape(-1, ys.shape[-1]))
                 out = (None, y.reshape(-1, self.hidden))
-        finally:
-            dec.return_input = False
         st.lengths = [a + int(b) for a, b in zip(st.lengths, k)]
         return out
 

@@ -14,6 +14,7 @@ tensors and all dropout masks come from a counter-based Philox stream keyed by
 data-parallel ranks regenerate them with no storage.  Tensors must live on the
 GPU; there is no CPU path.
 """
+import contextlib
 import copy
 import math
 import os
@@ -26,7 +27,7 @@ from . import ops
 from ._lib import BayesLMError
 from .ops import Drop, NoiseSpec
 
-__all__ = ["NoiseState", "variational_sites", "PositionalEncoding", "MultiheadAttention", "BayesMultiheadAttention", "BayesLinear",
+__all__ = ["NoiseState", "variational_sites", "mc_sampling", "PositionalEncoding", "MultiheadAttention", "BayesMultiheadAttention", "BayesLinear",
            "StandardTransformerEncoderLayer", "BayesTransformerEncoderLayer", "BayesTransformerModel",
            "TransformerModel", "GPNN", "GaussTransformerEncoderLayer", "GaussTransformerModel", "RNNModel", "BayesRNNModel", "Bayes2LSTM", "repackage_hidden",
            "VTransformerEncoderLayer", "VTransformerModel", "GPLSTMCell", "GPLSTM", "GaussRNNModel", "VNN", "VLSTMCell",
@@ -163,6 +164,40 @@ def variational_sites(model):
     return [m for m in model.modules() if callable(getattr(m, "draws_noise", None)) and m.draws_noise()]
 
 
+def require_variational_sites(model, mc_samples):
+    """variational_sites(model), or the refusal of Monte-Carlo sampling on a model that has none: e.g. --uncertainty none,
+    Gaussian type 0, Variational '00', VTransformer -- S passes would be S identical mean-weight passes at S times the cost."""
+    sites = variational_sites(model)
+    if not sites:
+        raise BayesLMError("--mc-samples %d: %s has no variational tensor to sample (mean-weight scoring is "
+                           "--mc-samples 0)" % (mc_samples, type(model).__name__))
+    return sites
+
+
+@contextlib.contextmanager
+def mc_sampling(model, seed, mc_samples):
+    """The Monte-Carlo sampling state of the n-best scorer and IncrementalLM: training mode with dropout off, the optional
+    sampling flags (GPNN.sample: False unless somebody raises it) raised, the weights keyed by ``seed`` -- the caller then
+    picks sample s with ``model.set_step(s)``.  Left, by return or by exception, in eval mode with the flags lowered again
+    and the caller's (seed, step, auto_step).  ``mc_samples``: the sample count, for the refusal of a model with nothing to sample."""
+    ns = model.noise_state
+    raised = [m for m in require_variational_sites(model, mc_samples) if getattr(m, "sample", True) is False]
+    saved = (ns.seed, ns.step, ns.auto_step)
+    for m in raised:
+        m.sample = True
+    model.train()
+    ns.dropout_off = True
+    model.set_seed(seed)
+    try:
+        yield
+    finally:
+        ns.dropout_off = False
+        model.eval()
+        for m in raised:
+            m.sample = False
+        ns.seed, ns.step, ns.auto_step = saved
+
+
 def repackage_hidden(h):
     """Detach hidden states from their history (train.py:291-295)."""
     if isinstance(h, torch.Tensor):
@@ -261,30 +296,56 @@ class _ProjHolder(nn.Module):
         self.weight, self.bias = lin.weight, lin.bias
         self.in_features, self.out_features = in_f, out_f
 
-    rows = None  # inference only (the n-best scorer): apply the projection to these flat rows of x, not to all of them
-    # inference only (scorer, evaluate()): with targets set, the DECODER returns the per-row NLL of its logits against them
-    # instead of the logits themselves, which are never stored (ops.linear_nll)
-    nll_targets = None
-    # inference only (two-model scoring): the DECODER hands back its input rows instead of logits -- the interpolated decoder +
-    # cross-entropy launch (ops.linear_nll_interp) takes both models' rows at once
-    return_input = False
+    # The three inference modes of the vocabulary projection.  forward reads them; ``inference`` is the only place that sets them.
+    rows = None  # apply the projection to these flat rows of x, not to all of them (the n-best scorer)
+    nll_targets = None  # return the per-row NLL of the logits against these targets; the logits are never stored (ops.linear_nll)
+    return_input = False  # hand back the input rows instead of logits, for a decoder launch that takes several passes or two models
+    _scope = False  # an ``inference`` scope is open
     is_decoder = False  # set by _LMHead._init_io for the vocabulary projection
 
+    @contextlib.contextmanager
+    def inference(self, rows=None, targets=None, input_rows=False):
+        """Scope in which this decoder runs in the given inference mode(s) -- ``rows``, ``targets`` (nll_targets) and
+        ``input_rows`` (return_input) set the attributes above; on leaving, by return or by exception, they are again what they were.  Yields the decoder: ``set_nll_targets`` replaces the targets inside the
+        scope.  Needs torch.no_grad(), and one decoder serves one scope at a time -- a mode left set would make the next
+        ``model(...)`` return NLLs or hidden rows where logits are expected."""
+        if torch.is_grad_enabled():
+            raise BayesLMError("_ProjHolder.inference is an inference-only scope: enter it under torch.no_grad()")
+        if self._scope:
+            raise BayesLMError("_ProjHolder.inference does not nest: this decoder is already in an inference scope")
+        found = (self.rows, self.nll_targets, self.return_input)
+        self._scope = True
+        self.rows, self.nll_targets, self.return_input = rows, targets, bool(input_rows)
+        try:
+            yield self
+        finally:
+            self.rows, self.nll_targets, self.return_input = found
+            self._scope = False
+
+    def set_nll_targets(self, targets):
+        """Replace ``nll_targets`` inside an open ``inference`` scope (engine.evaluate: new targets per window)."""
+        if not self._scope:
+            raise BayesLMError("_ProjHolder.set_nll_targets: no inference scope is open on this decoder")
+        self.nll_targets = targets
+
     def forward(self, x, link=None):
-        if self.rows is not None:
+        if self.rows is not None or self.return_input or self.nll_targets is not None:
             if torch.is_grad_enabled():
-                raise BayesLMError("_ProjHolder.rows is an inference-only row selection")
-            x = x.reshape(-1, x.shape[-1]).index_select(0, self.rows)
-        if self.return_input:
-            if torch.is_grad_enabled():
-                raise BayesLMError("_ProjHolder.return_input is an inference-only path")
-            return x
-        if self.nll_targets is not None:
-            if torch.is_grad_enabled():
-                raise BayesLMError("_ProjHolder.nll_targets is an inference-only path")
-            return ops.linear_nll(x, self.weight, self.bias, self.nll_targets)
+                raise BayesLMError("_ProjHolder: rows, return_input and nll_targets are inference-only modes")
+            if self.rows is not None:
+                x = x.reshape(-1, x.shape[-1]).index_select(0, self.rows)
+            if self.return_input:
+                return x
+            if self.nll_targets is not None:
+                return ops.linear_nll(x, self.weight, self.bias, self.nll_targets)
         out = ops.linear(x, self.weight, self.bias, link)
         return ops.as_logits(out) if self.is_decoder else out  # grad mode: F.cross_entropy on it runs the engine's kernels (ops.Logits)
+
+
+def inference_decoder(model):
+    """``model.decoder`` if it takes the inference modes (_ProjHolder.inference), else None."""
+    dec = getattr(model, "decoder", None)
+    return dec if isinstance(dec, _ProjHolder) else None
 
 
 def _need_causal(attn_mask):

@@ -1407,6 +1407,18 @@ def cross_entropy_interp(logits_a, logits_b, alpha, targets):
     return nll.mean(), nll
 
 
+def _inference_only(name, *tensors):
+    """The guard of the fused decoder family: forward-only launches, refused where autograd would expect a backward."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise BayesLMError("%s is an inference-only path (no backward): call it under torch.no_grad()" % name)
+
+
+def _unit_rows(x, name):
+    """(..., K) fp32 -> its 2-D rows (M, K) with unit inner stride (a copy only when the inner stride is not 1)."""
+    x2 = _f32(x, name).reshape(-1, x.shape[-1])
+    return x2 if x2.stride(-1) == 1 else x2.contiguous()
+
+
 def linear_nll_supported(weight, bias):
     """Decoders blm_linear_nll takes: fp32 on the GPU, row-major, vocabulary a multiple of 4, 16-byte aligned bias."""
     return (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 2 and weight.is_contiguous()
@@ -1417,11 +1429,8 @@ def linear_nll(x, weight, bias, targets):
     """Inference only: per-row NLL of the decoder ``x @ weight.T + bias`` against ``targets`` without materialising the (M, V)
     logits (blm_linear_nll: softmax partials per column tile in the GEMM epilogue + a folding kernel).  What
     decoder -> log_softmax -> gather computes in train.py:452-455 / compute_sentence_scores...py:157-170.  -> (M,) NLL"""
-    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
-        raise BayesLMError("linear_nll is an inference-only path (no backward): call it under torch.no_grad()")
-    x2 = _f32(x, "x").reshape(-1, x.shape[-1])
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
+    _inference_only("linear_nll", x, weight)
+    x2 = _unit_rows(x, "x")
     M, K = x2.shape
     V = weight.shape[0]
     if weight.shape[1] != K or targets.numel() != M:
@@ -1470,45 +1479,61 @@ class McDecoder:
         self.wp, self.bp = _mc_pad(_f32(weight, "weight"), None if bias is None else _f32(bias, "bias"))
 
 
+def _mc_operands(name, x, weight, bias, S, dec, n_targets):
+    """The checks linear_mc_stats and linear_mc_logprobs share -> (x fp32, S, M, K, V, padded weight, padded bias, Sp, chunks):
+    Sp the samples rounded up to a power of two, chunks the token ranges whose M * Sp * K * 4 bytes stay under the LDS-DMA
+    loaders' 2^32.  ``n_targets``: the number of targets, or None without targets."""
+    _inference_only(name, x, weight, bias)
+    if dec is not None and (dec.weight is not weight or dec.bias is not bias):
+        raise ValueError("%s: dec was built for another decoder" % name)
+    x = _f32(x, "x")
+    if x.dim() != 3:
+        raise ValueError("%s: x must be (S, M, K)" % name)
+    S_, M, K = x.shape
+    if S is not None and int(S) != S_:
+        raise ValueError("%s: S = %d but x holds %d samples" % (name, S, S_))
+    S = S_
+    if not 1 <= S <= 64:
+        raise BayesLMError("%s: 1..64 samples, got %d" % (name, S))
+    weight = _f32(weight, "weight")
+    if weight.dim() != 2 or weight.shape[1] != K or (n_targets is not None and n_targets != M) or (
+            bias is not None and bias.numel() != weight.shape[0]):
+        raise ValueError("%s: x (S, M, K), weight (V, K), bias (V,) and M targets expected" % name)
+    if bias is not None:
+        bias = _f32(bias, "bias")
+    L.require_gfx950()
+    wp, bp = (dec.wp, dec.bp) if dec is not None else _mc_pad(weight, bias)
+    Sp = 1 << (S - 1).bit_length()
+    return x, S, M, K, weight.shape[0], wp, bp, Sp, _row_chunks(M, Sp * K)
+
+
+def _mc_token_major(x, a, b, Sp):
+    """Rows [a, b) of the sample-major (S, M, K) operand as the kernels take them: token-major (b - a, Sp, K), zeros in the
+    padding samples."""
+    S, _, K = x.shape
+    if S == Sp:
+        return x[:, a:b].transpose(0, 1).contiguous()
+    xt = torch.zeros(b - a, Sp, K, device=x.device, dtype=torch.float32)
+    xt[:, :S] = x[:, a:b].transpose(0, 1)
+    return xt
+
+
 def linear_mc_stats(x, weight, bias, targets, S=None, dec=None):
     """Inference only: token-level predictive uncertainty of S Monte-Carlo weight samples without materialising any of the
     S x M x V logits (blm_linear_mc_stats: two decoder products whose epilogues keep per-tile partials, and a folding kernel).
     ``x``: (S, M, K), sample-major as the S forward passes produce it; ``weight`` (V, K), ``bias`` (V,) or None, ``targets`` (M,).
     ``dec``: McDecoder(weight, bias) of the run, reused instead of padding the vocabulary (V % 4 != 0) again per call.
     -> McStats(nll_s (M, S), bma_nll, h_pred, mi (M,)); definitions in include/bayeslm.h."""
-    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        raise BayesLMError("linear_mc_stats is an inference-only path (no backward): call it under torch.no_grad()")
-    if dec is not None and (dec.weight is not weight or dec.bias is not bias):
-        raise ValueError("linear_mc_stats: dec was built for another decoder")
-    x = _f32(x, "x")
-    if x.dim() != 3:
-        raise ValueError("linear_mc_stats: x must be (S, M, K)")
-    S_, M, K = x.shape
-    if S is not None and int(S) != S_:
-        raise ValueError("linear_mc_stats: S = %d but x holds %d samples" % (S, S_))
-    S = S_
-    if not 1 <= S <= 64:
-        raise BayesLMError("linear_mc_stats: 1..64 samples, got %d" % S)
-    weight = _f32(weight, "weight")
-    if weight.dim() != 2 or weight.shape[1] != K or targets.numel() != M or (bias is not None and bias.numel() != weight.shape[0]):
-        raise ValueError("linear_mc_stats: x (S, M, K), weight (V, K), bias (V,) and M targets expected")
-    if bias is not None:
-        bias = _f32(bias, "bias")
-    L.require_gfx950()
-    V = weight.shape[0]
-    wp, bp = (dec.wp, dec.bp) if dec is not None else _mc_pad(weight, bias)
+    x, S, M, K, V, wp, bp, Sp, chunks = _mc_operands("linear_mc_stats", x, weight, bias, S, dec, targets.numel())
     tgt = dev_tensor(targets.reshape(-1), "targets", torch.int64)
     dev = x.device
     nll_s = torch.empty(M, S, device=dev, dtype=torch.float32)
     bma, h, mi = (torch.empty(M, device=dev, dtype=torch.float32) for _ in range(3))
     if M == 0:
         return McStats(nll_s, bma, h, mi)
-    Sp = 1 << (S - 1).bit_length()
-    chunks = _row_chunks(M, Sp * K)  # token chunks whose M * Sp * K * 4 bytes stay under the LDS-DMA loaders' 2^32
     ws = torch.empty(int(lib().blm_linear_mc_stats_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
     for a, b in chunks:
-        xt = torch.zeros(b - a, Sp, K, device=dev, dtype=torch.float32)  # token-major, samples padded to Sp rows
-        xt[:, :S] = x[:, a:b].transpose(0, 1)
+        xt = _mc_token_major(x, a, b, Sp)
         check(lib().blm_linear_mc_stats(ptr(xt), K, ptr(wp), K, ptr(bp), ptr(tgt[a:b]), S, ptr(nll_s[a:b]), ptr(bma[a:b]),
                                         ptr(h[a:b]), ptr(mi[a:b]), ptr(ws), b - a, V, K, stream()), "blm_linear_mc_stats")
     return McStats(nll_s, bma, h, mi)
@@ -1530,28 +1555,7 @@ def linear_mc_logprobs(x, weight, bias, tgt=None, S=None, dec=None, stats=True):
     (blm_linear_mc_logprobs: linear_mc_stats' two decoder products, the second one also storing log pbar from its epilogue).
     ``x``: (S, M, K) as linear_mc_stats takes it; ``dec``: the run's McDecoder; ``stats``: also h_pred and mi; ``tgt`` (M,): also
     nll_s and bma_nll.  -> McLogProbs; S = 1 gives the log-softmax."""
-    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        raise BayesLMError("linear_mc_logprobs is an inference-only path (no backward): call it under torch.no_grad()")
-    if dec is not None and (dec.weight is not weight or dec.bias is not bias):
-        raise ValueError("linear_mc_logprobs: dec was built for another decoder")
-    x = _f32(x, "x")
-    if x.dim() != 3:
-        raise ValueError("linear_mc_logprobs: x must be (S, M, K)")
-    S_, M, K = x.shape
-    if S is not None and int(S) != S_:
-        raise ValueError("linear_mc_logprobs: S = %d but x holds %d samples" % (S, S_))
-    S = S_
-    if not 1 <= S <= 64:
-        raise BayesLMError("linear_mc_logprobs: 1..64 samples, got %d" % S)
-    weight = _f32(weight, "weight")
-    if weight.dim() != 2 or weight.shape[1] != K or (tgt is not None and tgt.numel() != M) or (
-            bias is not None and bias.numel() != weight.shape[0]):
-        raise ValueError("linear_mc_logprobs: x (S, M, K), weight (V, K), bias (V,) and M targets expected")
-    if bias is not None:
-        bias = _f32(bias, "bias")
-    L.require_gfx950()
-    V = weight.shape[0]
-    wp, bp = (dec.wp, dec.bp) if dec is not None else _mc_pad(weight, bias)
+    x, S, M, K, V, wp, bp, Sp, chunks = _mc_operands("linear_mc_logprobs", x, weight, bias, S, dec, None if tgt is None else tgt.numel())
     dev = x.device
     logp, Np = _padded_rows((M,), V, dev)
     h, mi = ((torch.empty(M, device=dev, dtype=torch.float32) for _ in range(2)) if stats else (None, None))
@@ -1562,16 +1566,10 @@ def linear_mc_logprobs(x, weight, bias, tgt=None, S=None, dec=None, stats=True):
         bma = torch.empty(M, device=dev, dtype=torch.float32)
     if M == 0:
         return McLogProbs(logp, h, mi, nll_s, bma)
-    Sp = 1 << (S - 1).bit_length()
-    chunks = _row_chunks(M, Sp * K)  # token chunks whose M * Sp * K * 4 bytes stay under the LDS-DMA loaders' 2^32
     ws = torch.empty(int(lib().blm_linear_mc_logprobs_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
     for a, b in chunks:
         o_tgt, o_nll, o_bma, o_h, o_mi = (None if t is None else ptr(t[a:b]) for t in (tgt, nll_s, bma, h, mi))
-        if S == Sp:
-            xt = x[:, a:b].transpose(0, 1).contiguous()  # token-major
-        else:
-            xt = torch.zeros(b - a, Sp, K, device=dev, dtype=torch.float32)  # samples padded to Sp rows
-            xt[:, :S] = x[:, a:b].transpose(0, 1)
+        xt = _mc_token_major(x, a, b, Sp)
         check(lib().blm_linear_mc_logprobs(ptr(xt), K, ptr(wp), K, ptr(bp), o_tgt, S, ptr(logp[a:b]), Np, o_nll, o_bma, o_h, o_mi,
                                            ptr(ws), b - a, V, K, stream()),
               "blm_linear_mc_logprobs")
@@ -1598,22 +1596,31 @@ def linear_nll_interp_supported(w1, b1, w2, b2):
     return ok(w1, b1) and ok(w2, b2) and w1.shape[0] == w2.shape[0]
 
 
+def _interp_operands(name, x1, x2, dec, counts_ok, counted):
+    """The operand prelude of the two-model launches -> (rows of x1, rows of x2, M, K1, K2, V), checked against the InterpDecoder
+    ``dec``.  ``counts_ok(M)``: the caller's own count check, ``counted`` its wording in the one shape error."""
+    _inference_only(name, x1, x2)
+    a, b = _unit_rows(x1, "x1"), _unit_rows(x2, "x2")
+    M, K1 = a.shape
+    K2 = b.shape[1]
+    if b.shape[0] != M or dec.w1.shape[1] != K1 or dec.w2.shape[1] != K2 or not counts_ok(M):
+        raise ValueError("%s: x1 (M, K1), x2 (M, K2), decoders (V, K1) / (V, K2) and %s expected" % (name, counted))
+    L.require_gfx950()
+    return a, b, M, K1, K2, dec.w1.shape[0]
+
+
+def _edge_operands(edge_node, edge_tgt, device):
+    """The (node, target) pairs of a prefix-trie launch as int64 device vectors, and the (E,) NLL buffer it fills."""
+    en = dev_tensor(edge_node.reshape(-1), "edge_node", torch.int64)
+    et = dev_tensor(edge_tgt.reshape(-1), "edge_tgt", torch.int64)
+    return en, et, torch.empty(en.numel(), device=device, dtype=torch.float32)
+
+
 def linear_nll_interp(x1, x2, dec, targets):
     """Inference only: per-row NLL of the INTERPOLATED logits alpha (x1 W1^T + b1) + (1 - alpha) (x2 W2^T + b2)
     (compute_sentence_scores_bayes_jianwei.py:157-168) from ONE decoder + cross-entropy launch over the packed operands
     [alpha x1 | (1 - alpha) x2] . [W1 | W2]^T: neither model's (M, V) logits are stored.  ``dec``: InterpDecoder.  -> (M,) NLL"""
-    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
-        raise BayesLMError("linear_nll_interp is an inference-only path (no backward): call it under torch.no_grad()")
-    a = _f32(x1, "x1").reshape(-1, x1.shape[-1])
-    b = _f32(x2, "x2").reshape(-1, x2.shape[-1])
-    a = a if a.stride(-1) == 1 else a.contiguous()
-    b = b if b.stride(-1) == 1 else b.contiguous()
-    M, K1 = a.shape
-    K2 = b.shape[1]
-    V = dec.w1.shape[0]
-    if b.shape[0] != M or dec.w1.shape[1] != K1 or dec.w2.shape[1] != K2 or targets.numel() != M:
-        raise ValueError("linear_nll_interp: x1 (M, K1), x2 (M, K2), decoders (V, K1) / (V, K2) and M targets expected")
-    L.require_gfx950()
+    a, b, M, K1, K2, V = _interp_operands("linear_nll_interp", x1, x2, dec, lambda M: targets.numel() == M, "M targets")
     tgt = dev_tensor(targets.reshape(-1), "targets", torch.int64)
     nll = torch.empty(M, device=a.device, dtype=torch.float32)
     if M == 0:
@@ -1685,6 +1692,19 @@ _STATE_TAP = None
 _PACK = threading.local()  # per thread: two scorers on two threads never see each other's layout
 
 
+def _split_qkv(q, k, v, contiguous=False):
+    """The attention operands of the packed-row layouts -> (q, k, v, d, row stride): the fused (R, 1, 3d) projection in ``q``
+    (k = v = None) is addressed in place, separate (R, 1, d) tensors as they are or -- ``contiguous`` -- as contiguous copies."""
+    if k is None:
+        qkv = _f32(q, "qkv")
+        d = qkv.shape[-1] // 3
+        return qkv, qkv[..., d:], qkv[..., 2 * d:], d, 3 * d
+    qq, kk, vv = _f32(q, "q"), _f32(k, "k"), _f32(v, "v")
+    if contiguous:
+        qq, kk, vv = qq.contiguous(), kk.contiguous(), vv.contiguous()
+    return qq, kk, vv, qq.shape[-1], qq.shape[-1]
+
+
 class packed_tokens:
     """Inference helper (the n-best scorer): inside the context the Transformer stacks keep their activations as a
     compact (R, 1, d) matrix of the REAL tokens of a padded (T, N) batch of hypotheses -- every token-wise operation
@@ -1692,8 +1712,8 @@ class packed_tokens:
     batch of AMI-shaped hypotheses); only the attention core sees the padded layout (scatter before, gather after; the
     padding rows hold zeros and, the attention being causal and column-wise, never reach a real token).
     ``sel`` (R,) int64: flat indices t * N + n of the real tokens, in the order the caller wants the rows.
-    The layout is thread-local and does not nest.  (The scorer also sets ``decoder.rows`` on the model it scores with:
-    a model object serves one scoring call at a time.)"""
+    The layout is thread-local and does not nest.  (The scorer also holds the model's decoder in a ``_ProjHolder.inference``
+    scope, which refuses a second entry: a model object serves one scoring call at a time.)"""
 
     def __init__(self, sel, T, N):
         self.sel, self.T, self.N = sel, int(T), int(N)
@@ -1736,13 +1756,7 @@ class packed_tokens:
         (blm_attn_fwd_rows: the kernel finds a token's row through rowmap); anything else is scattered into the padded layout,
         run through the ordinary kernels and gathered back -- a zero fill, an index_copy and a gather per layer."""
         if self._rows_ok:
-            if k is None:
-                qkv = _f32(q, "qkv")
-                d = qkv.shape[-1] // 3
-                qq, kk, vv, ld = qkv, qkv[..., d:], qkv[..., 2 * d:], 3 * d
-            else:
-                qq, kk, vv = _f32(q, "q"), _f32(k, "k"), _f32(v, "v")
-                d = ld = qq.shape[-1]
+            qq, kk, vv, d, ld = _split_qkv(q, k, v)
             R = qq.numel() // qq.shape[-1]
             out = torch.empty(R, 1, d, device=qq.device, dtype=torch.float32)
             L.require_gfx950()
@@ -1778,13 +1792,7 @@ class tree_tokens(packed_tokens):
 
     def attention(self, q, k, v, nhead):
         """q / k / v (M, 1, d) (or q = the fused (M, 1, 3d) projection, k = v = None) -> (M, 1, d) over the trie mask."""
-        if k is None:
-            qkv = _f32(q, "qkv")
-            d = qkv.shape[-1] // 3
-            qq, kk, vv, ld = qkv, qkv[..., d:], qkv[..., 2 * d:], 3 * d
-        else:
-            qq, kk, vv = _f32(q, "q").contiguous(), _f32(k, "k").contiguous(), _f32(v, "v").contiguous()
-            d = ld = qq.shape[-1]
+        qq, kk, vv, d, ld = _split_qkv(q, k, v, contiguous=True)
         R = qq.numel() // qq.shape[-1]
         out = torch.empty(R, 1, d, device=qq.device, dtype=torch.float32)
         L.require_gfx950()
@@ -1797,20 +1805,15 @@ def linear_nll_edges(x, dec, edge_node, edge_tgt):
     """Inference only: per-edge NLL over a prefix trie, nll[e] = logsumexp(x[node] W^T + b) - (x[node] . W[tgt] + b[tgt]) for the
     E (node, target) edges, no logit stored (blm_linear_nll_edges).  ``x`` (M, K) node rows; ``dec``: McDecoder(weight, bias) of the
     scoring run (the vocabulary padded to a multiple of 4 once); ``edge_node`` / ``edge_tgt`` (E,) int64.  -> (E,) NLL"""
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise BayesLMError("linear_nll_edges is an inference-only path (no backward): call it under torch.no_grad()")
-    x2 = _f32(x, "x").reshape(-1, x.shape[-1])
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
+    _inference_only("linear_nll_edges", x)
+    x2 = _unit_rows(x, "x")
     M, K = x2.shape
     V, Np = dec.weight.shape[0], dec.wp.shape[0]
     if dec.wp.shape[1] != K or edge_node.numel() != edge_tgt.numel():
         raise ValueError("linear_nll_edges: x (M, K), a (V, K) decoder and E (node, target) pairs expected")
     L.require_gfx950()
-    en = dev_tensor(edge_node.reshape(-1), "edge_node", torch.int64)
-    et = dev_tensor(edge_tgt.reshape(-1), "edge_tgt", torch.int64)
+    en, et, nll = _edge_operands(edge_node, edge_tgt, x2.device)
     E = en.numel()
-    nll = torch.empty(E, device=x2.device, dtype=torch.float32)
     if E == 0:
         return nll
     ws = torch.empty(int(lib().blm_linear_nll_edges_ws_floats(M, Np)), device=x2.device, dtype=torch.float32)
@@ -1822,22 +1825,10 @@ def linear_nll_edges(x, dec, edge_node, edge_tgt):
 def linear_nll_interp_edges(x1, x2, dec, edge_node, edge_tgt):
     """Inference only: linear_nll_edges over two models' INTERPOLATED logits alpha (x1 W1^T + b1) + (1 - alpha) (x2 W2^T + b2)
     (the mixing of linear_nll_interp; ``dec``: the run's InterpDecoder).  -> (E,) NLL"""
-    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
-        raise BayesLMError("linear_nll_interp_edges is an inference-only path (no backward): call it under torch.no_grad()")
-    a = _f32(x1, "x1").reshape(-1, x1.shape[-1])
-    b = _f32(x2, "x2").reshape(-1, x2.shape[-1])
-    a = a if a.stride(-1) == 1 else a.contiguous()
-    b = b if b.stride(-1) == 1 else b.contiguous()
-    M, K1 = a.shape
-    K2 = b.shape[1]
-    V = dec.w1.shape[0]
-    if b.shape[0] != M or dec.w1.shape[1] != K1 or dec.w2.shape[1] != K2 or edge_node.numel() != edge_tgt.numel():
-        raise ValueError("linear_nll_interp_edges: x1 (M, K1), x2 (M, K2), decoders (V, K1) / (V, K2) and E (node, target) pairs expected")
-    L.require_gfx950()
-    en = dev_tensor(edge_node.reshape(-1), "edge_node", torch.int64)
-    et = dev_tensor(edge_tgt.reshape(-1), "edge_tgt", torch.int64)
+    a, b, M, K1, K2, V = _interp_operands("linear_nll_interp_edges", x1, x2, dec, lambda M: edge_node.numel() == edge_tgt.numel(),
+                                          "E (node, target) pairs")
+    en, et, nll = _edge_operands(edge_node, edge_tgt, a.device)
     E = en.numel()
-    nll = torch.empty(E, device=a.device, dtype=torch.float32)
     if E == 0:
         return nll
     ws = torch.empty(int(lib().blm_linear_nll2_edges_ws_floats(M, V, K1, K2)), device=a.device, dtype=torch.float32)

@@ -608,6 +608,36 @@ def test_mc_samples_refused_when_nothing_is_sampled(dev, kind):
     assert S.compute_scores_batched(nbest, m, vocab, mtype, dev)  # mean-weight scoring is unaffected
 
 
+@pytest.mark.parametrize("fam,uncertainty", [("tlm_gauss", False), ("lstm_bayes", False), ("tlm_gauss", True)])
+def test_mc_scoring_leaves_the_noise_key_as_it_found_it(dev, fam, uncertainty):
+    """compute_scores_batched(mc_samples=2) runs in model.mc_sampling: afterwards the model's (seed, step, auto_step) are the
+    values from before the call -- the step counter is not taken over -- and it is in eval mode with dropout on again and
+    the GPNN flags lowered.  A second call gives the same scores."""
+    from bayeslms_amd import compute_sentence_scores as S, model as M
+    g, _, _ = load_golden("scorer_tlm_ffn")
+    vocab, nbest = _scorer_nbest(g)
+    V = len(vocab)
+    torch.manual_seed(7)
+    if fam == "tlm_gauss":
+        m, mtype = M.GaussTransformerModel(V, 16, 4, 32, 2, 0.5, True, 3), "Transformer"
+    else:
+        m, mtype = M.BayesRNNModel("LSTM", V, 12, 12, 2, 0.5, True, 3), "LSTM"
+    m = m.to(dev)
+    m.set_seed(31337)
+    m.noise_state.step = 9
+    ns = m.noise_state
+    before = (ns.seed, ns.step, ns.auto_step)
+    assert before == (31337, 9, True)
+    first = S.compute_scores_batched(nbest, m, vocab, mtype, dev, mc_samples=2, seed=5, uncertainty=uncertainty)
+    assert (ns.seed, ns.step, ns.auto_step) == before
+    assert not m.training and ns.dropout_off is False
+    assert all(not getattr(mod, "sample", False) for mod in m.modules() if isinstance(mod, M.GPNN))
+    assert m.decoder.rows is None and m.decoder.nll_targets is None and m.decoder.return_input is False
+    again = S.compute_scores_batched(nbest, m, vocab, mtype, dev, mc_samples=2, seed=5, uncertainty=uncertainty)
+    assert (first[0] if uncertainty else first) == (again[0] if uncertainty else again)
+    assert (ns.seed, ns.step, ns.auto_step) == before
+
+
 @pytest.mark.parametrize("tag", ["tlm_ffn_interp", "lstm_bayes3_interp", "tlm_gauss3_interp", "lstm_gauss33_interp"])
 def test_scorer_cli_interpolation_matches_reference(dev, tag, tmp_path, monkeypatch):
     """--interpolation_flag 1: two models; the batched scorer takes both decoders in ONE launch over packed operands
