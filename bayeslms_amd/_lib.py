@@ -195,7 +195,15 @@ SIGNATURES = {
     "blm_clip_sgd_multi_wd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _i, _f, _f, _vp]),
 }
 
-_lib = None
+# The entries that return a VALUE (include/bayeslm.h); every other one returns a blm_status, which calls() checks
+VALUE_RETURNING = frozenset((
+    "blm_abi_version", "blm_last_error", "blm_get_gemm_mode", "blm_gemm_plan_get_cus", "blm_gemm_plan_comm_window_left",
+    "blm_mfma_probe_ws_floats", "blm_ln_bwd_ws_floats", "blm_attn_bwd_ws_floats", "blm_attn_decode_ws_floats",
+    "blm_linear_nll_ws_floats", "blm_linear_mc_stats_ws_floats", "blm_linear_mc_logprobs_ws_floats", "blm_linear_nll2_wcat_floats",
+    "blm_linear_nll2_ws_floats", "blm_linear_nll_edges_ws_floats", "blm_linear_nll2_edges_ws_floats", "blm_sqnorm_ws_floats",
+    "blm_mix2_partials", "blm_lstm_search_cell_partials", "blm_lstm_search_step_partials"))
+
+_views = None  # (raw, checked): two CDLL instances of one dlopen handle, each with its own function objects
 ROCTX_RANGES = [0]  # ranges pushed so far (BLM_ROCTX=1)
 
 
@@ -223,34 +231,57 @@ def _wrap_with_roctx(l):
 
 
 class BayesLMError(RuntimeError):
-    pass
+    status = None  # the blm_status of the failed call, where one failed
 
 
-def lib():
-    """The loaded library; raises if it is not built (no fallback)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise BayesLMError(
-                "libbayeslm_hip.so is not built (%s). Build it with `make -C bayeslms_amd/csrc` or "
-                "`python -c 'import __graft_entry__ as g; g.build()'`; there is no CPU fallback." % LIB_PATH)
-        l = C.CDLL(LIB_PATH)
+def _failure(what, rc, message):
+    e = BayesLMError("%s failed (status %d): %s" % (what, rc, message.decode("utf-8", "replace")))
+    e.status = rc
+    return e
+
+
+def _load():
+    global _views
+    if not os.path.exists(LIB_PATH):
+        raise BayesLMError(
+            "libbayeslm_hip.so is not built (%s). Build it with `make -C bayeslms_amd/csrc` or "
+            "`python -c 'import __graft_entry__ as g; g.build()'`; there is no CPU fallback." % LIB_PATH)
+    raw, checked = C.CDLL(LIB_PATH), C.CDLL(LIB_PATH)  # one dlopen handle, two sets of function objects
+    last_error = checked.blm_last_error  # the function itself: a failure's message is not a range of its own under BLM_ROCTX=1
+
+    def errcheck(rc, fn, args):
+        if rc != OK:
+            raise _failure(fn.__name__, rc, last_error())
+        return rc
+    for l in (raw, checked):
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
-        if l.blm_abi_version() != ABI_VERSION:
-            raise BayesLMError("libbayeslm_hip.so ABI %d != binding ABI %d" % (l.blm_abi_version(), ABI_VERSION))
-        if os.environ.get("BLM_ROCTX", "0") == "1":
-            _wrap_with_roctx(l)
-        _lib = l
-    return _lib
+            if l is checked and name not in VALUE_RETURNING:
+                fn.errcheck = errcheck
+    if raw.blm_abi_version() != ABI_VERSION:
+        raise BayesLMError("libbayeslm_hip.so ABI %d != binding ABI %d" % (raw.blm_abi_version(), ABI_VERSION))
+    if os.environ.get("BLM_ROCTX", "0") == "1":
+        _wrap_with_roctx(raw)
+        _wrap_with_roctx(checked)
+    _views = raw, checked
+    return _views
+
+
+def lib():
+    """The loaded library, raw: an entry returns its blm_status (see check); raises if it is not built (no fallback)."""
+    return (_views or _load())[0]
+
+
+def calls():
+    """The same library, checked (what ops calls): a non-zero blm_status raises BayesLMError with check()'s message."""
+    return (_views or _load())[1]
 
 
 def check(rc, what=""):
     if rc != OK:
-        raise BayesLMError("%s failed (status %d): %s" % (what or "libbayeslm_hip call", rc,
-                                                          lib().blm_last_error().decode("utf-8", "replace")))
+        raise _failure(what or "libbayeslm_hip call", rc, lib().blm_last_error())
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -304,7 +335,7 @@ def require_gfx950():
         raise BayesLMError("no GPU visible: bayeslms_amd runs on MI355X (gfx950) only")
     arch = C.create_string_buffer(32)
     ncu, lds = C.c_int(0), C.c_int(0)
-    check(lib().blm_query(torch.cuda.current_device(), arch, C.byref(ncu), C.byref(lds)), "blm_query")
+    calls().blm_query(torch.cuda.current_device(), arch, C.byref(ncu), C.byref(lds))
     name = arch.value.decode()
     if not name.startswith("gfx950"):
         raise BayesLMError("libbayeslm_hip.so is built for gfx950 only, device is %s" % name)

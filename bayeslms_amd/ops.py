@@ -20,12 +20,13 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib as L
-from ._lib import BayesLMError, check, dev_tensor, lib, ptr, stream
+from ._lib import BayesLMError, calls, dev_tensor, ptr, stream
 
 __all__ = ["Drop", "NoiseSpec", "ResidualLink", "linear", "bayes_linear", "ffn", "ffn_gp", "attention", "attention_qkv", "add_dropout_ln",
            "embed", "add_pe", "dropout", "cross_entropy", "kl_mean", "philox_normal", "sample_weight", "sampled", "lstm_layer", "lstm_stack2", "lstm_stack2_ok", "set_lstm_wavefront", "lstm_cell", "gp_mix", "add_rowvec",
@@ -179,8 +180,7 @@ def rows_gather_add(dst, slot, src, n_src):
     """dst[v,:] += src[slot[v],:] where 0 <= slot[v] < n_src."""
     L.require_gfx950()
     V, D = dst.shape
-    check(lib().blm_rows_gather_add(ptr(dst), ptr(dev_tensor(slot, "slot", torch.int64)), ptr(src), V, D, int(n_src),
-                                    stream()), "blm_rows_gather_add")
+    calls().blm_rows_gather_add(ptr(dst), ptr(dev_tensor(slot, "slot", torch.int64)), ptr(src), V, D, int(n_src), stream())
 
 
 def _notify(*params):
@@ -215,7 +215,7 @@ def _init_multi(items):
                     raise BayesLMError("_init_multi: %d elements into %d" % (src.numel(), dst.numel()))
                 keep.append(src)
                 arr[i] = src.data_ptr()
-        check(lib().blm_init_multi(len(part), d, a, b, n, stream()), "blm_init_multi")
+        calls().blm_init_multi(len(part), d, a, b, n, stream())
 
 
 def _grad_in_place(w):
@@ -400,6 +400,18 @@ def set_kernel_timer(t):
     _TIMER = t
 
 
+_NO_EVENT = SimpleNamespace(record=lambda: None)
+
+
+def _timer_start(fmt, T):
+    """Opens and starts a _TIMER bracket tagged ``fmt % T``; .record() on what it returns ends it (no timer: the shared no-op)."""
+    if _TIMER is None:
+        return _NO_EVENT
+    ev0, ev1 = _TIMER.bracket(fmt % T)
+    ev0.record()
+    return ev1
+
+
 # ----------------------------------------------------------------------------
 # raw GEMM
 # ----------------------------------------------------------------------------
@@ -408,19 +420,19 @@ def set_gemm_mode(mode):
     instruction (include/bayeslm.h blm_set_gemm_mode): lower precision than the reference's fp32 (4.5e-6 against
     3.6e-7 max relative error per GEMM at K = 4096), about twice the GEMM rate.  Process-wide."""
     code = {"f32": 0, "bf16x3": 1, "bf16x6": 2}[mode]
-    check(lib().blm_set_gemm_mode(code), "blm_set_gemm_mode")
+    calls().blm_set_gemm_mode(code)
 
 
 def set_option(name, value):
     """Kernel-selection options of the library (include/bayeslm.h blm_set_option): "attn_hpw", "attn_short", "attn_valu",
     "lstm_gemv", "lstm_pipe", "lstm_tail", "deterministic" (see set_deterministic).  Each of the others picks between two BUILT and parity-tested forms of a kernel; the defaults are
     the measured winners (INTEGRATION.md lists them with their tests and BLM_* environment variables)."""
-    check(lib().blm_set_option(name.encode(), int(value)), "blm_set_option")
+    calls().blm_set_option(name.encode(), int(value))
 
 
 def get_option(name):
     v = C.c_int(0)
-    check(lib().blm_get_option(name.encode(), C.byref(v)), "blm_get_option")
+    calls().blm_get_option(name.encode(), C.byref(v))
     return int(v.value)
 
 
@@ -443,22 +455,22 @@ def set_gemm_cus(n):
     """Compute units the GEMM planner may count on (0: the whole chip).  engine.GradReducer narrows it while gradient buckets
     are in flight: the collective's channel workgroups hold CUs beside the backward GEMMs (include/bayeslm.h
     blm_gemm_plan_set_cus).  Host-side state of the planner: it affects launches enqueued AFTER the call."""
-    check(lib().blm_gemm_plan_set_cus(int(n)), "blm_gemm_plan_set_cus")
+    calls().blm_gemm_plan_set_cus(int(n))
 
 
 def get_gemm_cus():
-    return int(lib().blm_gemm_plan_get_cus())
+    return int(calls().blm_gemm_plan_get_cus())
 
 
 def gemm_comm_window(us):
     """A gradient bucket expected to spend ``us`` microseconds on the links has been launched (0: the exchange is over): the
     GEMMs planned while the window is open run beside the collective's channel workgroups and take the plans measured
     there (include/bayeslm.h blm_gemm_plan_comm_window)."""
-    check(lib().blm_gemm_plan_comm_window(float(us)), "blm_gemm_plan_comm_window")
+    calls().blm_gemm_plan_comm_window(float(us))
 
 
 def get_gemm_mode():
-    return ("f32", "bf16x3", "bf16x6")[int(lib().blm_get_gemm_mode())]
+    return ("f32", "bf16x3", "bf16x6")[int(calls().blm_get_gemm_mode())]
 
 
 def gemm(op, A, B, Cout, M, N, K, lda, ldb, ldc, *, alpha=1.0, accumulate=False, epilogue=L.EPI_NONE, bias=None,
@@ -504,11 +516,11 @@ def _gemm(op, A, B, Cout, M, N, K, lda, ldb, ldc, alpha, accumulate, epilogue, b
         a.drop_col_offset = int(drop.col_offset)
         a.drop_global_cols = int(drop.global_cols or drop_B)
     a.colsum_a = ptr(colsum_a)
-    check(lib().blm_gemm(C.byref(a), stream()), "blm_gemm")
+    calls().blm_gemm(C.byref(a), stream())
 
 
 def _colsum_into(dy2, M, N, out, accumulate=True, ld=None):
-    check(lib().blm_colsum(ptr(dy2), N if ld is None else int(ld), ptr(out), M, N, 1 if accumulate else 0, stream()), "blm_colsum")
+    calls().blm_colsum(ptr(dy2), N if ld is None else int(ld), ptr(out), M, N, 1 if accumulate else 0, stream())
 
 
 # ----------------------------------------------------------------------------
@@ -650,8 +662,7 @@ def sample_weight(mu, lgstd, noise, row_lo=0, srows=None, out=None, kl_out=None,
     v = _variational(lgstd, noise, row_lo, srows)
     if out is None and (noise is not None or kl_out is None):
         out = torch.empty_like(mu)
-    check(lib().blm_sample_weight(ptr(mu), rows, cols, C.byref(v), ptr(out), ptr(kl_out), float(kl_weight), stream()),
-          "blm_sample_weight")
+    calls().blm_sample_weight(ptr(mu), rows, cols, C.byref(v), ptr(out), ptr(kl_out), float(kl_weight), stream())
     return out
 
 
@@ -674,7 +685,7 @@ class _SampleWeight(torch.autograd.Function):
         v = _variational(lgstd, noise, row_lo, lgstd.shape[0])
         gmu, _, dmu = _wgrad_target(mu, zero=True) if mu.requires_grad else (None, False, None)
         glg, _, dlg = _wgrad_target(lgstd, zero=True) if lgstd.requires_grad else (None, False, None)
-        check(lib().blm_sample_weight_bwd(ptr(dW), rows, cols, C.byref(v), ptr(gmu), ptr(glg), stream()), "blm_sample_weight_bwd")
+        calls().blm_sample_weight_bwd(ptr(dW), rows, cols, C.byref(v), ptr(gmu), ptr(glg), stream())
         _notify(mu, lgstd)
         return dmu, dlg, None, None
 
@@ -709,7 +720,7 @@ class _VarGroup(torch.autograd.Function):
             it.v = _variational(lg, noise, row_lo, lg.shape[0])
             it.w_out, it.kl_weight, it.kl_minus = ptr(W), float(klw), float(klm)
             outs.append(W)
-        check(lib().blm_variational_group_fwd(items, n, ptr(kl), stream()), "blm_variational_group_fwd")
+        calls().blm_variational_group_fwd(items, n, ptr(kl), stream())
         ctx.specs = specs
         if kl is None:
             kl = torch.zeros((), device=specs[0][0].device, dtype=torch.float32)
@@ -737,7 +748,7 @@ class _VarGroup(torch.autograd.Function):
         g = grads[n]
         if g is not None:
             g = _f32(g.reshape(1), "g")
-        check(lib().blm_variational_group_bwd(items, n, ptr(g), stream()), "blm_variational_group_bwd")
+        calls().blm_variational_group_bwd(items, n, ptr(g), stream())
         _notify(*touched)
         return (None,) * (1 + 2 * n)
 
@@ -955,7 +966,7 @@ class _FFNGP(torch.autograd.Function):
             buf, acc, dcoef = _wgrad_target(coef)
             if not acc:
                 buf.zero_()
-            check(lib().blm_gp_coef_grad(ptr(dhk), ptr(z), ptr(buf), M, F_, stream()), "blm_gp_coef_grad")
+            calls().blm_gp_coef_grad(ptr(dhk), ptr(z), ptr(buf), M, F_, stream())
         if w2.requires_grad:
             gemm(L.GEMM_TN, dy, h, _grad_buf(w2), N2, F_, M, N2, F_, F_, accumulate=True)
         if b2.requires_grad:
@@ -1013,12 +1024,12 @@ class _Attention(torch.autograd.Function):
             keep = _f32(drop.keep, "keep")
             if keep.numel() != (drop.global_cols or B) * nhead * T * T or not keep.is_contiguous():
                 raise BayesLMError("attention: keep mask must be (global_cols * nhead, T, T) contiguous")
-            check(lib().blm_attn_fwd_keep(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(lse), T, B, nhead, hd,
-                                          ptr(keep), drop.col_offset, drop.global_cols or B, stream()), "blm_attn_fwd_keep")
+            calls().blm_attn_fwd_keep(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(lse), T, B, nhead, hd,
+                                      ptr(keep), drop.col_offset, drop.global_cols or B, stream())
         else:
-            check(lib().blm_attn_fwd(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(lse), T, B, nhead, hd,
-                                     float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
-                                     drop.global_cols or B, stream()), "blm_attn_fwd")
+            calls().blm_attn_fwd(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(lse), T, B, nhead, hd,
+                                 float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
+                                 drop.global_cols or B, stream())
         ctx.save_for_backward(q, kk if not packed else None, vv if not packed else None, out, lse)
         ctx.meta = (nhead, drop, packed, d)
         return out
@@ -1038,18 +1049,18 @@ class _Attention(torch.autograd.Function):
             dq, dk, dv = (torch.empty(T, B, d, device=a.device, dtype=torch.float32) for _ in range(3))
             ldd = d
         if drop.keep is not None:
-            check(lib().blm_attn_bwd_keep(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(dout), ptr(lse),
-                                          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ldd, T, B, nhead, d // nhead,
-                                          ptr(drop.keep), drop.col_offset, drop.global_cols or B, stream()), "blm_attn_bwd_keep")
+            calls().blm_attn_bwd_keep(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(dout), ptr(lse),
+                                      dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ldd, T, B, nhead, d // nhead,
+                                      ptr(drop.keep), drop.col_offset, drop.global_cols or B, stream())
             return (dqkv, None, None, None, None) if packed else (dq, dk, dv, None, None)
         r = drop.rng() if drop.on else None
         # scratch for dS (B*nhead, T, T): the dK/dV kernel leaves it there, dQ = dS K needs no second recomputation
-        nws = int(lib().blm_attn_bwd_ws_floats(T, B, nhead, d // nhead)) if _ATTN_WS else 0
+        nws = int(calls().blm_attn_bwd_ws_floats(T, B, nhead, d // nhead)) if _ATTN_WS else 0
         ws = torch.empty(nws, device=a.device, dtype=torch.float32) if nws > 0 else None
-        check(lib().blm_attn_bwd_ws(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(dout), ptr(lse),
-                                    dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ldd, T, B, nhead, d // nhead,
-                                    float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
-                                    drop.global_cols or B, ptr(ws), nws, stream()), "blm_attn_bwd_ws")
+        calls().blm_attn_bwd_ws(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(dout), ptr(lse),
+                                dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ldd, T, B, nhead, d // nhead,
+                                float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
+                                drop.global_cols or B, ptr(ws), nws, stream())
         if packed:
             return dqkv, None, None, None, None
         return dq, dk, dv, None, None
@@ -1085,9 +1096,9 @@ class _AddDropLN(torch.autograd.Function):
         rstd = torch.empty_like(mean)
         L.require_gfx950()
         r = drop.rng() if drop.on else None
-        check(lib().blm_add_dropout_ln_fwd(ptr(x), ptr(y), ptr(gamma), ptr(beta), ptr(out), ptr(s), ptr(mean), ptr(rstd),
-                                           rows, B, D, float(eps), float(drop.p), C.byref(r) if r is not None else None,
-                                           drop.col_offset, drop.global_cols or B, stream()), "blm_add_dropout_ln_fwd")
+        calls().blm_add_dropout_ln_fwd(ptr(x), ptr(y), ptr(gamma), ptr(beta), ptr(out), ptr(s), ptr(mean), ptr(rstd),
+                                       rows, B, D, float(eps), float(drop.p), C.byref(r) if r is not None else None,
+                                       drop.col_offset, drop.global_cols or B, stream())
         ctx.save_for_backward(s, mean, rstd)
         ctx.meta = (gamma, beta, drop, rows, B, D)
         return out
@@ -1099,16 +1110,16 @@ class _AddDropLN(torch.autograd.Function):
         dout = _f32(dout, "dout")
         dx = torch.empty_like(s)
         dy = torch.empty_like(s) if drop.on else None
-        ws = torch.empty(int(lib().blm_ln_bwd_ws_floats(rows * B, D)), device=s.device, dtype=torch.float32)
+        ws = torch.empty(int(calls().blm_ln_bwd_ws_floats(rows * B, D)), device=s.device, dtype=torch.float32)
         r = drop.rng() if drop.on else None
         # frozen LayerNorm parameters (architect step): their sums land in a scratch row instead of .grad; a parameter that is not
         # the caller's contiguous leaf gets its sums back through autograd (the kernel accumulates: zeroed buffers)
         dgamma, _, rgamma = _wgrad_target(gamma, zero=True) if gamma.requires_grad else (torch.zeros_like(gamma), False, None)
         dbeta, _, rbeta = _wgrad_target(beta, zero=True) if beta.requires_grad else (torch.zeros_like(beta), False, None)
-        check(lib().blm_add_dropout_ln_bwd(ptr(dout), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dy),
-                                           ptr(dgamma), ptr(dbeta), ptr(ws), rows, B, D,
-                                           float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
-                                           drop.global_cols or B, stream()), "blm_add_dropout_ln_bwd")
+        calls().blm_add_dropout_ln_bwd(ptr(dout), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dy),
+                                       ptr(dgamma), ptr(dbeta), ptr(ws), rows, B, D,
+                                       float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
+                                       drop.global_cols or B, stream())
         _notify(gamma, beta)
         dres = dx
         if ctx.link is not None and ctx.needs_input_grad[0]:
@@ -1139,9 +1150,9 @@ class _Embed(torch.autograd.Function):
         out = torch.empty(T, B, D, device=weight.device, dtype=torch.float32)
         L.require_gfx950()
         r = drop.rng() if drop.on else None
-        check(lib().blm_embed_fwd(ptr(ids), ptr(weight), ptr(pe), ptr(out), T, B, D, V, float(scale), float(drop.p),
-                                  C.byref(r) if r is not None else None, drop.col_offset, drop.global_cols or B,
-                                  stream()), "blm_embed_fwd")
+        calls().blm_embed_fwd(ptr(ids), ptr(weight), ptr(pe), ptr(out), T, B, D, V, float(scale), float(drop.p),
+                              C.byref(r) if r is not None else None, drop.col_offset, drop.global_cols or B,
+                              stream())
         ctx.save_for_backward(ids)
         ctx.meta = (weight, scale, drop)
         return out
@@ -1158,15 +1169,15 @@ class _Embed(torch.autograd.Function):
             sink = _EMBED_SINK(weight, ids) if (_EMBED_SINK is not None and _grad_in_place(weight)) else None
             if sink is not None:
                 buf, slots, nrows, done = sink
-                check(lib().blm_embed_bwd(ptr(slots), ptr(dy), ptr(buf), T, B, D, int(nrows), float(scale),
-                                          float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
-                                          drop.global_cols or B, stream()), "blm_embed_bwd")
+                calls().blm_embed_bwd(ptr(slots), ptr(dy), ptr(buf), T, B, D, int(nrows), float(scale),
+                                      float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
+                                      drop.global_cols or B, stream())
                 done()
                 return None, None, None, None, None
             gw, _, dw = _wgrad_target(weight, zero=True)
-            check(lib().blm_embed_bwd(ptr(ids), ptr(dy), ptr(gw), T, B, D, V, float(scale),
-                                      float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
-                                      drop.global_cols or B, stream()), "blm_embed_bwd")
+            calls().blm_embed_bwd(ptr(ids), ptr(dy), ptr(gw), T, B, D, V, float(scale),
+                                  float(drop.p), C.byref(r) if r is not None else None, drop.col_offset,
+                                  drop.global_cols or B, stream())
             _notify(weight)
             return None, dw, None, None, None
         return None, None, None, None, None
@@ -1203,9 +1214,9 @@ class _AddPE(torch.autograd.Function):
         out = torch.empty_like(x)
         L.require_gfx950()
         r = drop.rng() if drop.on else None
-        check(lib().blm_add_pe_dropout(ptr(x), ptr(pe), ptr(out), T, B, D, float(drop.p),
-                                       C.byref(r) if r is not None else None, drop.col_offset, drop.global_cols or B,
-                                       stream()), "blm_add_pe_dropout")
+        calls().blm_add_pe_dropout(ptr(x), ptr(pe), ptr(out), T, B, D, float(drop.p),
+                                   C.byref(r) if r is not None else None, drop.col_offset, drop.global_cols or B,
+                                   stream())
         ctx.drop = drop
         return out
 
@@ -1246,8 +1257,7 @@ def _dropout_apply(x, drop, row0=0, out=None):
     y = torch.empty_like(x) if out is None else out
     L.require_gfx950()
     r = drop.rng()
-    check(lib().blm_dropout_rows(ptr(x), ptr(y), rows, int(row0), B, D, float(drop.p), C.byref(r), drop.col_offset,
-                                 drop.global_cols or B, stream()), "blm_dropout_rows")
+    calls().blm_dropout_rows(ptr(x), ptr(y), rows, int(row0), B, D, float(drop.p), C.byref(r), drop.col_offset, drop.global_cols or B, stream())
     return y
 
 
@@ -1289,8 +1299,7 @@ class _CrossEntropy(torch.autograd.Function):
         fuse = grad_mode and unit_grad and not keep
         lse = torch.empty(M, device=logits.device, dtype=torch.float32) if (grad_mode and not fuse) else None
         L.require_gfx950()
-        check(lib().blm_ce_fwd_bwd(ptr(logits), ld, ptr(targets), ptr(nll), ptr(lse), ptr(loss),
-                                   ptr(logits) if fuse else None, 1.0 / M, M, V, stream()), "blm_ce_fwd_bwd")
+        calls().blm_ce_fwd_bwd(ptr(logits), ld, ptr(targets), ptr(nll), ptr(lse), ptr(loss), ptr(logits) if fuse else None, 1.0 / M, M, V, stream())
         if fuse:  # the buffer now holds the gradient: any other autograd consumer of the logits must fail, not read it
             torch.autograd.graph.increment_version(whole)
         inv_count = None
@@ -1330,8 +1339,7 @@ class _CrossEntropy(torch.autograd.Function):
             out = _padded_rows(logits.shape[:-1], V, logits.device)[0]
         else:
             out = torch.empty(M, ld, device=logits.device, dtype=torch.float32)[:, :V].view(logits.shape)
-        check(lib().blm_ce_bwd(ptr(logits), ld, ptr(targets), ptr(lse), ptr(g), 1.0 / M, ptr(out), M, V, stream()),
-              "blm_ce_bwd")
+        calls().blm_ce_bwd(ptr(logits), ld, ptr(targets), ptr(lse), ptr(g), 1.0 / M, ptr(out), M, V, stream())
         if not keep:
             torch.autograd.graph.increment_version(logits)
         return out, None, None, None
@@ -1403,7 +1411,7 @@ def cross_entropy_interp(logits_a, logits_b, alpha, targets):
     M, V = a.shape
     tgt = targets.contiguous()
     nll = torch.empty(M, device=a.device, dtype=torch.float32)
-    check(lib().blm_ce_interp_fwd(ptr(a), ptr(b), V, float(alpha), ptr(tgt), ptr(nll), M, V, stream()), "blm_ce_interp_fwd")
+    calls().blm_ce_interp_fwd(ptr(a), ptr(b), V, float(alpha), ptr(tgt), ptr(nll), M, V, stream())
     return nll.mean(), nll
 
 
@@ -1438,9 +1446,8 @@ def linear_nll(x, weight, bias, targets):
     L.require_gfx950()
     tgt = targets.reshape(-1).contiguous()
     nll = torch.empty(M, device=x2.device, dtype=torch.float32)
-    ws = torch.empty(int(lib().blm_linear_nll_ws_floats(M, V)), device=x2.device, dtype=torch.float32)
-    check(lib().blm_linear_nll(ptr(x2), x2.stride(0), ptr(weight), weight.stride(0), ptr(bias), ptr(tgt), ptr(nll), None, ptr(ws),
-                               M, V, K, stream()), "blm_linear_nll")
+    ws = torch.empty(int(calls().blm_linear_nll_ws_floats(M, V)), device=x2.device, dtype=torch.float32)
+    calls().blm_linear_nll(ptr(x2), x2.stride(0), ptr(weight), weight.stride(0), ptr(bias), ptr(tgt), ptr(nll), None, ptr(ws), M, V, K, stream())
     return nll
 
 
@@ -1531,11 +1538,11 @@ def linear_mc_stats(x, weight, bias, targets, S=None, dec=None):
     bma, h, mi = (torch.empty(M, device=dev, dtype=torch.float32) for _ in range(3))
     if M == 0:
         return McStats(nll_s, bma, h, mi)
-    ws = torch.empty(int(lib().blm_linear_mc_stats_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
+    ws = torch.empty(int(calls().blm_linear_mc_stats_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
     for a, b in chunks:
         xt = _mc_token_major(x, a, b, Sp)
-        check(lib().blm_linear_mc_stats(ptr(xt), K, ptr(wp), K, ptr(bp), ptr(tgt[a:b]), S, ptr(nll_s[a:b]), ptr(bma[a:b]),
-                                        ptr(h[a:b]), ptr(mi[a:b]), ptr(ws), b - a, V, K, stream()), "blm_linear_mc_stats")
+        calls().blm_linear_mc_stats(ptr(xt), K, ptr(wp), K, ptr(bp), ptr(tgt[a:b]), S, ptr(nll_s[a:b]), ptr(bma[a:b]),
+                                    ptr(h[a:b]), ptr(mi[a:b]), ptr(ws), b - a, V, K, stream())
     return McStats(nll_s, bma, h, mi)
 
 
@@ -1566,13 +1573,12 @@ def linear_mc_logprobs(x, weight, bias, tgt=None, S=None, dec=None, stats=True):
         bma = torch.empty(M, device=dev, dtype=torch.float32)
     if M == 0:
         return McLogProbs(logp, h, mi, nll_s, bma)
-    ws = torch.empty(int(lib().blm_linear_mc_logprobs_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
+    ws = torch.empty(int(calls().blm_linear_mc_logprobs_ws_floats(max(b - a for a, b in chunks), S, V)), device=dev, dtype=torch.float32)
     for a, b in chunks:
         o_tgt, o_nll, o_bma, o_h, o_mi = (None if t is None else ptr(t[a:b]) for t in (tgt, nll_s, bma, h, mi))
         xt = _mc_token_major(x, a, b, Sp)
-        check(lib().blm_linear_mc_logprobs(ptr(xt), K, ptr(wp), K, ptr(bp), o_tgt, S, ptr(logp[a:b]), Np, o_nll, o_bma, o_h, o_mi,
-                                           ptr(ws), b - a, V, K, stream()),
-              "blm_linear_mc_logprobs")
+        calls().blm_linear_mc_logprobs(ptr(xt), K, ptr(wp), K, ptr(bp), o_tgt, S, ptr(logp[a:b]), Np, o_nll, o_bma, o_h, o_mi,
+                                       ptr(ws), b - a, V, K, stream())
     return McLogProbs(logp, h, mi, nll_s, bma)
 
 
@@ -1585,7 +1591,7 @@ class InterpDecoder:
         if self.w1.shape[0] != self.w2.shape[0]:
             raise BayesLMError("interpolated decoders need one vocabulary: %d and %d rows" % (self.w1.shape[0], self.w2.shape[0]))
         V, K1, K2 = self.w1.shape[0], self.w1.shape[1], self.w2.shape[1]
-        self.wcat = torch.empty(int(lib().blm_linear_nll2_wcat_floats(V, K1, K2)), device=self.w1.device, dtype=torch.float32)
+        self.wcat = torch.empty(int(calls().blm_linear_nll2_wcat_floats(V, K1, K2)), device=self.w1.device, dtype=torch.float32)
         self.packed = False
 
 
@@ -1625,11 +1631,10 @@ def linear_nll_interp(x1, x2, dec, targets):
     nll = torch.empty(M, device=a.device, dtype=torch.float32)
     if M == 0:
         return nll
-    ws = torch.empty(int(lib().blm_linear_nll2_ws_floats(M, V, K1, K2)), device=a.device, dtype=torch.float32)
-    check(lib().blm_linear_nll2(ptr(a), a.stride(0), ptr(dec.w1), dec.w1.stride(0), ptr(dec.b1), K1,
-                                ptr(b), b.stride(0), ptr(dec.w2), dec.w2.stride(0), ptr(dec.b2), K2, dec.alpha,
-                                ptr(tgt), ptr(nll), None, ptr(dec.wcat), 0 if dec.packed else 1, ptr(ws), M, V, stream()),
-          "blm_linear_nll2")
+    ws = torch.empty(int(calls().blm_linear_nll2_ws_floats(M, V, K1, K2)), device=a.device, dtype=torch.float32)
+    calls().blm_linear_nll2(ptr(a), a.stride(0), ptr(dec.w1), dec.w1.stride(0), ptr(dec.b1), K1,
+                            ptr(b), b.stride(0), ptr(dec.w2), dec.w2.stride(0), ptr(dec.b2), K2, dec.alpha,
+                            ptr(tgt), ptr(nll), None, ptr(dec.wcat), 0 if dec.packed else 1, ptr(ws), M, V, stream())
     dec.packed = True
     return nll
 
@@ -1649,8 +1654,7 @@ class _KLMean(torch.autograd.Function):
         n = rows * cols
         w = float(n) / float(count_override) if count_override else 1.0
         L.require_gfx950()
-        check(lib().blm_kl_mean_fwd(mu.data_ptr() + 4 * row_lo * ld, ld, ptr(lgstd), rows, cols, int(minus_one), w,
-                                    ptr(out), stream()), "blm_kl_mean_fwd")
+        calls().blm_kl_mean_fwd(mu.data_ptr() + 4 * row_lo * ld, ld, ptr(lgstd), rows, cols, int(minus_one), w, ptr(out), stream())
         ctx.meta = (mu, lgstd, row_lo, rows, cols, ld, w)
         return out
 
@@ -1661,8 +1665,8 @@ class _KLMean(torch.autograd.Function):
         # the kernel writes both gradients; a tensor that does not require one gets a scratch buffer
         gm, _, dmu = _wgrad_target(mu, zero=True) if mu.requires_grad else (torch.zeros_like(mu), False, None)
         gl, _, dlg = _wgrad_target(lgstd, zero=True) if lgstd.requires_grad else (torch.zeros_like(lgstd), False, None)
-        check(lib().blm_kl_mean_bwd(mu.data_ptr() + 4 * row_lo * ld, ld, ptr(lgstd), rows, cols, ptr(g), w,
-                                    gm.data_ptr() + 4 * row_lo * ld, ld, ptr(gl), stream()), "blm_kl_mean_bwd")
+        calls().blm_kl_mean_bwd(mu.data_ptr() + 4 * row_lo * ld, ld, ptr(lgstd), rows, cols, ptr(g), w,
+                                gm.data_ptr() + 4 * row_lo * ld, ld, ptr(gl), stream())
         _notify(mu, lgstd)
         return dmu, dlg, None, None, None
 
@@ -1681,7 +1685,7 @@ def philox_normal(n, seed, stream_id, step, device="cuda"):
     out = torch.empty(n, device=device, dtype=torch.float32)
     L.require_gfx950()
     r = L.rng(seed, stream_id, step)
-    check(lib().blm_philox_normal(ptr(out), n, C.byref(r), stream()), "blm_philox_normal")
+    calls().blm_philox_normal(ptr(out), n, C.byref(r), stream())
     return out
 
 
@@ -1760,12 +1764,13 @@ class packed_tokens:
             R = qq.numel() // qq.shape[-1]
             out = torch.empty(R, 1, d, device=qq.device, dtype=torch.float32)
             L.require_gfx950()
-            rc = lib().blm_attn_fwd_rows(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(self.rowmap()), self.T, self.N,
-                                         nhead, d // nhead, stream())
-            if rc == 0:
+            try:
+                calls().blm_attn_fwd_rows(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(self.rowmap()), self.T, self.N,
+                                          nhead, d // nhead, stream())
                 return out
-            if rc != L.ERR_UNSUPPORTED:
-                check(rc, "blm_attn_fwd_rows")
+            except BayesLMError as e:
+                if e.status != L.ERR_UNSUPPORTED:
+                    raise
             self._rows_ok = False
         if k is None:
             return self.pack(attention(self.unpack(q), nhead))
@@ -1796,8 +1801,8 @@ class tree_tokens(packed_tokens):
         R = qq.numel() // qq.shape[-1]
         out = torch.empty(R, 1, d, device=qq.device, dtype=torch.float32)
         L.require_gfx950()
-        check(lib().blm_attn_fwd_tree(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(self.end), ptr(self.lo), R, nhead,
-                                      d // nhead, stream()), "blm_attn_fwd_tree")
+        calls().blm_attn_fwd_tree(qq.data_ptr(), kk.data_ptr(), vv.data_ptr(), ld, ptr(out), ptr(self.end), ptr(self.lo), R, nhead,
+                                  d // nhead, stream())
         return out
 
 
@@ -1816,9 +1821,9 @@ def linear_nll_edges(x, dec, edge_node, edge_tgt):
     E = en.numel()
     if E == 0:
         return nll
-    ws = torch.empty(int(lib().blm_linear_nll_edges_ws_floats(M, Np)), device=x2.device, dtype=torch.float32)
-    check(lib().blm_linear_nll_edges(ptr(x2), x2.stride(0), ptr(dec.wp), dec.wp.stride(0), ptr(dec.bp), ptr(en), ptr(et), ptr(nll), ptr(ws),
-                                     M, E, Np, V, K, stream()), "blm_linear_nll_edges")
+    ws = torch.empty(int(calls().blm_linear_nll_edges_ws_floats(M, Np)), device=x2.device, dtype=torch.float32)
+    calls().blm_linear_nll_edges(ptr(x2), x2.stride(0), ptr(dec.wp), dec.wp.stride(0), ptr(dec.bp), ptr(en), ptr(et), ptr(nll), ptr(ws),
+                                 M, E, Np, V, K, stream())
     return nll
 
 
@@ -1831,11 +1836,10 @@ def linear_nll_interp_edges(x1, x2, dec, edge_node, edge_tgt):
     E = en.numel()
     if E == 0:
         return nll
-    ws = torch.empty(int(lib().blm_linear_nll2_edges_ws_floats(M, V, K1, K2)), device=a.device, dtype=torch.float32)
-    check(lib().blm_linear_nll2_edges(ptr(a), a.stride(0), ptr(dec.w1), dec.w1.stride(0), ptr(dec.b1), K1,
-                                      ptr(b), b.stride(0), ptr(dec.w2), dec.w2.stride(0), ptr(dec.b2), K2, dec.alpha,
-                                      ptr(en), ptr(et), ptr(nll), ptr(dec.wcat), 0 if dec.packed else 1, ptr(ws), M, E, V, stream()),
-          "blm_linear_nll2_edges")
+    ws = torch.empty(int(calls().blm_linear_nll2_edges_ws_floats(M, V, K1, K2)), device=a.device, dtype=torch.float32)
+    calls().blm_linear_nll2_edges(ptr(a), a.stride(0), ptr(dec.w1), dec.w1.stride(0), ptr(dec.b1), K1,
+                                  ptr(b), b.stride(0), ptr(dec.w2), dec.w2.stride(0), ptr(dec.b2), K2, dec.alpha,
+                                  ptr(en), ptr(et), ptr(nll), ptr(dec.wcat), 0 if dec.packed else 1, ptr(ws), M, E, V, stream())
     dec.packed = True
     return nll
 
@@ -1918,13 +1922,12 @@ class cached_tokens:
         self.layer += 1
         L.require_gfx950()
         T, N, hd = self.T, self.N, c.head_dim
-        check(lib().blm_kv_append(kk.data_ptr(), vv.data_ptr(), ld, ptr(kv), ptr(c.past), ptr(self.n_new), T, N, c.n_cap, nhead,
-                                  c.max_len, hd, stream()), "blm_kv_append")
-        nws = int(lib().blm_attn_decode_ws_floats(T, N, nhead, self.ctx_max, hd))
+        calls().blm_kv_append(kk.data_ptr(), vv.data_ptr(), ld, ptr(kv), ptr(c.past), ptr(self.n_new), T, N, c.n_cap, nhead, c.max_len, hd, stream())
+        nws = int(calls().blm_attn_decode_ws_floats(T, N, nhead, self.ctx_max, hd))
         ws = torch.empty(max(nws, 1), device=qq.device, dtype=torch.float32)
         out = torch.empty(T, N, d, device=qq.device, dtype=torch.float32)
-        check(lib().blm_attn_decode(qq.data_ptr(), ld, ptr(kv), ptr(c.past), ptr(self.n_new), ptr(out), ptr(ws), nws, T, N, c.n_cap,
-                                    nhead, c.max_len, hd, self.ctx_max, stream()), "blm_attn_decode")
+        calls().blm_attn_decode(qq.data_ptr(), ld, ptr(kv), ptr(c.past), ptr(self.n_new), ptr(out), ptr(ws), nws, T, N, c.n_cap,
+                                nhead, c.max_len, hd, self.ctx_max, stream())
         return self.pack(out)
 
 
@@ -1945,8 +1948,8 @@ def embed_at(ids, weight, pe, scale, pos0, x=None):
         raise BayesLMError("embed_at: pos0 must be (N,) int32")
     out = torch.empty(T, N, D, device=pe.device, dtype=torch.float32)
     L.require_gfx950()
-    check(lib().blm_embed_at(ptr(ids), ptr(weight) if ids is not None else None, V, float(scale), ptr(x), ptr(pe), pe.shape[0],
-                             ptr(pos0), ptr(out), T, N, D, stream()), "blm_embed_at")
+    calls().blm_embed_at(ptr(ids), ptr(weight) if ids is not None else None, V, float(scale), ptr(x), ptr(pe), pe.shape[0],
+                         ptr(pos0), ptr(out), T, N, D, stream())
     return out
 
 
@@ -1959,7 +1962,7 @@ def log_softmax_rows(x, V=None, out=None):
     R, V = x.shape[0], int(V if V is not None else x.shape[1])
     out = torch.empty(R, V, device=x.device, dtype=torch.float32) if out is None else out
     L.require_gfx950()
-    check(lib().blm_log_softmax_rows(ptr(x), x.stride(0), ptr(out), out.stride(0), R, V, stream()), "blm_log_softmax_rows")
+    calls().blm_log_softmax_rows(ptr(x), x.stride(0), ptr(out), out.stride(0), R, V, stream())
     return out
 
 
@@ -1979,11 +1982,10 @@ def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=
     r = L.rng(seed, stream_id, step)
     L.require_gfx950()
     if top_k == 0 and top_p == 1.0:
-        check(lib().blm_sample_rows(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), C.byref(r), ptr(out), stream()),
-              "blm_sample_rows")
+        calls().blm_sample_rows(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), C.byref(r), ptr(out), stream())
     else:
-        check(lib().blm_sample_rows_filtered(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), top_k, top_p,
-                                             C.byref(r), ptr(out), stream()), "blm_sample_rows_filtered")
+        calls().blm_sample_rows_filtered(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), top_k, top_p,
+                                         C.byref(r), ptr(out), stream())
     return out
 
 
@@ -1999,7 +2001,7 @@ def topk_rows(x, k):
     vals = torch.empty(R, k, device=x.device, dtype=torch.float32)
     ids = torch.empty(R, k, device=x.device, dtype=torch.int64)
     L.require_gfx950()
-    check(lib().blm_topk_rows(ptr(x), x.stride(0), R, V, k, ptr(vals), ptr(ids), stream()), "blm_topk_rows")
+    calls().blm_topk_rows(ptr(x), x.stride(0), R, V, k, ptr(vals), ptr(ids), stream())
     return vals, ids
 
 
@@ -2019,8 +2021,8 @@ def beam_select(cand_vals, cand_ids, score, finished, beams, eos):
     parent = torch.empty(n, device=score.device, dtype=torch.int64)
     token = torch.empty(n, device=score.device, dtype=torch.int64)
     L.require_gfx950()
-    check(lib().blm_beam_select(ptr(cand_vals), ptr(cand_ids), ptr(score), ptr(finished), n // B, B, cand_vals.shape[1], int(eos),
-                                ptr(score_out), ptr(fin_out), ptr(parent), ptr(token), stream()), "blm_beam_select")
+    calls().blm_beam_select(ptr(cand_vals), ptr(cand_ids), ptr(score), ptr(finished), n // B, B, cand_vals.shape[1], int(eos),
+                            ptr(score_out), ptr(fin_out), ptr(parent), ptr(token), stream())
     return score_out, fin_out, parent, token
 
 
@@ -2032,8 +2034,8 @@ def kv_gather(src, dst, idx, n_src, outer, nhead, max_len, head_dim, len_src=Non
         raise BayesLMError("kv_gather: source and destination must be two states of the same shape")
     idx = dev_tensor(idx, "idx", torch.int64)
     L.require_gfx950()
-    check(lib().blm_kv_gather(ptr(src), ptr(dst), ptr(idx), ptr(len_src), ptr(len_dst), idx.numel(), int(n_src), n_cap, outer, nhead,
-                              max_len, head_dim, stream()), "blm_kv_gather")
+    calls().blm_kv_gather(ptr(src), ptr(dst), ptr(idx), ptr(len_src), ptr(len_dst), idx.numel(), int(n_src), n_cap, outer, nhead,
+                          max_len, head_dim, stream())
     return dst
 
 
@@ -2087,6 +2089,11 @@ def _bias_pair_grads(b_refs, dbs, needs):
     return out
 
 
+def _new(dev, *shape):
+    """Uninitialised fp32 scratch on ``dev``: every element is written by a kernel before it is read."""
+    return torch.empty(*shape, device=dev, dtype=torch.float32)
+
+
 class _LSTMLayer(torch.autograd.Function):
     """One layer over T steps.  Input GEMM batched over T (M = T*B), recurrent GEMM + fused cell per
     step.  Weights arrive already sampled (W = mu + noise on the gate rows)."""
@@ -2100,13 +2107,13 @@ class _LSTMLayer(torch.autograd.Function):
         H = w_hh.shape[1]
         G = 4 * H
         dev = x.device
-        bias = torch.empty(G, device=dev, dtype=torch.float32)
-        hs = torch.empty(T + 1, B, H, device=dev, dtype=torch.float32)
-        cs = torch.empty(T + 1, B, H, device=dev, dtype=torch.float32)
+        bias = _new(dev, G)
+        hs = _new(dev, T + 1, B, H)
+        cs = _new(dev, T + 1, B, H)
         _init_multi([(bias, b_ih, b_hh), (hs[0], h0, None), (cs[0], c0, None)])  # one launch: b_ih + b_hh, the initial state
-        xw = torch.empty(T, B, G, device=dev, dtype=torch.float32)
+        xw = _new(dev, T, B, G)
         gemm(L.GEMM_NT, x, w_ih, xw, T * B, G, E, E, E, G, epilogue=L.EPI_BIAS, bias=bias)
-        ga = torch.empty(T, B, G, device=dev, dtype=torch.float32)
+        ga = _new(dev, T, B, G)
         st = stream()
         # one launch per step (recurrent product + cell, blm_lstm_step_fwd) when the shape allows it,
         # else skinny GEMM + cell kernel
@@ -2117,21 +2124,16 @@ class _LSTMLayer(torch.autograd.Function):
             # from B ~ 200 on (n-best rescoring 64.5 k -> 70-72 k hypotheses/s)
             fused_step = False
         if fused_step:  # the whole layer from one call: T launches issued by the library
-            ev = _TIMER.bracket("lstm_seq_fwd T=%d" % T) if _TIMER is not None else None
-            if ev:
-                ev[0].record()
-            check(lib().blm_lstm_seq_fwd(ptr(xw), ptr(w_hh), ptr(hs), ptr(cs), ptr(ga), ptr(noise_rows), T, B, H, st),
-                  "blm_lstm_seq_fwd")
-            if ev:
-                ev[1].record()
+            ev = _timer_start("lstm_seq_fwd T=%d", T)
+            calls().blm_lstm_seq_fwd(ptr(xw), ptr(w_hh), ptr(hs), ptr(cs), ptr(ga), ptr(noise_rows), T, B, H, st)
+            ev.record()
         else:
-            hw = torch.empty(B, G, device=dev, dtype=torch.float32)
+            hw = _new(dev, B, G)
             for t in range(T):
                 gemm(L.GEMM_NT, hs[t], w_hh, hw, B, G, H, H, H, G)
-                check(lib().blm_lstm_cell_fwd(ptr(xw[t]), ptr(hw), ptr(cs[t]), ptr(hs[t + 1]), ptr(cs[t + 1]), ptr(ga[t]),
-                                              B, H, st), "blm_lstm_cell_fwd")
+                calls().blm_lstm_cell_fwd(ptr(xw[t]), ptr(hw), ptr(cs[t]), ptr(hs[t + 1]), ptr(cs[t + 1]), ptr(ga[t]), B, H, st)
                 if noise_rows is not None:
-                    check(lib().blm_add_rowvec(ptr(hs[t + 1]), ptr(noise_rows[t]), B, H, st), "blm_add_rowvec")
+                    calls().blm_add_rowvec(ptr(hs[t + 1]), ptr(noise_rows[t]), B, H, st)
         if _STATE_TAP is not None:
             _STATE_TAP.layers.append((hs.index_select(0, _STATE_TAP.idx), cs.index_select(0, _STATE_TAP.idx)))
         ctx.save_for_backward(x, hs, cs, ga, w_ih, w_hh)
@@ -2149,11 +2151,11 @@ class _LSTMLayer(torch.autograd.Function):
         G = 4 * H
         dev = x.device
         dy = torch.zeros(T, B, H, device=dev, dtype=torch.float32) if dy is None else _f32(dy, "dy")
-        dgates = torch.empty(T, B, G, device=dev, dtype=torch.float32)
+        dgates = _new(dev, T, B, G)
         st = stream()
-        dh = torch.empty(B, H, device=dev, dtype=torch.float32)
-        dcs = torch.empty(2, B, H, device=dev, dtype=torch.float32)  # ping-pong dc buffers
-        db = torch.empty(G, device=dev, dtype=torch.float32)
+        dh = _new(dev, B, H)
+        dcs = _new(dev, 2, B, H)  # ping-pong dc buffers
+        db = _new(dev, G)
         _init_multi([(dh, dhT, None), (dcs[0], dcT, None), (db, None, None)])  # one launch: incoming state gradients (or zeros), db = 0
         fused_step = (H % 32 == 0 and w_hh.is_contiguous() and w_hh.data_ptr() % 16 == 0 and dgates.data_ptr() % 16 == 0)
         noise = getattr(ctx, "has_noise", False)
@@ -2165,20 +2167,16 @@ class _LSTMLayer(torch.autograd.Function):
         if fused_step:
             # one launch per step: dh_{t-1} = dgates_t . W_hh on the matrix cores with the cell backward
             # of step t-1 fused behind it (blm_lstm_step_bwd); W_hh is transposed once per layer
-            w_t = torch.empty(H, G, device=dev, dtype=torch.float32)
-            check(lib().blm_transpose(ptr(w_hh), ptr(w_t), G, H, st), "blm_transpose")
-            ev = _TIMER.bracket("lstm_seq_bwd T=%d" % T) if _TIMER is not None else None
-            if ev:
-                ev[0].record()
+            w_t = _new(dev, H, G)
+            calls().blm_transpose(ptr(w_hh), ptr(w_t), G, H, st)
+            ev = _timer_start("lstm_seq_bwd T=%d", T)
             # the whole chain from one call (step T-1: the plain cell backward; every earlier step one fused launch)
-            check(lib().blm_lstm_seq_bwd(ptr(dh), ptr(dy), ptr(cs), ptr(ga), ptr(w_t), ptr(dgates), ptr(dcs), 0,
-                                         ptr(dhr) if noise else None, T, T, 0, B, H, st), "blm_lstm_seq_bwd")
+            calls().blm_lstm_seq_bwd(ptr(dh), ptr(dy), ptr(cs), ptr(ga), ptr(w_t), ptr(dgates), ptr(dcs), 0,
+                                     ptr(dhr) if noise else None, T, T, 0, B, H, st)
             k = T & 1
-            dh = torch.empty(B, H, device=dev, dtype=torch.float32)
-            check(lib().blm_lstm_step_bwd(ptr(dgates[0]), ptr(w_t), None, None, None, None, None, None, None, ptr(dh),
-                                          B, H, st), "blm_lstm_step_bwd")
-            if ev:
-                ev[1].record()
+            dh = _new(dev, B, H)
+            calls().blm_lstm_step_bwd(ptr(dgates[0]), ptr(w_t), None, None, None, None, None, None, None, ptr(dh), B, H, st)
+            ev.record()
             dc = dcs[k]
         else:
             # recurrent dh of every step accumulates (split-K atomics) into one pre-zeroed buffer: a
@@ -2186,14 +2184,14 @@ class _LSTMLayer(torch.autograd.Function):
             dh0 = torch.zeros(B, H, device=dev, dtype=torch.float32)
             for t in range(T - 1, -1, -1):
                 k = (T - 1 - t) & 1
-                check(lib().blm_lstm_cell_bwd2(ptr(dhr[t]), ptr(dy[t]), ptr(dcs[k]), ptr(cs[t]), ptr(cs[t + 1]), ptr(ga[t]),
-                                               ptr(dgates[t]), ptr(dcs[k ^ 1]), B, H, st), "blm_lstm_cell_bwd2")
+                calls().blm_lstm_cell_bwd2(ptr(dhr[t]), ptr(dy[t]), ptr(dcs[k]), ptr(cs[t]), ptr(cs[t + 1]), ptr(ga[t]),
+                                           ptr(dgates[t]), ptr(dcs[k ^ 1]), B, H, st)
                 gemm(L.GEMM_NN, dgates[t], w_hh, dhr[t - 1] if t > 0 else dh0, B, H, G, G, H, H, accumulate=True)
             dh = dh0
             dc = dcs[T & 1]
         d_noise = None
         if noise:  # noise row t was added to every batch row of h_t: its gradient is the column sum of dh_t
-            d_noise = torch.empty(T, H, device=dev, dtype=torch.float32)
+            d_noise = _new(dev, T, H)
             tot = dhr + dy
             for t in range(T):
                 _colsum_into(tot[t], B, H, d_noise[t], accumulate=False)
@@ -2306,22 +2304,19 @@ class _LSTMStack2(torch.autograd.Function):
         G = 4 * H
         dev = x.device
         st = stream
-        lib_ = lib()
-        new = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)  # noqa: E731
-        bias1, bias2 = new(G), new(G)
-        hs1, cs1, ga1 = new(T + 1, B, H), new(T + 1, B, H), new(T, B, G)
-        hs2, cs2, ga2 = new(T + 1, B, H), new(T + 1, B, H), new(T, B, G)
+        lib_ = calls()
+        bias1, bias2 = _new(dev, G), _new(dev, G)
+        hs1, cs1, ga1 = _new(dev, T + 1, B, H), _new(dev, T + 1, B, H), _new(dev, T, B, G)
+        hs2, cs2, ga2 = _new(dev, T + 1, B, H), _new(dev, T + 1, B, H), _new(dev, T, B, G)
         # one launch: both layers' b_ih + b_hh and the four initial states into row 0 of the state histories
         _init_multi([(bias1, b_ih1, b_hh1), (bias2, b_ih2, b_hh2), (hs1[0], h0a, None), (cs1[0], c0a, None), (hs2[0], h0b, None),
                      (cs2[0], c0b, None)])
-        xw1 = new(T, B, G)
+        xw1 = _new(dev, T, B, G)
         gemm(L.GEMM_NT, x, w_ih1, xw1, T * B, G, E, E, E, G, epilogue=L.EPI_BIAS, bias=bias1)
-        xw2 = new(T, B, G)
-        x2 = new(T, B, H) if drop.on else None  # layer 2's input = drop(h1) (nn.LSTM's inter-layer dropout)
+        xw2 = _new(dev, T, B, G)
+        x2 = _new(dev, T, B, H) if drop.on else None  # layer 2's input = drop(h1) (nn.LSTM's inter-layer dropout)
         main, side = torch.cuda.current_stream(), _side_stream()
-        tev = _TIMER.bracket("lstm_stack2_fwd T=%d" % T) if _TIMER is not None else None
-        if tev:
-            tev[0].record()
+        tev = _timer_start("lstm_stack2_fwd T=%d", T)
         bh, bg = B * H * 4, B * G * 4  # bytes per time row
         p_xw1, p_xw2 = xw1.data_ptr(), xw2.data_ptr()
         p = {k: v.data_ptr() for k, v in (("hs1", hs1), ("cs1", cs1), ("ga1", ga1), ("hs2", hs2), ("cs2", cs2), ("ga2", ga2))}
@@ -2339,9 +2334,9 @@ class _LSTMStack2(torch.autograd.Function):
                     gemm(L.GEMM_NT, inp, w_ih2, xw2[a0:a1], (a1 - a0) * B, G, H, H, H, G, epilogue=L.EPI_BIAS, bias=bias2)
                 t0, t1 = cur if cur is not None else (0, 0)
                 a0, a1 = prev if prev is not None else (0, 0)
-                check(lib_.blm_lstm_seq_pair_fwd(p_xw1 + t0 * bg, ptr(w_hh1), p["hs1"] + t0 * bh, p["cs1"] + t0 * bh, p["ga1"] + t0 * bg, t1 - t0,
-                                                 p_xw2 + a0 * bg, ptr(w_hh2), p["hs2"] + a0 * bh, p["cs2"] + a0 * bh, p["ga2"] + a0 * bg, a1 - a0,
-                                                 B, H, st()), "blm_lstm_seq_pair_fwd")
+                lib_.blm_lstm_seq_pair_fwd(p_xw1 + t0 * bg, ptr(w_hh1), p["hs1"] + t0 * bh, p["cs1"] + t0 * bh, p["ga1"] + t0 * bg, t1 - t0,
+                                           p_xw2 + a0 * bg, ptr(w_hh2), p["hs2"] + a0 * bh, p["cs2"] + a0 * bh, p["ga2"] + a0 * bg, a1 - a0,
+                                           B, H, st())
                 prev = cur
             chunks = []
         else:
@@ -2354,8 +2349,7 @@ class _LSTMStack2(torch.autograd.Function):
                 between.wait_stream(main)
 
         def layer1(t0, t1):
-            check(lib_.blm_lstm_seq_fwd(p_xw1 + t0 * bg, ptr(w_hh1), p["hs1"] + t0 * bh, p["cs1"] + t0 * bh, p["ga1"] + t0 * bg,
-                                        None, t1 - t0, B, H, st()), "blm_lstm_seq_fwd")
+            lib_.blm_lstm_seq_fwd(p_xw1 + t0 * bg, ptr(w_hh1), p["hs1"] + t0 * bh, p["cs1"] + t0 * bh, p["ga1"] + t0 * bg, None, t1 - t0, B, H, st())
             ev = torch.cuda.Event()
             ev.record(main)
             return ev
@@ -2376,8 +2370,7 @@ class _LSTMStack2(torch.autograd.Function):
             with torch.cuda.stream(side):
                 if three:
                     side.wait_event(ev2)
-                check(lib_.blm_lstm_seq_fwd(p_xw2 + t0 * bg, ptr(w_hh2), p["hs2"] + t0 * bh, p["cs2"] + t0 * bh,
-                                            p["ga2"] + t0 * bg, None, n, B, H, st()), "blm_lstm_seq_fwd")
+                lib_.blm_lstm_seq_fwd(p_xw2 + t0 * bg, ptr(w_hh2), p["hs2"] + t0 * bh, p["cs2"] + t0 * bh, p["ga2"] + t0 * bg, None, n, B, H, st())
         # issue order with three streams: layer 1's NEXT chunk goes to its stream before the host turns to layer 2's previous one,
         # so the leading recurrence never waits for the host
         pend = None
@@ -2393,8 +2386,7 @@ class _LSTMStack2(torch.autograd.Function):
             layer2(*pend)
         if chunks:
             main.wait_stream(side)
-        if tev:
-            tev[1].record()
+        tev.record()
         if _STATE_TAP is not None:
             _STATE_TAP.layers.append((hs1.index_select(0, _STATE_TAP.idx), cs1.index_select(0, _STATE_TAP.idx)))
             _STATE_TAP.layers.append((hs2.index_select(0, _STATE_TAP.idx), cs2.index_select(0, _STATE_TAP.idx)))
@@ -2413,18 +2405,17 @@ class _LSTMStack2(torch.autograd.Function):
         H = w_hh1.shape[1]
         G = 4 * H
         dev = x.device
-        lib_ = lib()
+        lib_ = calls()
         st = stream
         dy = torch.zeros(T, B, H, device=dev, dtype=torch.float32) if dy is None else _f32(dy, "dy")
-        new = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)  # noqa: E731
 
         def state(w_hh):
-            w_t = new(H, G)
-            check(lib_.blm_transpose(ptr(w_hh), ptr(w_t), G, H, st()), "blm_transpose")
-            return {"dh": new(B, H), "dcs": new(2, B, H), "k": 0, "w_t": w_t, "dg": new(T, B, G)}
+            w_t = _new(dev, H, G)
+            lib_.blm_transpose(ptr(w_hh), ptr(w_t), G, H, st())
+            return {"dh": _new(dev, B, H), "dcs": _new(dev, 2, B, H), "k": 0, "w_t": w_t, "dg": _new(dev, T, B, G)}
         s1, s2 = state(w_hh1), state(w_hh2)
-        dy1 = new(T, B, H)  # gradient reaching layer 1's outputs = layer 2's input gradient
-        db1, db2 = new(G), new(G)
+        dy1 = _new(dev, T, B, H)  # gradient reaching layer 1's outputs = layer 2's input gradient
+        db1, db2 = _new(dev, G), _new(dev, G)
         # one launch: the incoming state gradients (or zeros) of both layers, zeroed bias gradients, and dy1 = 0 -- its chunks are
         # written by K-sliced products that would each need a memset of their own otherwise
         _init_multi([(s1["dh"], dh1T, None), (s1["dcs"][0], dc1T, None), (s2["dh"], dh2T, None), (s2["dcs"][0], dc2T, None),
@@ -2434,14 +2425,12 @@ class _LSTMStack2(torch.autograd.Function):
         def chain(s, dyp, cs, ga, t_hi, t_lo):
             """dgates[t] for t = t_hi-1 .. t_lo (descending) of one layer from one call: the first launch of the whole chain is the
             plain cell backward of step T-1, every other one the fused step (dh_t = dgates[t+1] . W_hh, then the cell of step t)."""
-            check(lib_.blm_lstm_seq_bwd(ptr(s["dh"]), dyp, ptr(cs), ptr(ga), ptr(s["w_t"]), ptr(s["dg"]), ptr(s["dcs"]), s["k"], None,
-                                        T, t_hi, t_lo, B, H, st()), "blm_lstm_seq_bwd")
+            lib_.blm_lstm_seq_bwd(ptr(s["dh"]), dyp, ptr(cs), ptr(ga), ptr(s["w_t"]), ptr(s["dg"]), ptr(s["dcs"]), s["k"], None,
+                                  T, t_hi, t_lo, B, H, st())
             s["k"] ^= (t_hi - t_lo) & 1
         main, side, between = torch.cuda.current_stream(), _side_stream(), _side_stream(1)
-        dh01, dh02 = new(B, H), new(B, H)  # allocated on the main stream's pool, like everything else both streams touch
-        tev = _TIMER.bracket("lstm_stack2_bwd T=%d" % T) if _TIMER is not None else None
-        if tev:
-            tev[0].record()
+        dh01, dh02 = _new(dev, B, H), _new(dev, B, H)  # allocated on the main stream's pool, like everything else both streams touch
+        tev = _timer_start("lstm_stack2_bwd T=%d", T)
         chunks = _stack_chunks(T)
         three = len(chunks) > 4  # as in forward
         if not three:
@@ -2471,11 +2460,9 @@ class _LSTMStack2(torch.autograd.Function):
         # gradient w.r.t. the initial states: dh_{-1} = dgates[0] . W_hh
         for s, strm, d in ((s2, side, dh02), (s1, main, dh01)):
             with torch.cuda.stream(strm):
-                check(lib_.blm_lstm_step_bwd(ptr(s["dg"][0]), ptr(s["w_t"]), None, None, None, None, None, None, None, ptr(d),
-                                             B, H, st()), "blm_lstm_step_bwd")
+                lib_.blm_lstm_step_bwd(ptr(s["dg"][0]), ptr(s["w_t"]), None, None, None, None, None, None, None, ptr(d), B, H, st())
         main.wait_stream(side)
-        if tev:
-            tev[1].record()
+        tev.record()
         dc02, dc01 = s2["dcs"][s2["k"]], s1["dcs"][s1["k"]]
         dg1, dg2 = s1["dg"], s2["dg"]
         inp2 = x2 if drop.on else hs1[1:]
@@ -2573,24 +2560,24 @@ class _LSTMRecurrentGP(torch.autograd.Function):
                                % (tuple(w_rec.shape), None if w_cell is None else tuple(w_cell.shape), G))
         dev = xw.device
         L.require_gfx950()
-        hs = torch.empty(T + 1, B, H, device=dev, dtype=torch.float32)
-        cs = torch.empty(T + 1, B, H, device=dev, dtype=torch.float32)
+        hs = _new(dev, T + 1, B, H)
+        cs = _new(dev, T + 1, B, H)
         hs[0].copy_(h0)
         cs[0].copy_(c0)
-        ga = torch.empty(T, B, G, device=dev, dtype=torch.float32)
-        zs = torch.empty(T, B, G if ovr == 4 else H, device=dev, dtype=torch.float32) if ovr >= 0 else None
+        ga = _new(dev, T, B, G)
+        zs = _new(dev, T, B, G if ovr == 4 else H) if ovr >= 0 else None
         st = stream()
         xw_p, hs_p, cs_p, ga_p = _P(xw), _P(hs), _P(cs), _P(ga)
         zs_p = None if zs is None else _P(zs)
         w_p, co_p, rb_p = ptr(w_rec), ptr(coef4), ptr(rbias)
-        step_fwd = lib().blm_lstm_step_fwd_gp
-        step_dh = lib().blm_lstm_step_dh
+        step_fwd = calls().blm_lstm_step_fwd_gp
+        step_dh = calls().blm_lstm_step_dh
         wc_p = ptr(w_cell)
         for t in range(T):
             if ovr == 5:  # z_t = c_{t-1} Wg^T: the second recurrent product of the step, one skinny launch in front of it
-                check(step_dh(cs_p[t], wc_p, zs_p[t], B, H, H, st), "blm_lstm_step_dh")
-            check(step_fwd(xw_p[t], w_p, hs_p[t], cs_p[t], hs_p[t + 1], cs_p[t + 1], ga_p[t], None, ovr, co_p, rb_p,
-                           None if zs_p is None else zs_p[t], B, H, st), "blm_lstm_step_fwd_gp")
+                step_dh(cs_p[t], wc_p, zs_p[t], B, H, H, st)
+            step_fwd(xw_p[t], w_p, hs_p[t], cs_p[t], hs_p[t + 1], cs_p[t + 1], ga_p[t], None, ovr, co_p, rb_p,
+                     None if zs_p is None else zs_p[t], B, H, st)
         if _STATE_TAP is not None:
             _STATE_TAP.layers.append((hs.index_select(0, _STATE_TAP.idx), cs.index_select(0, _STATE_TAP.idx)))
         ctx.save_for_backward(hs, cs, ga, w_rec, *([zs, coef4] if ovr >= 0 else []), *([w_cell] if ovr == 5 else []))
@@ -2613,40 +2600,39 @@ class _LSTMRecurrentGP(torch.autograd.Function):
         dev = ga.device
         dy = _f32(dy, "dy")
         st = stream()
-        dgates = torch.empty(T, B, G, device=dev, dtype=torch.float32)
-        dact = torch.empty(T, B, H, device=dev, dtype=torch.float32) if (0 <= ovr < 4 or ovr == 5) else None
+        dgates = _new(dev, T, B, G)
+        dact = _new(dev, T, B, H) if (0 <= ovr < 4 or ovr == 5) else None
         # A operands of the next products: ovr 4 -- d z of the hidden projection (B,4H); ovr 5 -- d z of the cell-state GPNN (B,H)
-        dzs = torch.empty(T, B, G if ovr == 4 else H, device=dev, dtype=torch.float32) if ovr >= 4 else None
+        dzs = _new(dev, T, B, G if ovr == 4 else H) if ovr >= 4 else None
         dh = torch.zeros(B, H, device=dev, dtype=torch.float32) if dhT is None else _f32(dhT, "dhT").clone()
         dcs = torch.zeros(2, B, H, device=dev, dtype=torch.float32)
         if dcT is not None:
             dcs[0].copy_(dcT)
-        w_t = torch.empty(H, G, device=dev, dtype=torch.float32)
-        check(lib().blm_transpose(ptr(w_rec), ptr(w_t), G, H, st), "blm_transpose")
+        w_t = _new(dev, H, G)
+        calls().blm_transpose(ptr(w_rec), ptr(w_t), G, H, st)
         # last step: plain cell backward (the GP gate as an external activation), then the mixture's derivative
         if 0 <= ovr < 4:
-            check(lib().blm_axpy(ptr(dy[T - 1]), ptr(dh), B * H, 1.0, st), "blm_axpy")
-            check(lib().blm_lstm_cell_ovr_bwd(ptr(dh), ptr(dcs[0]), ptr(cs[T - 1]), ptr(cs[T]), ptr(ga[T - 1]), ovr,
-                                              ptr(dgates[T - 1]), ptr(dact[T - 1]), ptr(dcs[1]), B, H, st), "blm_lstm_cell_ovr_bwd")
-            dz = torch.empty(B, H, device=dev, dtype=torch.float32)
-            check(lib().blm_gp_mix_bwd(ptr(dact[T - 1]), ptr(zs[T - 1]), ptr(coef4), ptr(dz), B, H, st), "blm_gp_mix_bwd")
+            calls().blm_axpy(ptr(dy[T - 1]), ptr(dh), B * H, 1.0, st)
+            calls().blm_lstm_cell_ovr_bwd(ptr(dh), ptr(dcs[0]), ptr(cs[T - 1]), ptr(cs[T]), ptr(ga[T - 1]), ovr,
+                                          ptr(dgates[T - 1]), ptr(dact[T - 1]), ptr(dcs[1]), B, H, st)
+            dz = _new(dev, B, H)
+            calls().blm_gp_mix_bwd(ptr(dact[T - 1]), ptr(zs[T - 1]), ptr(coef4), ptr(dz), B, H, st)
             dgates[T - 1][:, ovr * H:(ovr + 1) * H].copy_(dz)
         else:
             c_in = cs[T - 1]
             if ovr == 5:  # the last step's cell saw the mixture of z_{T-1}
-                c_in = torch.empty(B, H, device=dev, dtype=torch.float32)
-                check(lib().blm_gp_mix_fwd(ptr(zs[T - 1]), ptr(coef4), ptr(c_in), B, H, st), "blm_gp_mix_fwd")
-            check(lib().blm_lstm_cell_bwd2(ptr(dh), ptr(dy[T - 1]), ptr(dcs[0]), ptr(c_in), ptr(cs[T]), ptr(ga[T - 1]),
-                                           ptr(dgates[T - 1]), ptr(dcs[1]), B, H, st), "blm_lstm_cell_bwd2")
+                c_in = _new(dev, B, H)
+                calls().blm_gp_mix_fwd(ptr(zs[T - 1]), ptr(coef4), ptr(c_in), B, H, st)
+            calls().blm_lstm_cell_bwd2(ptr(dh), ptr(dy[T - 1]), ptr(dcs[0]), ptr(c_in), ptr(cs[T]), ptr(ga[T - 1]),
+                                       ptr(dgates[T - 1]), ptr(dcs[1]), B, H, st)
             if ovr == 5:
-                w_cell_t = torch.empty(H, H, device=dev, dtype=torch.float32)
-                check(lib().blm_transpose(ptr(w_cell), ptr(w_cell_t), H, H, st), "blm_transpose")
+                w_cell_t = _new(dev, H, H)
+                calls().blm_transpose(ptr(w_cell), ptr(w_cell_t), H, H, st)
                 dact[T - 1].copy_(dcs[1])
-                check(lib().blm_gp_mix_bwd(ptr(dcs[1]), ptr(zs[T - 1]), ptr(coef4), ptr(dzs[T - 1]), B, H, st), "blm_gp_mix_bwd")
-                check(lib().blm_lstm_step_dh(ptr(dzs[T - 1]), ptr(w_cell_t), ptr(dcs[1]), B, H, H, st), "blm_lstm_step_dh")
+                calls().blm_gp_mix_bwd(ptr(dcs[1]), ptr(zs[T - 1]), ptr(coef4), ptr(dzs[T - 1]), B, H, st)
+                calls().blm_lstm_step_dh(ptr(dzs[T - 1]), ptr(w_cell_t), ptr(dcs[1]), B, H, H, st)
             if ovr == 4:
-                check(lib().blm_gp_mix_bwd(ptr(dgates[T - 1]), ptr(zs[T - 1]), ptr(coef4), ptr(dzs[T - 1]), B, G, st),
-                      "blm_gp_mix_bwd")
+                calls().blm_gp_mix_bwd(ptr(dgates[T - 1]), ptr(zs[T - 1]), ptr(coef4), ptr(dzs[T - 1]), B, G, st)
         A = dzs if ovr == 4 else dgates
         k = 1
         A_p, dy_p, cs_p, ga_p, dg_p, dcs_p = _P(A), _P(dy), _P(cs), _P(ga), _P(dgates), _P(dcs)
@@ -2654,34 +2640,33 @@ class _LSTMRecurrentGP(torch.autograd.Function):
         da_p = None if dact is None else _P(dact)
         dzs_p = None if dzs is None else _P(dzs)
         wt_p, co_p = ptr(w_t), ptr(coef4)
-        step_bwd = lib().blm_lstm_step_bwd_gp
+        step_bwd = calls().blm_lstm_step_bwd_gp
         wct_p = ptr(w_cell_t) if ovr == 5 else None
-        step_dh = lib().blm_lstm_step_dh
+        step_dh = calls().blm_lstm_step_dh
         for t in range(T - 1, 0, -1):
-            check(step_bwd(A_p[t], wt_p, dy_p[t - 1], dcs_p[k], cs_p[t - 1], cs_p[t], ga_p[t - 1], dg_p[t - 1], dcs_p[k ^ 1], None,
-                           ovr, co_p, None if zs_p is None else zs_p[t - 1], None if da_p is None else da_p[t - 1],
-                           None if dzs_p is None else dzs_p[t - 1], B, H, st), "blm_lstm_step_bwd_gp")
+            step_bwd(A_p[t], wt_p, dy_p[t - 1], dcs_p[k], cs_p[t - 1], cs_p[t], ga_p[t - 1], dg_p[t - 1], dcs_p[k ^ 1], None,
+                     ovr, co_p, None if zs_p is None else zs_p[t - 1], None if da_p is None else da_p[t - 1],
+                     None if dzs_p is None else dzs_p[t - 1], B, H, st)
             if ovr == 5:  # raw cell-state gradient of the earlier step: d z . Wg
-                check(step_dh(dzs_p[t - 1], wct_p, dcs_p[k ^ 1], B, H, H, st), "blm_lstm_step_dh")
+                step_dh(dzs_p[t - 1], wct_p, dcs_p[k ^ 1], B, H, H, st)
             k ^= 1
-        dh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
-        check(lib().blm_lstm_step_bwd(ptr(A[0]), ptr(w_t), None, None, None, None, None, None, None, ptr(dh0), B, H, st),
-              "blm_lstm_step_bwd")
+        dh0 = _new(dev, B, H)
+        calls().blm_lstm_step_bwd(ptr(A[0]), ptr(w_t), None, None, None, None, None, None, None, ptr(dh0), B, H, st)
         dw = torch.empty_like(w_rec)
         gemm(L.GEMM_TN, A, hs, dw, G, H, T * B, G, H, H)  # hs[0:T] = h_{t-1}
         dcoef = drb = dwc = None
         if 0 <= ovr < 4 or ovr == 5:
             dcoef = torch.zeros_like(coef4)
-            check(lib().blm_gp_coef_grad(ptr(dact), ptr(zs), ptr(dcoef), T * B, H, st), "blm_gp_coef_grad")
+            calls().blm_gp_coef_grad(ptr(dact), ptr(zs), ptr(dcoef), T * B, H, st)
         if ovr == 5:  # the cell-state GPNN's affine map, batched over all steps: dWg = dz^T c_{t-1}, db = column sums of dz
             dwc = torch.empty_like(w_cell)
             gemm(L.GEMM_TN, dzs, cs, dwc, H, H, T * B, H, H, H)  # cs[0:T] = c_{t-1}
-            drb = torch.empty(H, device=dev, dtype=torch.float32)
+            drb = _new(dev, H)
             _colsum_into(dzs, T * B, H, drb, accumulate=False)
         elif ovr == 4:
             dcoef = torch.zeros_like(coef4)
-            check(lib().blm_gp_coef_grad(ptr(dgates), ptr(zs), ptr(dcoef), T * B, G, st), "blm_gp_coef_grad")
-            drb = torch.empty(G, device=dev, dtype=torch.float32)
+            calls().blm_gp_coef_grad(ptr(dgates), ptr(zs), ptr(dcoef), T * B, G, st)
+            drb = _new(dev, G)
             _colsum_into(dzs, T * B, G, drb, accumulate=False)
         return dgates, dh0, dcs[k], dw, dcoef, None, drb, dwc
 
@@ -2738,32 +2723,30 @@ class _LSTMRecurrentGPNN2(torch.autograd.Function):
             raise BayesLMError("lstm_recurrent_gpnn2: needs n_MC_terms < %d, H %% 64 == 0, a GPNN2(H, %d)" % (MP, NO))
         dev = xw.device
         L.require_gfx950()
-        lib_, st = lib(), stream()
-        new = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)  # noqa: E731
+        lib_, st = calls(), stream()
         nF = T if noises is not None else 1
         # F_t^T with zero rows m >= M (the w_t operand of the feature product) and F_t padded along m (the w_t operand of
         # d x = d f . F_t^T), all T of them in ONE launch, with the noise of calls 0..T-1 of the step-wise path
-        FT, Fp = new(nF, MP, H), new(nF, H, GP)
+        FT, Fp = _new(dev, nF, MP, H), _new(dev, nF, H, GP)
         eps_all, rng0 = _LSTMRecurrentGPNN2._noise(noises, dev)
         if noises is None:
             eps_all = torch.zeros(1, H, M, device=dev, dtype=torch.float32)  # mean frequencies at every step
-        check(lib_.blm_gpnn2_sample_steps(ptr(_f32(fmean, "frequency_mean")), ptr(_f32(flgstd, "frequency_lgstd")), ptr(eps_all),
-                                          C.byref(rng0) if rng0 is not None else None, nF, H, M, MP, GP, ptr(FT), ptr(Fp), st),
-              "blm_gpnn2_sample_steps")
+        lib_.blm_gpnn2_sample_steps(ptr(_f32(fmean, "frequency_mean")), ptr(_f32(flgstd, "frequency_lgstd")), ptr(eps_all),
+                                    C.byref(rng0) if rng0 is not None else None, nF, H, M, MP, GP, ptr(FT), ptr(Fp), st)
         cwp = torch.zeros(NO, GP, device=dev, dtype=torch.float32)  # [coef.weight | coef.bias | 0]
         cwp[:, :M].copy_(coef_w)
         cwp[:, M].copy_(coef_b)
-        hs, cs = new(T + 1, B, H), new(T + 1, B, H)
+        hs, cs = _new(dev, T + 1, B, H), _new(dev, T + 1, B, H)
         hs[0].copy_(h0)
         cs[0].copy_(c0)
-        ga = new(T, B, G4)
-        z4 = new(T, B, G4) if mode == 0 else None
-        pre = new(T, B, H) if mode == 0 else None
-        feat, gout = new(T, B, MP), new(T, B, NO)
+        ga = _new(dev, T, B, G4)
+        z4 = _new(dev, T, B, G4) if mode == 0 else None
+        pre = _new(dev, T, B, H) if mode == 0 else None
+        feat, gout = _new(dev, T, B, MP), _new(dev, T, B, NO)
         sact = torch.zeros(T, B, GP, device=dev, dtype=torch.float32)  # the feature product writes columns < MP; the padding stays 0
         q = _LSTMRecurrentGPNN2._desc(mode, g, acts, T, B, H, M, nF, xw=xw, w_hh=w_hh, FT=FT, Fp=Fp, cwp=cwp, hs=hs, cs=cs, ga=ga, z4=z4,
                                       pre=pre, feat=feat, sact=sact, gout=gout)
-        check(lib_.blm_lstm_gpnn2_seq_fwd(C.byref(q), st), "blm_lstm_gpnn2_seq_fwd")
+        lib_.blm_lstm_gpnn2_seq_fwd(C.byref(q), st)
         if _STATE_TAP is not None:
             _STATE_TAP.layers.append((hs.index_select(0, _STATE_TAP.idx), cs.index_select(0, _STATE_TAP.idx)))
         ctx.save_for_backward(hs, cs, ga, feat, sact, Fp, cwp, *([w_hh] if mode != 2 else []), *([pre] if mode == 0 else []),
@@ -2785,24 +2768,23 @@ class _LSTMRecurrentGPNN2(torch.autograd.Function):
         NO = cwp.shape[0]
         dev = ga.device
         dy = _f32(dy, "dy")
-        lib_, st = lib(), stream()
-        new = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)  # noqa: E731
+        lib_, st = calls(), stream()
         nF = Fp.shape[0]
         w_t = None
         if mode != 2:
-            w_t = new(H, G4)
-            check(lib_.blm_transpose(ptr(w_hh), ptr(w_t), G4, H, st), "blm_transpose")
-        cwt = new(GP, NO)
-        check(lib_.blm_transpose(ptr(cwp), ptr(cwt), NO, GP, st), "blm_transpose")
-        dgates, df = new(T, B, G4), new(T, B, GP)
-        da = new(T, B, H) if mode != 2 else None
+            w_t = _new(dev, H, G4)
+            lib_.blm_transpose(ptr(w_hh), ptr(w_t), G4, H, st)
+        cwt = _new(dev, GP, NO)
+        lib_.blm_transpose(ptr(cwp), ptr(cwt), NO, GP, st)
+        dgates, df = _new(dev, T, B, G4), _new(dev, T, B, GP)
+        da = _new(dev, T, B, H) if mode != 2 else None
         dh = torch.zeros(B, H, device=dev, dtype=torch.float32) if dhT is None else _f32(dhT, "dhT").clone()
         dcs = torch.zeros(2, B, H, device=dev, dtype=torch.float32)
         if dcT is not None:
             dcs[0].copy_(dcT)
         q = _LSTMRecurrentGPNN2._desc(mode, g, acts, T, B, H, M, nF, w_hh_t=w_t, Fp=Fp, cwt=cwt, cs=cs, ga=ga, feat=feat, gout=gout, dy=dy,
                                       dh=dh, dcs2=dcs, dgates=dgates, da=da, df=df)
-        check(lib_.blm_lstm_gpnn2_seq_bwd(C.byref(q), st), "blm_lstm_gpnn2_seq_bwd")
+        lib_.blm_lstm_gpnn2_seq_bwd(C.byref(q), st)
         k = T & 1
         dw = None
         if mode != 2:
@@ -2811,7 +2793,7 @@ class _LSTMRecurrentGPNN2(torch.autograd.Function):
         dcw = dcb = None
         if need_cw or need_cb:
             dout = dgates if mode == 2 else da  # the gradient of the GPNN2's output, all steps
-            dcwp = new(NO, GP)
+            dcwp = _new(dev, NO, GP)
             gemm(L.GEMM_TN, dout, sact, dcwp, NO, GP, T * B, NO, GP, GP)  # column M of s is the constant 1: its row is d coef.bias
             dcw = dcwp[:, :M].contiguous() if need_cw else None
             dcb = dcwp[:, M].contiguous() if need_cb else None
@@ -2825,10 +2807,10 @@ class _LSTMRecurrentGPNN2(torch.autograd.Function):
             if noises is None:  # mean frequencies (deterministic GPNN2): d mean only, one contraction over all T*B rows
                 eps_all = torch.zeros(1, H, M, device=dev, dtype=torch.float32)
                 Tn, Bn = 1, T * B
-            check(lib_.blm_gpnn2_freq_grad(ptr(x_in), ptr(df), ptr(eps_all), C.byref(rng0) if rng0 is not None else None,
-                                           ptr(flgstd), ptr(_grad_buf(fmean)) if fmean.requires_grad else None,
-                                           ptr(_grad_buf(flgstd)) if (flgstd.requires_grad and noises is not None) else None,
-                                           Tn, Bn, H, M, GP, st), "blm_gpnn2_freq_grad")
+            lib_.blm_gpnn2_freq_grad(ptr(x_in), ptr(df), ptr(eps_all), C.byref(rng0) if rng0 is not None else None,
+                                     ptr(flgstd), ptr(_grad_buf(fmean)) if fmean.requires_grad else None,
+                                     ptr(_grad_buf(flgstd)) if (flgstd.requires_grad and noises is not None) else None,
+                                     Tn, Bn, H, M, GP, st)
             _notify(fmean, flgstd)
         return dgates, dh, dcs[k], dw, dcw, dcb, None, None, None, None, None, None
 
@@ -2849,25 +2831,23 @@ class _GPNN2Steps(torch.autograd.Function):
             raise BayesLMError("gpnn2_steps: needs n_MC_terms < %d, input width %% 64 == 0" % MP)
         dev = x.device
         L.require_gfx950()
-        lib_, st = lib(), stream()
-        new = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)  # noqa: E731
+        lib_, st = calls(), stream()
         nF = T if noises is not None else 1
-        FT, Fp = new(nF, MP, E), new(nF, E, GP)
+        FT, Fp = _new(dev, nF, MP, E), _new(dev, nF, E, GP)
         eps_all, rng0 = _LSTMRecurrentGPNN2._noise(noises, dev)
         if noises is None:
             eps_all = torch.zeros(1, E, M, device=dev, dtype=torch.float32)
-        check(lib_.blm_gpnn2_sample_steps(ptr(_f32(fmean, "frequency_mean")), ptr(_f32(flgstd, "frequency_lgstd")), ptr(eps_all),
-                                          C.byref(rng0) if rng0 is not None else None, nF, E, M, MP, GP, ptr(FT), ptr(Fp), st),
-              "blm_gpnn2_sample_steps")
+        lib_.blm_gpnn2_sample_steps(ptr(_f32(fmean, "frequency_mean")), ptr(_f32(flgstd, "frequency_lgstd")), ptr(eps_all),
+                                    C.byref(rng0) if rng0 is not None else None, nF, E, M, MP, GP, ptr(FT), ptr(Fp), st)
         cwp = torch.zeros(NO, GP, device=dev, dtype=torch.float32)
         cwp[:, :M].copy_(coef_w)
         cwp[:, M].copy_(coef_b)
-        feat, sact = new(T, B, MP), new(T, B, GP)
+        feat, sact = _new(dev, T, B, MP), _new(dev, T, B, GP)
         x_p, f_p, FT_p = _P(x), _P(feat), _P(FT)
         for t in range(T):
-            check(lib_.blm_lstm_step_dh(x_p[t], FT_p[t if nF > 1 else 0], f_p[t], B, MP, E, st), "blm_lstm_step_dh")
-        check(lib_.blm_gpnn2_actsum_fwd(ptr(feat), ptr(sact), T * B, M, MP, GP, 1.0 / math.sqrt(M), acts, st), "blm_gpnn2_actsum_fwd")
-        out = new(T, B, NO)
+            lib_.blm_lstm_step_dh(x_p[t], FT_p[t if nF > 1 else 0], f_p[t], B, MP, E, st)
+        lib_.blm_gpnn2_actsum_fwd(ptr(feat), ptr(sact), T * B, M, MP, GP, 1.0 / math.sqrt(M), acts, st)
+        out = _new(dev, T, B, NO)
         gemm(L.GEMM_NT, sact, cwp, out, T * B, NO, GP, GP, GP, NO)
         ctx.save_for_backward(x, feat, sact, Fp, cwp)
         ctx.meta = (acts, M, fmean, flgstd, noises, coef_w.requires_grad, coef_b.requires_grad)
@@ -2882,22 +2862,21 @@ class _GPNN2Steps(torch.autograd.Function):
         MP, GP = _LSTMRecurrentGPNN2.MP, _LSTMRecurrentGPNN2.GP
         dev = x.device
         dout = _f32(dout, "dout")
-        lib_, st = lib(), stream()
-        new = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)  # noqa: E731
+        lib_, st = calls(), stream()
         nF = Fp.shape[0]
-        ds = new(T, B, GP)
+        ds = _new(dev, T, B, GP)
         gemm(L.GEMM_NN, dout, cwp, ds, T * B, GP, NO, NO, GP, GP)
-        df = new(T, B, GP)
-        check(lib_.blm_gpnn2_actsum_bwd(ptr(ds), ptr(feat), ptr(df), T * B, M, MP, GP, 1.0 / math.sqrt(M), acts, st), "blm_gpnn2_actsum_bwd")
+        df = _new(dev, T, B, GP)
+        lib_.blm_gpnn2_actsum_bwd(ptr(ds), ptr(feat), ptr(df), T * B, M, MP, GP, 1.0 / math.sqrt(M), acts, st)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = new(T, B, E)
+            dx = _new(dev, T, B, E)
             df_p, dx_p, Fp_p = _P(df), _P(dx), _P(Fp)
             for t in range(T):
-                check(lib_.blm_lstm_step_dh(df_p[t], Fp_p[t if nF > 1 else 0], dx_p[t], B, E, GP, st), "blm_lstm_step_dh")
+                lib_.blm_lstm_step_dh(df_p[t], Fp_p[t if nF > 1 else 0], dx_p[t], B, E, GP, st)
         dcw = dcb = None
         if need_cw or need_cb:
-            dcwp = new(NO, GP)
+            dcwp = _new(dev, NO, GP)
             gemm(L.GEMM_TN, dout, sact, dcwp, NO, GP, T * B, NO, GP, GP)
             dcw = dcwp[:, :M].contiguous() if need_cw else None
             dcb = dcwp[:, M].contiguous() if need_cb else None
@@ -2907,10 +2886,10 @@ class _GPNN2Steps(torch.autograd.Function):
             if noises is None:
                 eps_all = torch.zeros(1, E, M, device=dev, dtype=torch.float32)
                 Tn, Bn = 1, T * B
-            check(lib_.blm_gpnn2_freq_grad(ptr(x), ptr(df), ptr(eps_all), C.byref(rng0) if rng0 is not None else None, ptr(flgstd),
-                                           ptr(_grad_buf(fmean)) if fmean.requires_grad else None,
-                                           ptr(_grad_buf(flgstd)) if (flgstd.requires_grad and noises is not None) else None,
-                                           Tn, Bn, E, M, GP, st), "blm_gpnn2_freq_grad")
+            lib_.blm_gpnn2_freq_grad(ptr(x), ptr(df), ptr(eps_all), C.byref(rng0) if rng0 is not None else None, ptr(flgstd),
+                                     ptr(_grad_buf(fmean)) if fmean.requires_grad else None,
+                                     ptr(_grad_buf(flgstd)) if (flgstd.requires_grad and noises is not None) else None,
+                                     Tn, Bn, E, M, GP, st)
             _notify(fmean, flgstd)
         return dx, dcw, dcb, None, None, None, None
 
@@ -2976,17 +2955,15 @@ class _LSTMCellStep(torch.autograd.Function):
         xw, hw, c_prev = _f32(xw, "xw"), _f32(hw, "hw"), _f32(c_prev, "c_prev")
         B, G = xw.shape
         H = G // 4
-        h = torch.empty(B, H, device=xw.device, dtype=torch.float32)
+        h = _new(xw.device, B, H)
         c = torch.empty_like(h)
-        ga = torch.empty(B, G, device=xw.device, dtype=torch.float32)
+        ga = _new(xw.device, B, G)
         L.require_gfx950()
         if gate_ovr is None:
-            check(lib().blm_lstm_cell_fwd(ptr(xw), ptr(hw), ptr(c_prev), ptr(h), ptr(c), ptr(ga), B, H, stream()),
-                  "blm_lstm_cell_fwd")
+            calls().blm_lstm_cell_fwd(ptr(xw), ptr(hw), ptr(c_prev), ptr(h), ptr(c), ptr(ga), B, H, stream())
         else:
             gate_ovr = _f32(gate_ovr, "gate_ovr")
-            check(lib().blm_lstm_cell_ovr_fwd(ptr(xw), ptr(hw), ptr(c_prev), ptr(gate_ovr), int(gate_idx), ptr(h), ptr(c),
-                                              ptr(ga), B, H, stream()), "blm_lstm_cell_ovr_fwd")
+            calls().blm_lstm_cell_ovr_fwd(ptr(xw), ptr(hw), ptr(c_prev), ptr(gate_ovr), int(gate_idx), ptr(h), ptr(c), ptr(ga), B, H, stream())
         ctx.save_for_backward(c_prev, c, ga)
         ctx.meta = (gate_ovr is not None, int(gate_idx), B, H)
         return h, c
@@ -2998,16 +2975,14 @@ class _LSTMCellStep(torch.autograd.Function):
         dev = c.device
         dh = torch.zeros(B, H, device=dev) if dh is None else _f32(dh, "dh")
         dc = None if dc is None else _f32(dc, "dc")
-        dgates = torch.empty(B, 4 * H, device=dev, dtype=torch.float32)
-        dc_prev = torch.empty(B, H, device=dev, dtype=torch.float32)
+        dgates = _new(dev, B, 4 * H)
+        dc_prev = _new(dev, B, H)
         d_ovr = None
         if has_ovr:
-            d_ovr = torch.empty(B, H, device=dev, dtype=torch.float32)
-            check(lib().blm_lstm_cell_ovr_bwd(ptr(dh), ptr(dc), ptr(c_prev), ptr(c), ptr(ga), gidx, ptr(dgates), ptr(d_ovr),
-                                              ptr(dc_prev), B, H, stream()), "blm_lstm_cell_ovr_bwd")
+            d_ovr = _new(dev, B, H)
+            calls().blm_lstm_cell_ovr_bwd(ptr(dh), ptr(dc), ptr(c_prev), ptr(c), ptr(ga), gidx, ptr(dgates), ptr(d_ovr), ptr(dc_prev), B, H, stream())
         else:
-            check(lib().blm_lstm_cell_bwd(ptr(dh), ptr(dc), ptr(c_prev), ptr(c), ptr(ga), ptr(dgates), ptr(dc_prev), B, H,
-                                          stream()), "blm_lstm_cell_bwd")
+            calls().blm_lstm_cell_bwd(ptr(dh), ptr(dc), ptr(c_prev), ptr(c), ptr(ga), ptr(dgates), ptr(dc_prev), B, H, stream())
         return dgates, dgates, dc_prev, d_ovr, None
 
 
@@ -3025,7 +3000,7 @@ class _GPMix(torch.autograd.Function):
         M = z.numel() // N
         out = torch.empty_like(z)
         L.require_gfx950()
-        check(lib().blm_gp_mix_fwd(ptr(z), ptr(coef4), ptr(out), M, N, stream()), "blm_gp_mix_fwd")
+        calls().blm_gp_mix_fwd(ptr(z), ptr(coef4), ptr(out), M, N, stream())
         ctx.save_for_backward(z, coef4)
         return out
 
@@ -3036,9 +3011,9 @@ class _GPMix(torch.autograd.Function):
         N = z.shape[-1]
         M = z.numel() // N
         dz = torch.empty_like(z)
-        check(lib().blm_gp_mix_bwd(ptr(dout), ptr(z), ptr(coef4), ptr(dz), M, N, stream()), "blm_gp_mix_bwd")
+        calls().blm_gp_mix_bwd(ptr(dout), ptr(z), ptr(coef4), ptr(dz), M, N, stream())
         dcoef = torch.zeros_like(coef4)
-        check(lib().blm_gp_coef_grad(ptr(dout), ptr(z), ptr(dcoef), M, N, stream()), "blm_gp_coef_grad")
+        calls().blm_gp_coef_grad(ptr(dout), ptr(z), ptr(dcoef), M, N, stream())
         return dz, dcoef
 
 
@@ -3055,14 +3030,14 @@ class _AddRowVec(torch.autograd.Function):
         v = _f32(v, "v")
         B, H = out.shape
         L.require_gfx950()
-        check(lib().blm_add_rowvec(ptr(out), ptr(v), B, H, stream()), "blm_add_rowvec")
+        calls().blm_add_rowvec(ptr(out), ptr(v), B, H, stream())
         return out
 
     @staticmethod
     def backward(ctx, g):
         g = _f32(g, "g")
         B, H = g.shape
-        dv = torch.empty(H, device=g.device, dtype=torch.float32)
+        dv = _new(g.device, H)
         _colsum_into(g, B, H, dv, accumulate=False)
         return g, dv
 
@@ -3085,7 +3060,7 @@ class PtrTable:
         self.bufs = torch.tensor([b.data_ptr() for b in bufs], dtype=torch.int64, device=dev)
         self.sizes = torch.tensor([p.numel() for p in params], dtype=torch.int64, device=dev)
         self.sq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.ws = torch.zeros(int(lib().blm_sqnorm_ws_floats(self.n)), dtype=torch.float32, device=dev)
+        self.ws = torch.zeros(int(calls().blm_sqnorm_ws_floats(self.n)), dtype=torch.float32, device=dev)
         self._keep = (params, grads, bufs)
 
 
@@ -3095,24 +3070,23 @@ def clip_sgd(table, clip, lr, momentum, first, grad_scale=1.0, weight_decay=0.0)
     L.require_gfx950()
     table.sq.zero_()
     st = stream()
-    check(lib().blm_sqnorm_multi(ptr(table.grads), ptr(table.sizes), table.n, ptr(table.sq), ptr(table.ws), st),
-          "blm_sqnorm_multi")
+    calls().blm_sqnorm_multi(ptr(table.grads), ptr(table.sizes), table.n, ptr(table.sq), ptr(table.ws), st)
     if weight_decay:
-        check(lib().blm_clip_sgd_multi_wd(ptr(table.params), ptr(table.grads), ptr(table.bufs), ptr(table.sizes), table.n,
-                                          ptr(table.sq), float(clip), float(lr), float(momentum), 1 if first else 0,
-                                          float(grad_scale), float(weight_decay), st), "blm_clip_sgd_multi_wd")
+        calls().blm_clip_sgd_multi_wd(ptr(table.params), ptr(table.grads), ptr(table.bufs), ptr(table.sizes), table.n,
+                                      ptr(table.sq), float(clip), float(lr), float(momentum), 1 if first else 0,
+                                      float(grad_scale), float(weight_decay), st)
     else:
-        check(lib().blm_clip_sgd_multi(ptr(table.params), ptr(table.grads), ptr(table.bufs), ptr(table.sizes), table.n,
-                                       ptr(table.sq), float(clip), float(lr), float(momentum), 1 if first else 0,
-                                       float(grad_scale), st), "blm_clip_sgd_multi")
+        calls().blm_clip_sgd_multi(ptr(table.params), ptr(table.grads), ptr(table.bufs), ptr(table.sizes), table.n,
+                                   ptr(table.sq), float(clip), float(lr), float(momentum), 1 if first else 0,
+                                   float(grad_scale), st)
     return table.sq
 
 
 def adam_step(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
     """In-place torch.optim.Adam update of one tensor (architect.py:33); ``step`` counts from 1."""
     L.require_gfx950()
-    check(lib().blm_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
-                              float(eps), float(weight_decay), int(step), stream()), "blm_adam_step")
+    calls().blm_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+                          float(eps), float(weight_decay), int(step), stream())
 
 
 # ----------------------------------------------------------------------------
@@ -3120,7 +3094,7 @@ def adam_step(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0
 # ----------------------------------------------------------------------------
 def _reduce_partials(partial, k):
     """(n, k) per-block partial sums -> (k,) on the device."""
-    out = torch.empty(k, device=partial.device, dtype=torch.float32)
+    out = _new(partial.device, k)
     _colsum_into(partial, partial.numel() // k, k, out, accumulate=False)
     return out
 
@@ -3143,7 +3117,7 @@ class _Mix2(torch.autograd.Function):
         out = torch.empty_like(a)
         dp, drng, dco, dgc = _drop_args(drop, B)
         L.require_gfx950()
-        check(lib().blm_mix2_fwd(ptr(a), ptr(b), ptr(probs), ptr(out), rows, B, N, dp, drng, dco, dgc, stream()), "blm_mix2_fwd")
+        calls().blm_mix2_fwd(ptr(a), ptr(b), ptr(probs), ptr(out), rows, B, N, dp, drng, dco, dgc, stream())
         ctx.save_for_backward(a, b, probs)
         ctx.meta = (drop, rows, B, N)
         return out
@@ -3155,10 +3129,9 @@ class _Mix2(torch.autograd.Function):
         dout = _f32(dout, "dout")
         da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        partial = torch.empty(int(lib().blm_mix2_partials(rows, B, N)), device=a.device, dtype=torch.float32)
+        partial = _new(a.device, int(calls().blm_mix2_partials(rows, B, N)))
         dp, drng, dco, dgc = _drop_args(drop, B)
-        check(lib().blm_mix2_bwd(ptr(dout), ptr(a), ptr(b), ptr(probs), None, ptr(da), ptr(db), ptr(partial), rows, B, N, dp,
-                                 drng, dco, dgc, stream()), "blm_mix2_bwd")
+        calls().blm_mix2_bwd(ptr(dout), ptr(a), ptr(b), ptr(probs), None, ptr(da), ptr(db), ptr(partial), rows, B, N, dp, drng, dco, dgc, stream())
         dprobs = _reduce_partials(partial, 2) if ctx.needs_input_grad[2] else None
         return da, db, dprobs, None
 
@@ -3184,17 +3157,16 @@ class _SearchFFN(torch.autograd.Function):
         rows = M // B
         dev = x.device
         need_bwd = any(ctx.needs_input_grad)
-        a1 = torch.empty(M, F_, device=dev, dtype=torch.float32) if need_bwd else None
-        zg = torch.empty(M, F_, device=dev, dtype=torch.float32) if need_bwd else None
-        h1 = torch.empty(M, F_, device=dev, dtype=torch.float32)
-        hg = torch.empty(M, F_, device=dev, dtype=torch.float32)
+        a1 = _new(dev, M, F_) if need_bwd else None
+        zg = _new(dev, M, F_) if need_bwd else None
+        h1 = _new(dev, M, F_)
+        hg = _new(dev, M, F_)
         gemm(L.GEMM_NT, x, w1, h1, M, F_, D, D, D, F_, epilogue=L.EPI_BIAS_GELU, bias=b1, aux=a1)
         gemm(L.GEMM_NT, x, wg, hg, M, F_, D, D, D, F_, epilogue=L.EPI_GP_MIX, bias=bg, aux=zg, coef=coef)
-        s = torch.empty(M, F_, device=dev, dtype=torch.float32)
+        s = _new(dev, M, F_)
         dp, drng, dco, dgc = _drop_args(drop, B)
-        check(lib().blm_mix2_fwd(ptr(h1), ptr(hg), ptr(probs), ptr(s), rows, B, F_, dp, drng, dco, dgc, stream()),
-              "blm_mix2_fwd")
-        y = torch.empty(*x.shape[:-1], N2, device=dev, dtype=torch.float32)
+        calls().blm_mix2_fwd(ptr(h1), ptr(hg), ptr(probs), ptr(s), rows, B, F_, dp, drng, dco, dgc, stream())
+        y = _new(dev, *x.shape[:-1], N2)
         gemm(L.GEMM_NT, s, w2, y, M, N2, F_, F_, F_, N2, epilogue=L.EPI_BIAS, bias=b2)
         ctx.save_for_backward(x, a1, h1, zg, hg, s, probs)
         ctx.p = (w1, b1, wg, bg, coef, w2, b2, drop, B)
@@ -3211,24 +3183,24 @@ class _SearchFFN(torch.autograd.Function):
         rows = M // B
         dev = x.device
         st = stream()
-        ds = torch.empty(M, F_, device=dev, dtype=torch.float32)
+        ds = _new(dev, M, F_)
         gemm(L.GEMM_NN, dy, w2, ds, M, F_, N2, N2, F_, F_)
-        partial = torch.empty(int(lib().blm_mix2_partials(rows, B, F_)), device=dev, dtype=torch.float32)
-        dz1 = torch.empty(M, F_, device=dev, dtype=torch.float32)
-        dzg = torch.empty(M, F_, device=dev, dtype=torch.float32)
+        partial = _new(dev, int(calls().blm_mix2_partials(rows, B, F_)))
+        dz1 = _new(dev, M, F_)
+        dzg = _new(dev, M, F_)
         dp, drng, dco, dgc = _drop_args(drop, B)
         # one pass: dz1 = p0 g GELU'(z1), dzg = p1 g mixture'(zg), the two mixing-weight partials, and -- only when
         # the coefficients want their gradient -- dhg = p1 g for blm_gp_coef_grad
-        dhg = torch.empty(M, F_, device=dev, dtype=torch.float32) if coef.requires_grad else None
-        check(lib().blm_mix2_gp_bwd(ptr(ds), ptr(h1), ptr(hg), ptr(probs), ptr(a1), ptr(zg), ptr(coef), ptr(dz1), ptr(dzg),
-                                    ptr(dhg), ptr(partial), rows, B, F_, dp, drng, dco, dgc, st), "blm_mix2_gp_bwd")
+        dhg = _new(dev, M, F_) if coef.requires_grad else None
+        calls().blm_mix2_gp_bwd(ptr(ds), ptr(h1), ptr(hg), ptr(probs), ptr(a1), ptr(zg), ptr(coef), ptr(dz1), ptr(dzg),
+                                ptr(dhg), ptr(partial), rows, B, F_, dp, drng, dco, dgc, st)
         dprobs = _reduce_partials(partial, 2) if ctx.needs_input_grad[6] else None
         dcoef = None
         if coef.requires_grad:
             buf, _, dcoef = _wgrad_target(coef)
             if dcoef is not None:
                 buf.zero_()
-            check(lib().blm_gp_coef_grad(ptr(dhg), ptr(zg), ptr(buf), M, F_, st), "blm_gp_coef_grad")
+            calls().blm_gp_coef_grad(ptr(dhg), ptr(zg), ptr(buf), M, F_, st)
             del dhg
         if w2.requires_grad:
             gemm(L.GEMM_TN, dy, s, _grad_buf(w2), N2, F_, M, N2, F_, F_, accumulate=True,
@@ -3277,27 +3249,25 @@ class _LSTMSearchLayer(torch.autograd.Function):
         dev = x.device
         st = stream()
         need_bwd = any(ctx.needs_input_grad)
-        xw = torch.empty(T, B, 8 * H, device=dev, dtype=torch.float32)
+        xw = _new(dev, T, B, 8 * H)
         gemm(L.GEMM_NT, x, w8_ih, xw, T * B, 8 * H, I, I, I, 8 * H, epilogue=L.EPI_BIAS, bias=bias8)
-        hs = torch.empty(T + 1, B, H, device=dev, dtype=torch.float32)
-        cs = torch.empty(T + 1, B, H, device=dev, dtype=torch.float32)
+        hs = _new(dev, T + 1, B, H)
+        cs = _new(dev, T + 1, B, H)
         hs[0].copy_(h0)
         cs[0].copy_(c0)
-        acts = torch.empty(T, B, 8 * H, device=dev, dtype=torch.float32) if need_bwd else None
+        acts = _new(dev, T, B, 8 * H) if need_bwd else None
         if H % 32 == 0:  # one launch per step: recurrent product over the stacked weight + the search cell
             xw_p, hs_p, cs_p, w_p, pr_p = _P(xw), _P(hs), _P(cs), ptr(w8_hh), ptr(probs)
             ac_p = _P(acts) if need_bwd else None
-            step_fwd = lib().blm_lstm_search_step_fwd
+            step_fwd = calls().blm_lstm_search_step_fwd
             for t in range(T):
-                check(step_fwd(xw_p[t], w_p, hs_p[t], cs_p[t], pr_p, hs_p[t + 1], cs_p[t + 1], ac_p[t] if need_bwd else None, B, H,
-                               st), "blm_lstm_search_step_fwd")
+                step_fwd(xw_p[t], w_p, hs_p[t], cs_p[t], pr_p, hs_p[t + 1], cs_p[t + 1], ac_p[t] if need_bwd else None, B, H, st)
         else:
-            hw = torch.empty(B, 8 * H, device=dev, dtype=torch.float32)
+            hw = _new(dev, B, 8 * H)
             for t in range(T):
                 gemm(L.GEMM_NT, hs[t], w8_hh, hw, B, 8 * H, H, H, H, 8 * H)
-                check(lib().blm_lstm_search_cell_fwd(ptr(xw[t]), ptr(hw), ptr(cs[t]), ptr(probs), ptr(hs[t + 1]),
-                                                     ptr(cs[t + 1]), ptr(acts[t]) if need_bwd else None, B, H, st),
-                      "blm_lstm_search_cell_fwd")
+                calls().blm_lstm_search_cell_fwd(ptr(xw[t]), ptr(hw), ptr(cs[t]), ptr(probs), ptr(hs[t + 1]),
+                                                 ptr(cs[t + 1]), ptr(acts[t]) if need_bwd else None, B, H, st)
         ctx.save_for_backward(x, hs, cs, acts, w8_ih, w8_hh, probs)
         ctx.dims = (T, B, I, H)
         return hs[1:], hs[T], cs[T]
@@ -3309,11 +3279,11 @@ class _LSTMSearchLayer(torch.autograd.Function):
         dev = x.device
         st = stream()
         dy = _f32(dy.contiguous(), "dy")
-        npart = int(lib().blm_lstm_search_cell_partials(B, H))
-        part = torch.empty(T, npart, device=dev, dtype=torch.float32)
-        dz = torch.empty(T, B, 8 * H, device=dev, dtype=torch.float32)
-        dcb = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
-        dhr = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
+        npart = int(calls().blm_lstm_search_cell_partials(B, H))
+        part = _new(dev, T, npart)
+        dz = _new(dev, T, B, 8 * H)
+        dcb = [_new(dev, B, H) for _ in range(2)]
+        dhr = [_new(dev, B, H) for _ in range(2)]
         dh_rec = _f32(dhT.contiguous(), "dhT") if dhT is not None else None
         dc = _f32(dcT.contiguous(), "dcT") if dcT is not None else None
         # H % 16 == 0: one launch per step -- the skinny recurrent dgrad dh = dz8 . W8 on the LSTM step kernel (fixed
@@ -3322,32 +3292,30 @@ class _LSTMSearchLayer(torch.autograd.Function):
         fused = H % 16 == 0
         part2 = None
         if fused:
-            w_t = torch.empty(H, 8 * H, device=dev, dtype=torch.float32)
-            check(lib().blm_transpose(ptr(w8_hh), ptr(w_t), 8 * H, H, st), "blm_transpose")
-            part = torch.empty(1, npart, device=dev, dtype=torch.float32)
-            check(lib().blm_lstm_search_cell_bwd(ptr(dy[T - 1]), ptr(dh_rec), ptr(dc), ptr(cs[T - 1]), ptr(cs[T]),
-                                                 ptr(acts[T - 1]), ptr(probs), ptr(dz[T - 1]), ptr(dcb[0]), ptr(part[0]), B, H, st),
-                  "blm_lstm_search_cell_bwd")
-            nstep = int(lib().blm_lstm_search_step_partials(B, H))
-            part2 = torch.empty(max(T - 1, 1), nstep, device=dev, dtype=torch.float32)
+            w_t = _new(dev, H, 8 * H)
+            calls().blm_transpose(ptr(w8_hh), ptr(w_t), 8 * H, H, st)
+            part = _new(dev, 1, npart)
+            calls().blm_lstm_search_cell_bwd(ptr(dy[T - 1]), ptr(dh_rec), ptr(dc), ptr(cs[T - 1]), ptr(cs[T]),
+                                             ptr(acts[T - 1]), ptr(probs), ptr(dz[T - 1]), ptr(dcb[0]), ptr(part[0]), B, H, st)
+            nstep = int(calls().blm_lstm_search_step_partials(B, H))
+            part2 = _new(dev, max(T - 1, 1), nstep)
             k = 0
             dz_p, dy_p, cs_p, ac_p, p2_p = _P(dz), _P(dy), _P(cs), _P(acts), _P(part2)
             dcb_p, wt_p, pr_p = (ptr(dcb[0]), ptr(dcb[1])), ptr(w_t), ptr(probs)
-            step_bwd = lib().blm_lstm_search_step_bwd
+            step_bwd = calls().blm_lstm_search_step_bwd
             for t in range(T - 1, 0, -1):
-                check(step_bwd(dz_p[t], wt_p, dy_p[t - 1], dcb_p[k], cs_p[t - 1], cs_p[t], ac_p[t - 1], pr_p, dz_p[t - 1],
-                               dcb_p[k ^ 1], p2_p[t - 1], B, H, st), "blm_lstm_search_step_bwd")
+                step_bwd(dz_p[t], wt_p, dy_p[t - 1], dcb_p[k], cs_p[t - 1], cs_p[t], ac_p[t - 1], pr_p, dz_p[t - 1],
+                         dcb_p[k ^ 1], p2_p[t - 1], B, H, st)
                 k ^= 1
-            check(lib().blm_lstm_step_dh(ptr(dz[0]), ptr(w_t), ptr(dhr[0]), B, H, 8 * H, st), "blm_lstm_step_dh")
+            calls().blm_lstm_step_dh(ptr(dz[0]), ptr(w_t), ptr(dhr[0]), B, H, 8 * H, st)
             dh_rec, dc = dhr[0], dcb[k]
             if T == 1:
                 part2 = None
         else:
             for t in range(T - 1, -1, -1):
                 k = t & 1
-                check(lib().blm_lstm_search_cell_bwd(ptr(dy[t]), ptr(dh_rec), ptr(dc), ptr(cs[t]), ptr(cs[t + 1]), ptr(acts[t]),
-                                                     ptr(probs), ptr(dz[t]), ptr(dcb[k]), ptr(part[t]), B, H, st),
-                      "blm_lstm_search_cell_bwd")
+                calls().blm_lstm_search_cell_bwd(ptr(dy[t]), ptr(dh_rec), ptr(dc), ptr(cs[t]), ptr(cs[t + 1]), ptr(acts[t]),
+                                                 ptr(probs), ptr(dz[t]), ptr(dcb[k]), ptr(part[t]), B, H, st)
                 dc = dcb[k]
                 gemm(L.GEMM_NN, dz[t], w8_hh, dhr[k], B, H, 8 * H, 8 * H, H, H)
                 dh_rec = dhr[k]
@@ -3364,12 +3332,12 @@ class _LSTMSearchLayer(torch.autograd.Function):
             gemm(L.GEMM_TN, dz, hs, dw_hh, 8 * H, H, M, 8 * H, H, H)
         if ctx.needs_input_grad[3]:
             dw_ih = torch.empty_like(w8_ih)
-            db = torch.empty(8 * H, device=dev, dtype=torch.float32) if ctx.needs_input_grad[5] else None
+            db = _new(dev, 8 * H) if ctx.needs_input_grad[5] else None
             if db is not None:
                 db.zero_()
             gemm(L.GEMM_TN, dz, x, dw_ih, 8 * H, I, M, 8 * H, I, I, colsum_a=db)
         elif ctx.needs_input_grad[5]:
-            db = torch.empty(8 * H, device=dev, dtype=torch.float32)
+            db = _new(dev, 8 * H)
             _colsum_into(dz, M, 8 * H, db, accumulate=False)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
