@@ -65,6 +65,12 @@ class Gpnn2Seq(C.Structure):
                                              "sact", "gout", "dy", "dh", "dcs2", "dgates", "da", "ds", "df")])
 
 
+class BeamPoolArgs(C.Structure):
+    """blm_beam_pool (include/bayeslm.h)."""
+    _fields_ = ([("abi_version", C.c_uint32), ("P", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("norm", "raw", "len", "step", "parent", "finished", "count", "inserted")])
+
+
 class GemmPlan(C.Structure):
     _fields_ = [("tile", C.c_int32), ("splits", C.c_int32), ("source", C.c_int32), ("model_us", C.c_float)]
 
@@ -127,6 +133,8 @@ SIGNATURES = {
     "blm_sample_rows": (_i, [_vp, _i64, _i, _i, _f, _rngp, _vp, _vp]),
     "blm_topk_rows": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "blm_beam_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "blm_beam_select_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _i, C.POINTER(BeamPoolArgs),
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_sample_rows_filtered": (_i, [_vp, _i64, _i, _i, _f, _i, _f, _rngp, _vp, _vp]),
     "blm_ce_fwd_bwd": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
     "blm_ce_interp_fwd": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _i, _i, _vp]),

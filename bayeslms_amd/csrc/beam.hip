@@ -1,8 +1,9 @@
 // Search on the incremental path (bayeslms_amd/incremental.py beam_search, generate.py): the k best entries of every row
-// (blm_topk_rows), the B best continuations of every group of B beams (blm_beam_select) and Gumbel-max sampling restricted to a
-// top-k / nucleus prefix of the row's order (blm_sample_rows_filtered).
+// (blm_topk_rows), the B best continuations of every group of B beams (blm_beam_select), the same step with a pool of finished
+// hypotheses beside the beam (blm_beam_select_pool) and Gumbel-max sampling restricted to a top-k / nucleus prefix of the row's
+// order (blm_sample_rows_filtered).
 //
-// One device routine serves all three: a most-significant-digit radix select over 64-bit composites
+// One device routine serves all four: a most-significant-digit radix select over 64-bit composites
 //     c(i) = order_key(value i) << nb  |  (2^nb - 1 - i)              nb = bits of the largest index
 // order_key maps a float to 32 bits so that a larger key is a better entry (value descending, -0 == +0, every NaN below -inf),
 // and the inverted index below it makes "lowest index first among equal values" part of the same integer order.  Composites
@@ -233,6 +234,154 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(const float* cand
   }
 }
 
+struct PoolSmem {
+  uint32_t okey[kTopkMax];  // order keys of the norms the pool holds before the step, in pool order
+  uint32_t nkey[kTopkMax];  // of the entries offered at this step, in insertion order (at most B eos + B flushed <= kTopkMax)
+  int n_cont, n_eos;        // candidates of the walk that are not eos / eos of rank < B
+  float best;               // score of new beam 0
+  uint32_t last_key;        // key of the full pool's last norm after the step
+};
+
+// blm_beam_select_pool (include/bayeslm.h).  The walk needs the first 2 B ranks only: one select + sort of them, a scan that
+// numbers the eos and the other candidates, and a merge of the offered entries into the pool by counting, for every entry, the
+// entries that precede it -- the pool is sorted and the offered ones are numbered, so ranks are distinct and every write has
+// its own slot.  All of the old pool is in registers before the first write to it.
+__global__ __launch_bounds__(kThreads) void beam_select_pool_kernel(const float* cand_vals, const int64_t* cand_ids, const float* score,
+                                                                    const uint8_t* live, int B, int k, int64_t eos, int step, int len,
+                                                                    int min_len, float inv_norm, float inv_norm_max, int flush,
+                                                                    blm_beam_pool pool, float* score_out, uint8_t* live_out,
+                                                                    int64_t* parent, int64_t* token, uint8_t* done_out) {
+  __shared__ SelSmem sm;
+  __shared__ PoolSmem ps;
+  const int t = threadIdx.x, g = blockIdx.x, g0 = g * B, n = B * k, P = pool.P;
+  const int want = min(2 * B, n);
+  const float* cv = cand_vals + (size_t)g0 * k;
+  const int64_t* ci = cand_ids + (size_t)g0 * k;
+  auto cand = [=](int i) { return score[g0 + i / k] + cv[i]; };
+  auto key = [=](int i) {
+    if (!live[g0 + i / k]) return 0u;
+    const float s = cand(i);
+    if (!(s > -INFINITY)) return 0u;  // NaN or -inf
+    if (len < min_len && ci[i] == eos) return 0u;
+    return order_key(s);
+  };
+  u64 taken;
+  const u64 cstar = radix_select<false>(key, NoMass(), n, (u64)want, sm, &taken);
+  collect_sorted(key, n, cstar, want, sm);
+  const int nb = index_bits(n);
+  const uint32_t imask = (1u << nb) - 1u;
+  // thread t holds rank t of the walk
+  bool is_eos = false, cont = false;
+  int b = 0;
+  float s = 0.f;
+  int64_t tok = eos;
+  if (t < want) {
+    const u64 c = sm.surv[t];
+    const int i = (int)(imask - (uint32_t)(c & imask));
+    if ((c >> nb) != 0 && i < n) {
+      b = i / k;
+      s = cand(i);
+      tok = ci[i];
+      is_eos = tok == eos;
+      cont = !is_eos;
+    }
+  }
+  const bool pooled = is_eos && t < B;
+  const u64 inc = block_scan((u64)(cont ? 1 : 0) | ((u64)(pooled ? 1 : 0) << 32), sm.wsum);
+  const int slot = (int)(uint32_t)inc - (cont ? 1 : 0);  // candidates that are not eos before this one
+  if (t == kThreads - 1) {
+    ps.n_cont = (int)(uint32_t)inc;
+    ps.n_eos = (int)(inc >> 32);
+    ps.best = -INFINITY;
+    ps.last_key = 0;
+  }
+  __syncthreads();
+  const int n_live = min(ps.n_cont, B), n_eos = ps.n_eos;
+  const bool beam = cont && slot < B;
+  const int n_new = n_eos + (flush ? n_live : 0);
+  // the entry this thread offers (at most one), numbered in insertion order
+  const bool offers = pooled || (beam && flush);
+  const int q = pooled ? (int)(inc >> 32) - 1 : n_eos + slot;
+  const float norm = __fmul_rn(s, inv_norm);
+  if (offers) ps.nkey[q] = order_key(norm);
+  if (beam && slot == 0) ps.best = s;
+  // the entry of the pool this thread moves
+  const size_t p0 = (size_t)g * P;
+  const int count = min(max(pool.count[g], 0), P);
+  float o_norm = 0.f, o_raw = 0.f;
+  int o_len = 0, o_step = 0;
+  int64_t o_parent = 0;
+  uint8_t o_fin = 0;
+  if (t < count) {
+    o_norm = pool.norm[p0 + t];
+    o_raw = pool.raw[p0 + t];
+    o_len = pool.len[p0 + t];
+    o_step = pool.step[p0 + t];
+    o_parent = pool.parent[p0 + t];
+    o_fin = pool.finished[p0 + t];
+    ps.okey[t] = order_key(o_norm);
+  }
+  __syncthreads();
+  const int n_after = min(P, count + n_new);
+  if (n_new > 0 && t < count) {
+    const uint32_t mine = ps.okey[t];
+    int r = t;
+    for (int j = 0; j < n_new; ++j) r += ps.nkey[j] > mine ? 1 : 0;
+    if (r < P && r != t) {
+      pool.norm[p0 + r] = o_norm;
+      pool.raw[p0 + r] = o_raw;
+      pool.len[p0 + r] = o_len;
+      pool.step[p0 + r] = o_step;
+      pool.parent[p0 + r] = o_parent;
+      pool.finished[p0 + r] = o_fin;
+    }
+    if (r == P - 1) ps.last_key = mine;
+  } else if (t == P - 1 && t < count) {
+    ps.last_key = ps.okey[t];
+  }
+  if (offers) {
+    const uint32_t mine = ps.nkey[q];
+    int r = 0;
+    for (int j = 0; j < count; ++j) r += ps.okey[j] >= mine ? 1 : 0;
+    for (int j = 0; j < n_new; ++j) r += (ps.nkey[j] > mine || (ps.nkey[j] == mine && j < q)) ? 1 : 0;
+    if (r < P) {
+      pool.norm[p0 + r] = norm;
+      pool.raw[p0 + r] = s;
+      pool.len[p0 + r] = len;
+      pool.step[p0 + r] = step;
+      pool.parent[p0 + r] = pooled ? g0 + b : g0 + slot;
+      pool.finished[p0 + r] = pooled ? 1 : 0;
+    }
+    if (r == P - 1) ps.last_key = mine;
+  }
+  __syncthreads();
+  const bool done = n_live == 0 || flush || (n_after == P && order_key(__fmul_rn(ps.best, inv_norm_max)) < ps.last_key);
+  if (beam) {
+    score_out[g0 + slot] = done ? -INFINITY : s;
+    live_out[g0 + slot] = done ? 0 : 1;
+    parent[g0 + slot] = g0 + b;
+    token[g0 + slot] = tok;
+  }
+  if (t >= n_live && t < B) {
+    score_out[g0 + t] = -INFINITY;
+    live_out[g0 + t] = 0;
+    parent[g0 + t] = g0 + t;
+    token[g0 + t] = eos;
+  }
+  if (t == 0) {
+    pool.count[g] = n_after;
+    pool.inserted[g] += n_new;
+    done_out[g] = done ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void all_done_kernel(const uint8_t* done, int G, uint8_t* all_done) {
+  int ok = 1;
+  for (int i = threadIdx.x; i < G; i += kThreads) ok &= done[i] != 0;
+  ok = __syncthreads_and(ok);
+  if (threadIdx.x == 0) *all_done = ok ? 1 : 0;
+}
+
 // Lowest index wins a tie; a NaN score never wins (blm_sample_rows' rule).
 __device__ __forceinline__ void best_of(float& v, int& i, float v2, int i2) {
   if (v2 > v || (v2 == v && i2 < i) || (v != v && v2 == v2)) {
@@ -351,6 +500,45 @@ extern "C" int blm_beam_select(const float* cand_vals, const int64_t* cand_ids, 
   if (G == 0) return BLM_OK;
   hipLaunchKernelGGL(beam_select_kernel, dim3(G), dim3(kThreads), 0, static_cast<hipStream_t>(stream), cand_vals, cand_ids, score,
                      finished, B, k, eos, score_out, finished_out, parent, token);
+  BLM_HIP(hipGetLastError());
+  return BLM_OK;
+}
+
+extern "C" int blm_beam_select_pool(const float* cand_vals, const int64_t* cand_ids, const float* score, const uint8_t* live, int G,
+                                    int B, int k, int V, int64_t eos, int step, int len, int min_len, float inv_norm,
+                                    float inv_norm_max, int flush, const blm_beam_pool* pool, float* score_out, uint8_t* live_out,
+                                    int64_t* parent, int64_t* token, uint8_t* done_out, uint8_t* all_done, void* stream) {
+  if (!cand_vals || !cand_ids || !score || !live || !pool || !score_out || !live_out || !parent || !token || !done_out || !all_done)
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: null operand");
+  if (pool->abi_version != BLM_ABI_VERSION)
+    return blm_fail(BLM_ERR_ABI, "blm_beam_select_pool: blm_beam_pool.abi_version %u, library %u", pool->abi_version, BLM_ABI_VERSION);
+  if (!pool->norm || !pool->raw || !pool->len || !pool->step || !pool->parent || !pool->finished || !pool->count || !pool->inserted)
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: null pool array");
+  if (G < 0 || B < 1 || k < 1 || V < 1) return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: bad shape");
+  if (B > BLM_TOPK_MAX / 2)
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: B = %d beams, 2 B exceeds BLM_TOPK_MAX = %d", B, BLM_TOPK_MAX);
+  if (k < (2 * B < V ? 2 * B : V))
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: k = %d candidates per beam, min(2 B, V) = %d needed", k, 2 * B < V ? 2 * B : V);
+  if (pool->P < 1 || pool->P > BLM_TOPK_MAX)
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: P = %d pool slots outside [1, BLM_TOPK_MAX = %d]", pool->P, BLM_TOPK_MAX);
+  if (!blm::extents_ok({G, B, k}) || !blm::extents_ok({G, pool->P}) || (long)B * k > blm::kMaxExtent)
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: extents too large");
+  if (step < 0 || len < 1 || min_len < 0) return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: step >= 0, len >= 1 and min_len >= 0 expected");
+  if (!(inv_norm_max >= 0.f) || !(inv_norm >= inv_norm_max) || inv_norm > 3e38f)
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: 0 <= inv_norm_max <= inv_norm < inf expected");
+  if (score == score_out || live == live_out)
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: the state before and after the step must be two buffers");
+  auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+  if (!al(cand_vals, 4) || !al(score, 4) || !al(score_out, 4) || !al(pool->norm, 4) || !al(pool->raw, 4) || !al(pool->len, 4) ||
+      !al(pool->step, 4) || !al(pool->count, 4) || !al(cand_ids, 8) || !al(parent, 8) || !al(token, 8) || !al(pool->parent, 8) ||
+      !al(pool->inserted, 8))
+    return blm_fail(BLM_ERR_INVALID, "blm_beam_select_pool: misaligned operand (4 bytes for float / int32, 8 for int64)");
+  if (G == 0) return BLM_OK;
+  hipLaunchKernelGGL(beam_select_pool_kernel, dim3(G), dim3(kThreads), 0, static_cast<hipStream_t>(stream), cand_vals, cand_ids, score,
+                     live, B, k, eos, step, len, min_len, inv_norm, inv_norm_max, flush, *pool, score_out, live_out, parent, token,
+                     done_out);
+  BLM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(all_done_kernel, dim3(1), dim3(kThreads), 0, static_cast<hipStream_t>(stream), done_out, G, all_done);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

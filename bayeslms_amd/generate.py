@@ -19,7 +19,14 @@ words whose probability reaches P (blm_sample_rows_filtered; the same noise as t
 instead of sampling (IncrementalLM.beam_search; a hypothesis ends at the sentence boundary ``<s>``): the ``--nbest`` N (default 1)
 best continuations of the prompt are written best first, one per line, ranked by score / length ** ``--length-penalty``, and
 ``--write-scores PATH`` writes one "rank score length" line per hypothesis.  With ``--mc-samples`` the search runs under the
-model average."""
+model average.
+
+``--finished-pool P`` (with ``--beam``; default 0: the search above, unchanged) searches with a pool of P finished hypotheses
+beside the beam (IncrementalLM.beam_search_pool): a hypothesis that ends leaves the beam, which is refilled to B live ones at
+every word, the pool is ranked by score / length ** ``--length-penalty`` (>= 0) INSIDE the loop, and the search stops once
+nothing alive can enter it.  ``--nbest`` may then go up to P (fewer lines are written when fewer hypotheses were found),
+``--min-words M`` refuses a hypothesis of fewer than M words (the closing ``<s>`` counted), and ``--write-scores`` writes
+"rank score normalised-score length" with a trailing "unfinished" on a hypothesis that was still alive after ``--words`` words."""
 import argparse
 import sys
 
@@ -53,12 +60,17 @@ def build_parser():
                    help='sample among the smallest set of most probable words whose probability reaches P, in (0, 1] (1: all)')
     p.add_argument('--beam', type=int, default=0, metavar='B',
                    help='B > 0: beam search with B beams instead of sampling; at most --words words per hypothesis, ended by <s>')
-    p.add_argument('--nbest', type=int, default=1, metavar='N', help='with --beam: write the N best hypotheses (N <= B)')
+    p.add_argument('--nbest', type=int, default=1, metavar='N', help='with --beam: write the N best hypotheses (N <= B; with --finished-pool P: N <= P)')
     p.add_argument('--length-penalty', type=float, default=0.0, metavar='A',
                    help='with --beam: the final ranking is by score / length ** A (the search itself is by raw score)')
     p.add_argument('--write-scores', type=str, default='', metavar='PATH',
                    help='with --beam: one line "rank score length" per written hypothesis (rank from 1, score %%.6f: its '
                         'cumulative log-probability including the closing <s>, length in words including it)')
+    p.add_argument('--finished-pool', type=int, default=0, metavar='P',
+                   help='with --beam, P > 0: keep the P best finished hypotheses in a pool beside the beam, ranked by score / length '
+                        '** A inside the search; --nbest may go up to P (0: finished hypotheses keep their beam slot)')
+    p.add_argument('--min-words', type=int, default=0, metavar='M',
+                   help='with --finished-pool: no hypothesis of fewer than M words, the closing <s> counted')
     p.add_argument('--seed', type=int, default=1111, help='key of the sampling noise: the same seed gives the same text')
     p.add_argument('--streams', type=int, default=1, help='independent samples, generated in one batch')
     p.add_argument('--prompt', type=str, default='', help='words every stream starts from (after <s>)')
@@ -91,6 +103,14 @@ def beam_generate(model, vocab, words, beam, nbest=1, prompt="", length_penalty=
     ctx = _context(vocab, prompt)
     lm = IncrementalLM(model, max_streams=beam, max_len=len(ctx) + words, mc_samples=mc_samples, seed=mc_seed)
     return lm.beam_search([ctx], beam, words, vocab['<s>'], length_penalty)[0][:nbest]
+
+
+def pool_generate(model, vocab, words, beam, pool, nbest=1, prompt="", length_penalty=0.0, min_words=0, mc_samples=0, mc_seed=1111):
+    """-> the (up to) ``nbest`` best PooledHypothesis of a ``beam``-wide search with a pool of ``pool`` finished hypotheses, for
+    at most ``words`` words after <s> + prompt, best first by normalised score."""
+    ctx = _context(vocab, prompt)
+    lm = IncrementalLM(model, max_streams=beam, max_len=len(ctx) + words, mc_samples=mc_samples, seed=mc_seed)
+    return lm.beam_search_pool([ctx], beam, words, vocab['<s>'], pool, length_penalty, min_words)[0][:nbest]
 
 
 def generate(model, vocab, words, streams=1, temperature=1.0, seed=1111, prompt="", mc_samples=0, mc_seed=1111, uncertainty=False,
@@ -136,10 +156,21 @@ def main(argv=None):
             raise SystemExit("--beam writes the hypotheses of ONE search: --streams %d cannot be given with it" % args.streams)
         if args.write_uncertainty:
             raise SystemExit("--write-uncertainty belongs to sampling; --beam has --write-scores")
-        if args.beam < 0 or not 1 <= args.nbest <= args.beam or args.words < 1:
+        if args.finished_pool:
+            if args.beam < 1 or args.words < 1 or not 1 <= args.nbest <= args.finished_pool:
+                raise SystemExit("--beam >= 1, 1 <= --nbest <= --finished-pool and --words >= 1 expected")
+            if not 1 <= args.finished_pool <= 256 or args.beam > 128:
+                raise SystemExit("--finished-pool in [1, 256] and --beam <= 128 with it expected")
+            if args.min_words < 0 or not 0.0 <= args.length_penalty < float("inf"):
+                raise SystemExit("--min-words >= 0 and a finite --length-penalty >= 0 expected with --finished-pool")
+        elif args.min_words:
+            raise SystemExit("--min-words needs --finished-pool")
+        elif args.beam < 0 or not 1 <= args.nbest <= args.beam or args.words < 1:
             raise SystemExit("--beam >= 1, 1 <= --nbest <= --beam and --words >= 1 expected")
     elif args.nbest != 1 or args.length_penalty != 0.0 or args.write_scores:
         raise SystemExit("--nbest, --length-penalty and --write-scores need --beam")
+    elif args.finished_pool or args.min_words:
+        raise SystemExit("--finished-pool and --min-words need --beam")
     args.temperature = 1.0 if args.temperature is None else args.temperature
     args.top_k = 0 if args.top_k is None else args.top_k
     args.top_p = 1.0 if args.top_p is None else args.top_p
@@ -161,7 +192,15 @@ def main(argv=None):
     S.load_partial(model, args.model_path)
     model = model.to(torch.device("cuda", torch.cuda.current_device())).eval()
     inv = {i: w for w, i in vocab.items()}
-    if args.beam:
+    if args.beam and args.finished_pool:
+        hyps = pool_generate(model, vocab, args.words, args.beam, args.finished_pool, args.nbest, args.prompt, args.length_penalty,
+                             args.min_words, args.mc_samples, args.mc_seed)
+        ids = [h.tokens for h in hyps]
+        if args.write_scores:
+            with open(args.write_scores, 'w', encoding='utf-8') as f:
+                f.write("".join("%d %.6f %.6f %d%s\n" % (r + 1, h.score, h.norm_score, h.length, "" if h.finished else " unfinished")
+                                for r, h in enumerate(hyps)))
+    elif args.beam:
         hyps = beam_generate(model, vocab, args.words, args.beam, args.nbest, args.prompt, args.length_penalty, args.mc_samples,
                              args.mc_seed)
         ids = [h.tokens for h in hyps]

@@ -13,6 +13,8 @@ the histories through the model again.
     vals, ids = lm.step_topk(st, ids, k=8)    # the 8 best next words of each stream, best first (blm_topk_rows)
     st = lm.reorder_device(st, idx)           # the same gather with a DEVICE index and no copy to the host (equal lengths promised)
     nbest = lm.beam_search([[bos, w1, w2]], beam=8, max_words=30, eos=bos)   # -> [[BeamHypothesis(tokens, score, length), ...]]
+    nbest = lm.beam_search_pool([[bos, w1]], beam=8, max_words=30, eos=bos, pool=20, length_penalty=0.8)   # finished hypotheses
+                                              # leave the beam for a pool ranked by score / length ** a -> [[PooledHypothesis, ...]]
 
     lm = IncrementalLM(model, max_streams=64, max_len=1024, mc_samples=8, seed=1111)   # the model average over 8 weight samples
     lp = lm.step(st, ids)                                   # log pbar, the distribution the n-best scorer's --mc-samples scores with
@@ -104,6 +106,15 @@ class BeamHypothesis(NamedTuple):
     tokens: list   # generated word ids (prompt excluded), cut after the first eos
     score: float   # raw fp32 cumulative log-probability of `tokens`, the eos included
     length: int    # len(tokens)
+
+
+class PooledHypothesis(NamedTuple):
+    """One result of IncrementalLM.beam_search_pool."""
+    tokens: list       # generated word ids (prompt excluded), the closing eos included when finished
+    score: float       # raw fp32 cumulative log-probability of `tokens`
+    norm_score: float  # fp32 score * float32(1 / length ** length_penalty): what the pool is ranked by
+    length: int        # len(tokens)
+    finished: bool     # ended by eos; False: still alive after max_words words
 
 
 class _SampleCache:
@@ -357,6 +368,86 @@ class IncrementalLM:
                 st = self.reorder_device(st, parent)
                 lp = self.step(st, token)
             return torch.stack(parents).cpu().numpy(), torch.stack(tokens).cpu().numpy(), score.cpu().numpy()
+
+    def beam_search_pool(self, prompts, beam, max_words, eos, pool=None, length_penalty=0.0, min_words=0, sync_every=16, _stop=True):
+        """Beam search with a pool of finished hypotheses over G prompts at once -> list (per prompt) of up to ``pool`` (default
+        ``beam``, at most BLM_TOPK_MAX) PooledHypothesis, best first by norm_score, then by the order in which they were pooled.
+
+        A hypothesis that produces ``eos`` among the ``beam`` best candidates of its word leaves the beam for the pool, ranked
+        there by norm_score = score / length ** ``length_penalty`` (a >= 0; one fp32 multiply by float32(1 / length ** a)), and
+        the beam is refilled to ``beam`` live hypotheses at every word; an eos that would end a hypothesis of fewer than
+        ``min_words`` words (the eos counted) is not considered.  The hypotheses still alive after ``max_words`` words are
+        pooled unfinished.  A prompt's search stops once its pool is full and nothing alive can still enter it (include/bayeslm.h,
+        blm_beam_select_pool, has the exact rules).  Per word: step -> blm_topk_rows(k = min(2 * beam, V)) ->
+        blm_beam_select_pool -> reorder_device; the pool, the parents and the tokens of every step stay on the device and are read
+        once at the end, where the hypotheses are traced back.  The host reads one "every prompt is done" flag every
+        ``sync_every`` words (0: never); results do not depend on it.  ``prompts``, ``max_words`` and the capacity checks are
+        beam_search's, all made before any launch.  With mc_samples the search runs under log pbar, the model average."""
+        G, B, W, eos, a, M_ = len(prompts), int(beam), int(max_words), int(eos), float(length_penalty), int(min_words)
+        P = B if pool is None else int(pool)
+        if G < 1 or any(len(p) < 1 for p in prompts):
+            raise BayesLMError("IncrementalLM.beam_search_pool: at least one prompt, and at least one word (the sentence start) in each")
+        if not 1 <= B <= L_TOPK_MAX // 2:
+            raise BayesLMError("IncrementalLM.beam_search_pool: beam = %d outside [1, BLM_TOPK_MAX / 2 = %d]" % (B, L_TOPK_MAX // 2))
+        if not 1 <= P <= L_TOPK_MAX:
+            raise BayesLMError("IncrementalLM.beam_search_pool: pool = %d outside [1, BLM_TOPK_MAX = %d]" % (P, L_TOPK_MAX))
+        if W < 1 or int(sync_every) < 0 or M_ < 0:
+            raise BayesLMError("IncrementalLM.beam_search_pool: max_words >= 1, min_words >= 0 and sync_every >= 0 expected")
+        if not a >= 0.0 or math.isinf(a):
+            raise BayesLMError("IncrementalLM.beam_search_pool: length_penalty %r: the stopping rule needs a finite a >= 0" % length_penalty)
+        if G * B > self.max_streams:
+            raise BayesLMError("IncrementalLM.beam_search_pool: %d prompts x %d beams, max_streams is %d" % (G, B, self.max_streams))
+        lens = [len(p) for p in prompts]
+        if max(lens) + W > self.max_len:
+            raise BayesLMError("IncrementalLM.beam_search_pool: prompt of %d words + %d new words, max_len is %d"
+                               % (max(lens), W, self.max_len))
+        if not 0 <= eos < self.vocab:
+            raise BayesLMError("IncrementalLM.beam_search_pool: eos %d outside the vocabulary" % eos)
+        n, V = G * B, self.vocab
+        k = min(2 * B, V)
+        ids = np.zeros((max(lens), G), dtype=np.int64)
+        for g, p in enumerate(prompts):
+            ids[:lens[g], g] = p
+        # a bound of 0 is never below a norm (log-probabilities are <= 0): nothing stops before the flush
+        inv_max = ops.beam_inv_norm(W, a) if _stop else 0.0
+        with torch.no_grad():
+            st = self.start(G)
+            lp = self.step(st, _upload(ids, self.device, torch.int64), n_new=lens)
+            fork = np.repeat(np.arange(G, dtype=np.int64), B)
+            st = self.reorder(st, fork)
+            lp = lp.index_select(0, _upload(fork, self.device, torch.int64))
+            l0 = np.zeros(n, dtype=np.uint8)
+            l0[::B] = 1  # one live beam per group, or the first step picks `beam` copies of one word
+            live = _upload(l0, self.device, torch.uint8)
+            score = torch.zeros(n, dtype=torch.float32, device=self.device)
+            fin = ops.BeamPool(G, P, self.device)
+            parents, tokens = [], []
+            for w in range(W):
+                vals, cand = ops.topk_rows(lp, k)
+                score, live, parent, token, _, all_done = ops.beam_select_pool(
+                    vals, cand, score, live, B, V, eos, w, w + 1, M_, ops.beam_inv_norm(w + 1, a), inv_max, w + 1 == W, fin)
+                parents.append(parent)
+                tokens.append(token)
+                if w + 1 == W:
+                    break
+                if sync_every and (w + 1) % int(sync_every) == 0 and bool(all_done.item()):  # the loop's only host read
+                    break
+                st = self.reorder_device(st, parent)
+                lp = self.step(st, token)
+            PA, TK, h = torch.stack(parents).cpu().numpy(), torch.stack(tokens).cpu().numpy(), fin.host()
+        out = []
+        for g in range(G):
+            hyps = []
+            for e in range(int(h["count"][g])):
+                done, cur, w = bool(h["finished"][g, e]), int(h["parent"][g, e]), int(h["step"][g, e])
+                toks = [eos] if done else []
+                for ww in range(w - 1 if done else w, -1, -1):
+                    toks.append(int(TK[ww, cur]))
+                    cur = int(PA[ww, cur])
+                toks.reverse()
+                hyps.append(PooledHypothesis(toks, float(h["raw"][g, e]), float(h["norm"][g, e]), int(h["len"][g, e]), done))
+            out.append(hyps)
+        return out
 
     # ---------------------------------------------------------------- stepping
     def step(self, st, ids, n_new=None, all_positions=False, targets=None, return_uncertainty=False):

@@ -2026,6 +2026,76 @@ def beam_select(cand_vals, cand_ids, score, finished, beams, eos):
     return score_out, fin_out, parent, token
 
 
+class BeamPool:
+    """The finished-hypothesis pool of beam_select_pool (blm_beam_pool, include/bayeslm.h): ``slots`` entries for each of
+    ``groups`` searches, every array a view of ONE device allocation.  Slots [0, count[g]) of group g are its entries best first
+    (norm descending, then insertion order); the rest is never read.  A new pool is empty."""
+    FIELDS = (("parent", torch.int64, True), ("inserted", torch.int64, False), ("norm", torch.float32, True),
+              ("raw", torch.float32, True), ("len", torch.int32, True), ("step", torch.int32, True), ("count", torch.int32, False),
+              ("finished", torch.uint8, True))  # widest elements first: every view is aligned to its element
+
+    def __init__(self, groups, slots, device):
+        self.groups, self.slots = int(groups), int(slots)
+        if self.groups < 1 or not 1 <= self.slots <= L.TOPK_MAX:
+            raise BayesLMError("BeamPool: groups >= 1 and 1 <= slots <= BLM_TOPK_MAX = %d expected, got %d and %d"
+                               % (L.TOPK_MAX, self.groups, self.slots))
+        sizes = [(self.groups * (self.slots if per_slot else 1)) * torch.empty(0, dtype=dt).element_size()
+                 for _, dt, per_slot in self.FIELDS]
+        self.buf = torch.zeros(sum(sizes), dtype=torch.uint8, device=device)
+        at = 0
+        for (name, dt, per_slot), nbytes in zip(self.FIELDS, sizes):
+            v = self.buf[at:at + nbytes].view(dt)
+            setattr(self, name, v.view(self.groups, self.slots) if per_slot else v)
+            at += nbytes
+        self.args = L.BeamPoolArgs(L.ABI_VERSION, self.slots, *(ptr(getattr(self, n)) for n in
+                                                              ("norm", "raw", "len", "step", "parent", "finished", "count", "inserted")))
+
+    def host(self):
+        """-> dict of host arrays, one copy of the allocation (synchronises)"""
+        flat = self.buf.cpu().numpy()
+        out, at = {}, 0
+        for name, dt, per_slot in self.FIELDS:
+            n = self.groups * (self.slots if per_slot else 1)
+            npdt = {torch.int64: "int64", torch.float32: "float32", torch.int32: "int32", torch.uint8: "uint8"}[dt]
+            a = flat[at:at + n * torch.empty(0, dtype=dt).element_size()].view(npdt)
+            out[name] = a.reshape(self.groups, self.slots) if per_slot else a
+            at += a.nbytes
+        return out
+
+
+def beam_inv_norm(length, length_penalty):
+    """float32(1 / length ** a) as beam_select_pool takes it: formed in float64 and rounded once, returned as a Python float"""
+    import numpy as np
+    return float(np.float32(1.0 / float(length) ** float(length_penalty)))
+
+
+def beam_select_pool(cand_vals, cand_ids, score, live, beams, vocab, eos, step, length, min_len, inv_norm, inv_norm_max, flush, pool):
+    """One beam-search step with a finished-hypothesis pool over groups of ``beams`` streams (blm_beam_select_pool, which has the
+    semantics): cand_vals / cand_ids (G * beams, k >= min(2 * beams, vocab)) from topk_rows, score (G * beams,) float32 and
+    live (G * beams,) uint8 before the step; ``length`` the length of a hypothesis that ends at this step, inv_norm /
+    inv_norm_max from beam_inv_norm; ``pool`` a BeamPool of G groups, updated in place.
+    -> (score, live, parent (global stream index), token, done (G,) uint8, all_done (1,) uint8) after it"""
+    cand_vals = dev_tensor(cand_vals, "cand_vals")
+    cand_ids = dev_tensor(cand_ids, "cand_ids", torch.int64)
+    score = dev_tensor(score, "score")
+    live = dev_tensor(live, "live", torch.uint8)
+    n, B = score.numel(), int(beams)
+    if cand_vals.dim() != 2 or cand_vals.shape != cand_ids.shape or cand_vals.shape[0] != n or live.numel() != n or B < 1 or n % B:
+        raise BayesLMError("beam_select_pool: (G * beams, k) candidates and (G * beams,) score / live expected")
+    if not isinstance(pool, BeamPool) or pool.groups != n // B or pool.buf.device != score.device:
+        raise BayesLMError("beam_select_pool: a BeamPool of %d groups on the candidates' device expected" % (n // B))
+    score_out, live_out = torch.empty_like(score), torch.empty_like(live)
+    parent = torch.empty(n, device=score.device, dtype=torch.int64)
+    token = torch.empty(n, device=score.device, dtype=torch.int64)
+    done = torch.empty(n // B + 1, device=score.device, dtype=torch.uint8)  # the groups' flags, then the one for all of them
+    L.require_gfx950()
+    calls().blm_beam_select_pool(ptr(cand_vals), ptr(cand_ids), ptr(score), ptr(live), n // B, B, cand_vals.shape[1], int(vocab),
+                                 int(eos), int(step), int(length), int(min_len), float(inv_norm), float(inv_norm_max), int(bool(flush)),
+                                 C.byref(pool.args), ptr(score_out), ptr(live_out), ptr(parent), ptr(token), ptr(done),
+                                 ptr(done) + n // B, stream())
+    return score_out, live_out, parent, token, done[:n // B], done[n // B:]
+
+
 def kv_gather(src, dst, idx, n_src, outer, nhead, max_len, head_dim, len_src=None, len_dst=None):
     """Beam prune / fork of a state laid out [outer][n_cap][nhead][max_len][head_dim] (blm_kv_gather, one launch): stream j of
     ``dst`` continues stream idx[j] of ``src``; with lengths, only each panel's live prefix is copied and len_dst[j] = len_src[idx[j]]."""

@@ -533,6 +533,58 @@ int blm_topk_rows(const float* x, int64_t ldx, int R, int V, int k, float* vals,
  * Start a search from scores [0, -inf, ..., -inf] per group, or the first step picks B copies of one word. */
 int blm_beam_select(const float* cand_vals, const int64_t* cand_ids, const float* score, const uint8_t* finished, int G, int B, int k,
                     int64_t eos, float* score_out, uint8_t* finished_out, int64_t* parent, int64_t* token, void* stream);
+/* The finished-hypothesis pool of blm_beam_select_pool: P slots for each of G groups, all caller-owned device memory.  Slots
+ * [0, count[g]) of group g are its entries in POOL ORDER, best first: norm descending (NaN last, -0 == +0), then insertion
+ * order ascending.  The entry point never touches a slot at or past count[g].  Start a search from count = inserted = 0. */
+typedef struct blm_beam_pool {
+  uint32_t abi_version; /* BLM_ABI_VERSION */
+  int32_t P;            /* slots per group, 1 <= P <= BLM_TOPK_MAX */
+  float* norm;          /* (G, P) raw * inv_norm of the step that pooled the entry: what the pool is ranked by */
+  float* raw;           /* (G, P) cumulative log-probability, the closing eos included */
+  int32_t* len;         /* (G, P) length in words, the closing eos included */
+  int32_t* step;        /* (G, P) the `step` argument of the call that pooled the entry */
+  int64_t* parent;      /* (G, P) GLOBAL stream index: of the beam BEFORE that step which the eos ended (finished = 1); of
+                         * the beam AFTER that step, i.e. the slot of that call's parent / token outputs (finished = 0) */
+  uint8_t* finished;    /* (G, P) 1: ended by eos; 0: cut off alive by a flush step */
+  int32_t* count;       /* (G,) entries held, <= P */
+  int64_t* inserted;    /* (G,) entries ever offered to the pool, kept or not */
+} blm_beam_pool;
+/* One step of a beam search that moves ended hypotheses to a pool and refills the beam, for G groups of B beams (stream
+ * g * B + b), one workgroup per group.  cand_vals / cand_ids (G * B, k) as for blm_beam_select, the ids of one beam distinct
+ * (blm_topk_rows' are); score (G * B,) raw cumulative log-probability and live (G * B,) before the step.  Scalars: `len`, the
+ * length in words of a hypothesis that ends at this step (its eos counted); `step`, stored with what is pooled; `min_len`;
+ * inv_norm = float32(1 / len ** a) and inv_norm_max = float32(1 / Lmax ** a), formed by the caller in float64 and rounded once
+ * (a >= 0 the length penalty, Lmax the greatest length the search can reach): 0 <= inv_norm_max <= inv_norm < inf.
+ *   Candidates.  A live beam b offers (s = score[b] + cand_vals[b, j], token cand_ids[b, j]) for j < k -- one fp32 add each.
+ *     A dead beam offers nothing; a candidate whose s is NaN or -inf is no candidate; nor is an eos candidate when
+ *     len < min_len.
+ *   Order.  s descending, then flat index b_local * k + j ascending.
+ *   Walk, over ranks 0 .. min(2 B, B k) - 1 of that order (rank from 0, eos candidates counted):  an eos candidate of rank < B
+ *     is OFFERED to the pool as (norm = s * inv_norm -- one fp32 multiply --, raw = s, len, step, parent = g * B + b,
+ *     finished = 1); an eos candidate of rank >= B is discarded; the first B candidates that are not eos become the new beams
+ *     0, 1, ... in walk order: score_out = s, live_out = 1, parent = g * B + b, token.  A beam has at most one eos candidate,
+ *     so with k >= min(2 B, V) these ranks hold everything the exact search over all B x V continuations would reach.  With
+ *     fewer than B such candidates the remaining beams are dead: score_out = -inf, live_out = 0, parent = the beam's own
+ *     stream index, token = eos.
+ *   Flush (flush != 0, the last step).  After the walk every new live beam, in beam order, is offered as (norm = s * inv_norm,
+ *     raw = s, len, step, parent = its own NEW stream index, finished = 0).
+ *   Pool.  Entries are offered one after the other -- the eos candidates in walk order, then the flushed beams --, each
+ *     raising inserted[g] by one.  While count[g] < P an offered entry is inserted at its place in pool order.  Once the pool
+ *     is full it replaces the LAST entry only if it precedes it, i.e. if its norm is strictly greater (or the last norm is NaN
+ *     and its own is not): it is later in insertion order than everything the pool holds.
+ *   Stopping.  Log-probabilities are <= 0 and a >= 0, so no continuation of a beam of score r can be pooled with a norm above
+ *     r * inv_norm_max (the same fp32 multiply).  done_out[g] = 1 when, after the step, no beam of the group is live -- after a
+ *     flush none is -- or the pool is full and its last norm is STRICTLY greater than that bound for new beam 0, the group's
+ *     best (a tie does not stop the group).  The beams of a done group are written dead: score_out = -inf, live_out = 0, parent
+ *     and token as the walk left them.  It then offers nothing, so its pool stays as it is, and it is done again, in every
+ *     later call.  *all_done = 1 when every group is done, else 0 (written by a second, one-workgroup launch).
+ * 1 <= B, 2 B <= BLM_TOPK_MAX, k >= min(2 B, V), len >= 1, step >= 0, min_len >= 0.  score_out / live_out must not alias score /
+ * live; float and int32 operands 4-byte, int64 operands 8-byte aligned.  Integer atomics in LDS only, no floating-point
+ * atomics and no value recomputed: the result is exact and does not depend on the order in which waves run. */
+int blm_beam_select_pool(const float* cand_vals, const int64_t* cand_ids, const float* score, const uint8_t* live, int G, int B, int k,
+                         int V, int64_t eos, int step, int len, int min_len, float inv_norm, float inv_norm_max, int flush,
+                         const blm_beam_pool* pool, float* score_out, uint8_t* live_out, int64_t* parent, int64_t* token,
+                         uint8_t* done_out, uint8_t* all_done, void* stream);
 /* blm_sample_rows restricted to an allowed set: with q = softmax(x / temperature), the first top_k entries of the order above
  * (0: all; not capped by BLM_TOPK_MAX) intersected with the shortest prefix of that order whose q-mass reaches top_p (in (0, 1];
  * 1: all; never empty).  The draw is the arg-max over the allowed set of x / temperature + the SAME Philox Gumbel noise as

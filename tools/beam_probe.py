@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """The device-resident beam search (IncrementalLM.beam_search) against the same search over the older public API, and the
-selection kernels on their own.
+search with a finished-hypothesis pool (IncrementalLM.beam_search_pool) beside them, and the selection kernels on their own.
 
     python tools/beam_probe.py [--out profiles/r07_beam_probe.txt] [--quick]
 
 1. words/s of IncrementalLM._beam_trace (step -> blm_topk_rows -> blm_beam_select -> reorder_device, no host read inside the
    loop) against step -> torch.topk -> .cpu() -> numpy selection -> host-index reorder, for the configs[2] Transformer and the
    configs[1] LSTM, vocabulary 33,000, a 128-word prompt, G x B in 1x4, 1x8, 1x16, 8x8, 1x64; eos is a word id the random
-   model has no reason to prefer, so both sides generate all WORDS words.  The two sides alternate inside one process; each
-   figure is the median of REPS timed searches after one warm-up search, and the spread (max - min) / median is printed.
+   model has no reason to prefer, so both sides generate all WORDS words.  The pooled search (step -> blm_topk_rows(k = 2 B) ->
+   blm_beam_select_pool -> reorder_device, a pool of B) is the third side at every point.  The sides alternate inside one
+   process; each figure is the median of REPS timed searches after one warm-up search, and the spread (max - min) / median is
+   printed.
 2. blm_topk_rows against torch.topk on the same (R, 33,000) rows, R 8 / 64 / 512, k 8 / 64, with R x V x 4 bytes over the
    kernel's time beside the 8 TB/s HBM figure (rows this small may be served from L2 or the Infinity Cache, not HBM).
 3. blm_sample_rows_filtered (top_k 50; top_p 0.9; both) against blm_sample_rows on the same rows.
@@ -50,12 +52,16 @@ def search_rates(kind, m, G, B, dev, say):
 
     def old():
         return REF.beam_search_old_api(lm, prompts, B, WORDS, eos, topk_host)
+
+    def pooled():  # step -> blm_topk_rows(k = 2 B) -> blm_beam_select_pool -> reorder_device, a pool of B per prompt
+        return lm.beam_search_pool(prompts, B, WORDS, eos, pool=B, sync_every=16)
     with torch.no_grad():
         a, b = new(), old()  # warm-up of every shape, and the two searches side by side
         same = bool(np.array_equal(a[1], b[1]))
-        t = {"new": [], "old": []}
+        pooled()
+        t = {"new": [], "old": [], "pool": []}
         for _ in range(REPS):
-            for name, fn in (("new", new), ("old", old)):
+            for name, fn in (("new", new), ("old", old), ("pool", pooled)):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 fn()
@@ -66,6 +72,12 @@ def search_rates(kind, m, G, B, dev, say):
     say("%-4s G x B = %d x %-2d  device search %8.1f words/s (%7.2f ms/word, spread %4.1f %%) | old API %8.1f words/s (%7.2f ms/word, "
         "spread %4.1f %%) | device / old %.2fx  same tokens: %s"
         % (kind, G, B, WORDS / mn, mn / WORDS * 1e3, 100 * sn, WORDS / mo, mo / WORDS * 1e3, 100 * so, mo / mn, same))
+    mp = statistics.median(t["pool"])
+    sp = (max(t["pool"]) - min(t["pool"])) / mp
+    say("%-4s G x B = %d x %-2d  pooled search %8.1f words/s (%7.2f ms/word, spread %4.1f %%) | pooled / device %.2fx the time per word | "
+        "old API / pooled %.2fx" % (kind, G, B, WORDS / mp, mp / WORDS * 1e3, 100 * sp, mp / mn, mo / mp))
+    if mp > mo * (1.0 + max(sp, so)):
+        say("#    the pooled search is SLOWER than the old-API search here, beyond the spread")
     return mo / mn, max(sn, so)
 
 
@@ -106,6 +118,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="profiles/r07_beam_probe.txt")
     ap.add_argument("--quick", action="store_true", help="the Transformer at 1x8 and the kernels only")
+    ap.add_argument("--searches-only", action="store_true", help="part 1 only (the three searches)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     L.require_gfx950()
@@ -115,7 +128,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
     say("# tools/beam_probe.py: V %d, prompt %d words, %d generated words per search, median of %d, both sides alternated" % (V, CTX, WORDS, REPS))
-    say("# 1. beam search: device-resident against the older public API (host clock around a search that ends in a synchronise)")
+    say("# 1. beam search: device-resident against the older public API, and the search with a finished-hypothesis pool of B beside "
+        "them (host clock around a search that ends in a synchronise)")
     slower = []
     for kind in (("tlm",) if args.quick else ("tlm", "lstm")):
         m = build(kind, dev)
@@ -126,14 +140,22 @@ def main():
         del m
         torch.cuda.empty_cache()
     say("# device search slower than the old-API search beyond the spread at: %s" % (", ".join(slower) or "no measured point"))
+    if args.searches_only:
+        if args.out:
+            _write(args.out, lines)
+        return
     say("# 2. blm_topk_rows against torch.topk (HIP events, 20 calls per timing, median of 5)")
     topk_alone(dev, say)
     say("# 3. blm_sample_rows_filtered against blm_sample_rows (HIP events, 20 calls per timing, median of 5)")
     sampling_alone(dev, say)
     if args.out:
-        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        _write(args.out, lines)
+
+
+def _write(path, lines):
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
