@@ -22,6 +22,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_MUL_DGELU, EPI_BAYES_WGRAD, EPI_GP_MIX, E
 GEMM_ACCUMULATE = 1
 STREAM_WEIGHT = 0x10000000   # stream class in the top 4 bits, tensor / site id in the low 28: the classes cannot alias
 STREAM_DROPOUT = 0x20000000
+STREAM_LRT = 0x30000000      # pre-activation noise of local reparameterisation (ops.bayes_linear_lrt), + site id
 
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
@@ -87,6 +88,10 @@ SIGNATURES = {
     "blm_variational_group_fwd": (_i, [C.POINTER(VarItem), _i, _vp, _vp]),
     "blm_variational_group_bwd": (_i, [C.POINTER(VarItem), _i, _vp, _vp]),
     "blm_philox_normal": (_i, [_vp, _i64, _rngp, _vp]),
+    "blm_lrt_prepare": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "blm_lrt_combine": (_i, [_vp, _vp, _vp, _rngp, _i, _i, _i, _i, _i, _vp]),
+    "blm_lrt_bwd_factor": (_i, [_vp, _vp, _vp, _vp, _rngp, _i, _i, _i, _i, _i, _vp]),
+    "blm_lrt_mul": (_i, [_vp, _vp, _vp, _i64, _f, _i, _vp]),
     "blm_kl_mean_fwd": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _f, _vp, _vp]),
     "blm_kl_mean_bwd": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _f, _vp, _i64, _vp, _vp]),
     "blm_gemm": (_i, [C.POINTER(GemmArgs), _vp]),

@@ -38,6 +38,12 @@ class NoiseState:
     """Shared by all modules of one model: Philox key, optimisation step and this rank's window of
     global batch columns.  ``fused`` selects eps generation inside the GEMM tile loader."""
 
+    # Opt-in (set it on the instance: model.set_local_reparam): the layers that can -- BayesLinear on its own, the Bayesian
+    # feed-forward of the Transformer -- sample their pre-activations with noise per batch row (ops.bayes_linear_lrt) instead
+    # of one weight per step; every other variational site refuses the flag at the model's next forward
+    # (_check_local_reparam).  Training only: mc_sampling refuses a flagged model.
+    local_reparam = False
+
     def __init__(self, seed=1111):
         self.seed = int(seed)
         self.step = 0
@@ -144,6 +150,38 @@ def _advance_step(module, _inputs, _output):
         st.step = (st.step + 1) & 0xFFFFFFFF
 
 
+def _local_reparam_refusals(model):
+    """(path, site) of every noise-drawing module of ``model`` that has no local-reparameterisation path.  The estimator
+    replaces ONE product x W^T: the second linear of a post-LN feed-forward has that shape.  A tensor that feeds several
+    products (the LSTM gates, the embedding projection and its transpose), the GP / Variational families and the search
+    super-nets keep the weight-sampling estimator only, and so does the Bayesian attention output projection."""
+    families = ((BayesMultiheadAttention, "MHA"), (Bayes2LSTM, "LSTM"), (GPNN, "GP"), (GPNN2, "GP"), (GPLSTMCell, "GP"),
+                (VNN, "Variational"), (VLSTMCell, "Variational"))
+    mods = dict(model.named_modules())
+    out = []
+    for path, m in mods.items():
+        if not (callable(getattr(m, "draws_noise", None)) and m.draws_noise()):
+            continue
+        parent = mods[path.rpartition(".")[0]] if path else None
+        if isinstance(m, BayesLinear) and (parent is None or (type(parent) is BayesTransformerEncoderLayer and m is parent.linear2)):
+            continue
+        site = "EMB" if m is model and getattr(m, "bayes_embed", False) else next(
+            (name for cls, name in families if isinstance(m, cls) or isinstance(parent, cls)), type(m).__name__)
+        out.append((path or type(m).__name__, site))
+    return out
+
+
+def _check_local_reparam(module, _inputs):
+    st = module._st()
+    if st.local_reparam and getattr(st, "_lrt_checked", None) is not module:
+        bad = _local_reparam_refusals(module)
+        if bad:
+            raise BayesLMError("NoiseState.local_reparam: no local-reparameterisation path at site %s; it serves the Bayesian "
+                               "feed-forward (--T_bayes_pos FFN) and BayesLinear on its own"
+                               % ", ".join("%s (%s)" % (site, path) for path, site in bad))
+        st._lrt_checked = module
+
+
 def bind_state(model, state):
     """Give every sub-module the model's NoiseState and a unique id range (16 ids per module)."""
     for idx, m in enumerate(model.modules()):
@@ -154,6 +192,7 @@ def bind_state(model, state):
         raise BayesLMError("model has too many modules for the noise-stream id field")
     if isinstance(model, _Site):  # the root: see NoiseState.auto_step
         model.register_forward_hook(_advance_step)
+        model.register_forward_pre_hook(_check_local_reparam)
     return state
 
 
@@ -168,6 +207,10 @@ def require_variational_sites(model, mc_samples):
     """variational_sites(model), or the refusal of Monte-Carlo sampling on a model that has none: e.g. --uncertainty none,
     Gaussian type 0, Variational '00', VTransformer -- S passes would be S identical mean-weight passes at S times the cost."""
     sites = variational_sites(model)
+    if getattr(getattr(model, "noise_state", None), "local_reparam", False):
+        raise BayesLMError("--mc-samples %d: NoiseState.local_reparam is set on %s.  Local reparameterisation draws noise per row, so "
+                           "no call is one model over a whole stream; Monte-Carlo sampling takes the weight-sampling path"
+                           % (mc_samples, type(model).__name__))
     if not sites:
         raise BayesLMError("--mc-samples %d: %s has no variational tensor to sample (mean-weight scoring is "
                            "--mc-samples 0)" % (mc_samples, type(model).__name__))
@@ -279,7 +322,22 @@ class BayesLinear(_Site):
             raise BayesLMError("kl_divergence(prior=...) is dead code in the reference (model.py:1120-1122)")
         return ops.kl_mean(self.weight_mean, self.weight_lgstd)
 
+    def lrt_noise(self):
+        """ops.LrtNoise of this layer when the forward at hand takes the local-reparameterisation path (training mode, noise
+        on, NoiseState.local_reparam), else None: today's path, untouched."""
+        st = self._st()
+        if not (st.local_reparam and self.training and self.sample):
+            return None
+        if st.source == "torch" or self.eps_override is not None:
+            raise BayesLMError("NoiseState.local_reparam at BayesLinear: %s" % (
+                "noise source 'torch' has no per-row draw of the reference to reproduce" if st.source == "torch" else
+                "eps_override injects a weight-shaped eps, this path draws per (row, column): hand zeta to ops.bayes_linear_lrt"))
+        return ops.LrtNoise(None, st.seed, self._site_base, st.step, st.col_offset, st.global_cols)
+
     def forward(self, input):
+        zeta = self.lrt_noise()
+        if zeta is not None:
+            return ops.bayes_linear_lrt(input, self.weight_mean, self.weight_lgstd, zeta, self.fused_kl_lambda)
         return ops.bayes_linear(input, self.weight_mean, self.weight_lgstd, self.noise(), self.fused_kl_lambda,
                                 self._st().fused and self._st().source == "philox")
 
@@ -449,7 +507,11 @@ class _PostLNLayer(_Site):
         a = self.self_attn(src, src, src, attn_mask=src_mask, _link=lk1)[0]
         x = ops.add_dropout_ln(src, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, self._drop(self.p, 1), lk1)
         l2 = self.linear2
-        if isinstance(l2, BayesLinear):
+        zeta = l2.lrt_noise() if isinstance(l2, BayesLinear) else None
+        if zeta is not None:  # the second linear samples its pre-activations: linear1 + GELU + dropout, then that layer
+            f = ops.ffn_lrt(x, self.linear1.weight, self.linear1.bias, l2.weight_mean, l2.weight_lgstd, zeta, l2.fused_kl_lambda,
+                            self._drop(self.p, 0), lk2)
+        elif isinstance(l2, BayesLinear):
             f = ops.ffn(x, self.linear1.weight, self.linear1.bias, l2.weight_mean, None, l2.weight_lgstd, l2.noise(),
                         l2.fused_kl_lambda, self._st().fused, self._drop(self.p, 0), lk2)
         else:
@@ -510,6 +572,10 @@ class _LMHead(_Site):
 
     def set_fused_sampling(self, on):
         self.noise_state.fused = bool(on)
+
+    def set_local_reparam(self, on):
+        """See NoiseState.local_reparam."""
+        self.noise_state.local_reparam = bool(on)
 
     def set_noise_source(self, source):
         """"philox" (default) | "torch": see NoiseState.source."""

@@ -28,7 +28,7 @@ import torch
 from . import _lib as L
 from ._lib import BayesLMError, calls, dev_tensor, ptr, stream
 
-__all__ = ["Drop", "NoiseSpec", "ResidualLink", "linear", "bayes_linear", "ffn", "ffn_gp", "attention", "attention_qkv", "add_dropout_ln",
+__all__ = ["Drop", "NoiseSpec", "LrtNoise", "ResidualLink", "linear", "bayes_linear", "bayes_linear_lrt", "ffn", "ffn_lrt", "ffn_gp", "attention", "attention_qkv", "add_dropout_ln",
            "embed", "add_pe", "dropout", "cross_entropy", "kl_mean", "philox_normal", "sample_weight", "sampled", "lstm_layer", "lstm_stack2", "lstm_stack2_ok", "set_lstm_wavefront", "lstm_cell", "gp_mix", "add_rowvec",
            "clip_sgd", "gemm", "PtrTable", "set_grad_ready_hook", "set_embed_grad_sink", "rows_gather_add", "KernelTimer", "set_kernel_timer"]
 
@@ -834,6 +834,128 @@ def bayes_linear(x, mu, lgstd, noise=None, kl_lambda=0.0, fused=False):
 
 
 # ----------------------------------------------------------------------------
+# BayesLinear under local reparameterisation (opt-in, no reference counterpart):
+#   y = x mu^T + sqrt(x^2 (sigma^2)^T) * zeta,  zeta ~ N(0,1) per (row, column)
+# ----------------------------------------------------------------------------
+@dataclass
+class LrtNoise:
+    """Where zeta of `bayes_linear_lrt` comes from: an injected (M, N) tensor (parity tests) or the Philox stream
+    (seed, STREAM_LRT + site, step), keyed by the global batch column like a dropout mask (Drop)."""
+    eps: torch.Tensor = None
+    seed: int = 0
+    site: int = 0
+    step: int = 0
+    col_offset: int = 0
+    global_cols: int = 0
+
+    def rng(self):
+        return L.rng(self.seed, L.STREAM_LRT + self.site, self.step)
+
+
+_ONES = {}
+
+
+def _one(device):
+    """A device scalar 1.0: the upstream gradient blm_kl_mean_bwd reads when the KL term is folded into a layer's backward."""
+    t = _ONES.get(device)
+    if t is None:
+        t = _ONES[device] = torch.ones(1, device=device, dtype=torch.float32)
+    return t
+
+
+def _lrt_prepare(src, mode):
+    dst = torch.empty_like(src)
+    calls().blm_lrt_prepare(ptr(src), ptr(dst), src.numel(), mode, stream())
+    return dst
+
+
+def _lrt_mul(out, a, b, scale=1.0, accumulate=False):
+    calls().blm_lrt_mul(ptr(out), ptr(a), ptr(b), out.numel(), float(scale), 1 if accumulate else 0, stream())
+
+
+class _BayesLinearLRT(torch.autograd.Function):
+    """m = x mu^T and v = x^2 (sigma^2)^T are two products of the GEMM family; one combine pass turns them into
+    y = m + sqrt(v) * zeta in place with zeta generated in registers and keeps s = sqrt(v).  Backward regenerates zeta in the
+    pass that forms q = dy zeta / (2 s) (0 where s == 0), then dmu += dy^T x, dlgstd += 2 sigma^2 * (q^T x^2) and
+    dx = dy mu + 2 x * (q sigma^2).  sigma^2 = exp(2 lgstd) is formed once in forward and kept (N x K, a weight's size);
+    x^2 is formed again in backward instead of being kept: a second M x K activation held from forward to backward would
+    cost more than the one streaming pass that rebuilds it.  No sampled W exists at any point.  The KL gradient, scaled by
+    kl_lambda, is blm_kl_mean_bwd's: what BLM_EPI_BAYES_WGRAD adds on the weight-sampling path."""
+
+    @staticmethod
+    def forward(ctx, x, mu, lgstd, noise, kl_lambda):
+        L.require_gfx950()
+        x = _f32(x, "x")
+        N, K = mu.shape
+        M = x.numel() // K
+        B = x.shape[-2] if x.dim() >= 2 else 1
+        sig2 = _lrt_prepare(lgstd.detach(), 1)
+        x2 = _lrt_prepare(x, 0)
+        y = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
+        s = torch.empty(M, N, device=x.device, dtype=torch.float32)
+        gemm(L.GEMM_NT, x, mu, y, M, N, K, K, K, N, tag="lrt_mean_fwd")
+        gemm(L.GEMM_NT, x2, sig2, s, M, N, K, K, K, N, tag="lrt_var_fwd")
+        ctx.key = (M // B if B else 0, B, N, int(noise.col_offset), int(noise.global_cols))
+        calls().blm_lrt_combine(ptr(y), ptr(s), ptr(noise.eps), C.byref(noise.rng()), *ctx.key, stream())
+        ctx.save_for_backward(x, s, sig2)
+        ctx.mu, ctx.lgstd, ctx.noise, ctx.kl_lambda = mu, lgstd, noise, kl_lambda
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, s, sig2 = ctx.saved_tensors
+        mu, lgstd, noise, kl_lambda = ctx.mu, ctx.lgstd, ctx.noise, ctx.kl_lambda
+        dy = _f32(dy, "dy")
+        N, K = mu.shape
+        M = x.numel() // K
+        q = torch.empty_like(s)
+        calls().blm_lrt_bwd_factor(ptr(dy), ptr(s), ptr(q), ptr(noise.eps), C.byref(noise.rng()), *ctx.key, stream())
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            gemm(L.GEMM_NN, q, sig2, dx, M, K, N, N, K, K, tag="lrt_var_dgrad")
+            _lrt_mul(dx, dx, x, 2.0)
+            gemm(L.GEMM_NN, dy, mu, dx, M, K, N, N, K, K, accumulate=True, tag="lrt_mean_dgrad")
+        dmu = dlg = gmu = glg = None
+        if mu.requires_grad:
+            gmu, _, dmu = _wgrad_target(mu, zero=True)
+            gemm(L.GEMM_TN, dy, x, gmu, N, K, M, N, K, K, accumulate=True, tag="lrt_mean_wgrad")
+        if lgstd.requires_grad:
+            glg, _, dlg = _wgrad_target(lgstd, zero=True)
+            t = torch.empty_like(sig2)
+            gemm(L.GEMM_TN, q, _lrt_prepare(x, 0), t, N, K, M, N, K, K, tag="lrt_var_wgrad")
+            _lrt_mul(glg, t, sig2, 2.0, accumulate=True)
+        if kl_lambda != 0.0 and (gmu is not None or glg is not None):
+            # the kernel writes both gradients; a tensor that does not require one gets a scratch buffer
+            calls().blm_kl_mean_bwd(ptr(mu), K, ptr(lgstd), N, K, ptr(_one(x.device)), float(kl_lambda),
+                                    ptr(gmu if gmu is not None else torch.zeros_like(mu)), K,
+                                    ptr(glg if glg is not None else torch.zeros_like(lgstd)), stream())
+        _notify(mu, lgstd)
+        return dx, dmu, dlg, None, None
+
+
+def bayes_linear_lrt(x, mu, lgstd, noise, kl_lambda=0.0):
+    """BayesLinear under local reparameterisation.  ``noise``: an `LrtNoise` (never None: eval mode is `bayes_linear`);
+    x is seen as (..., B, K), and zeta's Philox stream is keyed by the global batch column col_offset + b."""
+    mu, lgstd = _weight(mu, "mu"), _weight(lgstd, "lgstd")
+    if x.shape[-1] != mu.shape[-1] or mu.dim() != 2 or lgstd.shape != mu.shape:
+        raise BayesLMError("bayes_linear_lrt: input (..., %d) against mu %s and lgstd %s" % (x.shape[-1], tuple(mu.shape), tuple(lgstd.shape)))
+    if not isinstance(noise, LrtNoise):
+        raise BayesLMError("bayes_linear_lrt: noise must be an ops.LrtNoise, got %s (mean weights: bayes_linear)" % type(noise).__name__)
+    M, N = x.numel() // max(mu.shape[1], 1), mu.shape[0]
+    B = x.shape[-2] if x.dim() >= 2 else 1
+    e = noise.eps
+    if e is not None and not (torch.is_tensor(e) and e.is_cuda and e.dtype == torch.float32 and e.is_contiguous() and e.numel() == M * N):
+        # an injected zeta is read by the kernels with y's extent on trust: a wrong shape would read past it
+        raise BayesLMError("bayes_linear_lrt: injected zeta must be a contiguous fp32 GPU tensor with the output's %d x %d elements, got %s"
+                           % (M, N, (tuple(e.shape), e.dtype, e.device) if torch.is_tensor(e) else type(e)))
+    if noise.col_offset < 0 or (noise.global_cols and noise.col_offset + B > noise.global_cols) or (not noise.global_cols and noise.col_offset):
+        raise BayesLMError("bayes_linear_lrt: batch columns [%d, %d) do not fit a global batch of %d columns"
+                           % (noise.col_offset, noise.col_offset + B, noise.global_cols or B))
+    return _BayesLinearLRT.apply(x, mu, lgstd, noise, kl_lambda)
+
+
+# ----------------------------------------------------------------------------
 # FFN:  y = lin2(drop(gelu(x W1^T + b1)))        (model.py:1043, 1169)
 # lin2 is nn.Linear (w2, b2) or BayesLinear (mu2, lgstd2, no bias).
 # ----------------------------------------------------------------------------
@@ -900,28 +1022,73 @@ class _FFN(torch.autograd.Function):
         elif b2 is not None and b2.requires_grad:
             _colsum_into(dy, M, N2, _grad_buf(b2))
         _notify(w2, b2, lgstd2 if bayes else None)
-        # linear1 (bias gradient = column sums of dz, taken inside the wgrad GEMM)
-        if w1.requires_grad:
-            gemm(L.GEMM_TN, dz, x, _grad_buf(w1), F_, D, M, F_, D, D, accumulate=True,
-                 colsum_a=_grad_buf(b1) if b1.requires_grad else None)
-        elif b1.requires_grad:
-            _colsum_into(dz, M, F_, _grad_buf(b1))
-        _notify(w1, b1)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            parked = ctx.link.take(x) if ctx.link is not None else None
-            if parked is not None:
-                gemm(L.GEMM_NN, dz, w1, parked, M, D, F_, F_, D, D, accumulate=True)
-                dx = parked
-            else:
-                dx = torch.empty_like(x)
-                gemm(L.GEMM_NN, dz, w1, dx, M, D, F_, F_, D, D)
-        return (dx,) + (None,) * 10
+        return (_ffn_linear1_backward(ctx, x, dz, w1, b1),) + (None,) * 10
+
+
+def _ffn_linear1_backward(ctx, x, dz, w1, b1):
+    """The first linear's half of a feed-forward backward, given dz (M, ff): w1 / b1 gradients in place, dx returned."""
+    F_, D = w1.shape
+    M = x.numel() // D
+    # linear1 (bias gradient = column sums of dz, taken inside the wgrad GEMM)
+    if w1.requires_grad:
+        gemm(L.GEMM_TN, dz, x, _grad_buf(w1), F_, D, M, F_, D, D, accumulate=True,
+             colsum_a=_grad_buf(b1) if b1.requires_grad else None)
+    elif b1.requires_grad:
+        _colsum_into(dz, M, F_, _grad_buf(b1))
+    _notify(w1, b1)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        parked = ctx.link.take(x) if ctx.link is not None else None
+        if parked is not None:
+            gemm(L.GEMM_NN, dz, w1, parked, M, D, F_, F_, D, D, accumulate=True)
+            dx = parked
+        else:
+            dx = torch.empty_like(x)
+            gemm(L.GEMM_NN, dz, w1, dx, M, D, F_, F_, D, D)
+    return dx
 
 
 def ffn(x, w1, b1, w2, b2=None, lgstd2=None, noise=None, kl_lambda=0.0, fused=False, drop=NO_DROP, link=None):
     w1, b1, w2, b2, lgstd2 = (_weight(t, n, in_place=True) for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2"), (lgstd2, "lgstd2")))
     return _FFN.apply(x, w1, b1, w2, b2, lgstd2, noise, kl_lambda, fused, drop, link)
+
+
+class _FFNLinear1(torch.autograd.Function):
+    """h = drop(gelu(x W1^T + b1)) on its own: the first product of `_FFN` with the same bias + GELU + dropout epilogue, for a
+    feed-forward whose second linear cannot be part of the one fused function (`ffn_lrt`).  Backward multiplies the incoming
+    dh by the factor the epilogue left (GELU' and keep mask) in one elementwise pass where `_FFN` has it in a GEMM epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, drop, link):
+        ctx.link = link
+        x = _f32(x, "x")
+        if link is not None and ctx.needs_input_grad[0]:
+            link.arm(x)
+        F_, D = w1.shape
+        M = x.numel() // D
+        B = x.shape[-2] if x.dim() >= 2 else 1
+        z = torch.empty(M, F_, device=x.device, dtype=torch.float32) if any(ctx.needs_input_grad) else None
+        h = torch.empty(*x.shape[:-1], F_, device=x.device, dtype=torch.float32)
+        gemm(L.GEMM_NT, x, w1, h, M, F_, D, D, D, F_, epilogue=L.EPI_BIAS_GELU, bias=b1, aux=z, drop=drop, drop_B=B,
+             tag="ffn_linear1_fwd")
+        ctx.save_for_backward(x, z)
+        ctx.p = (w1, b1)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        x, z = ctx.saved_tensors
+        w1, b1 = ctx.p
+        dh = _f32(dh, "dh")
+        dz = torch.empty_like(z)
+        _lrt_mul(dz, dh, z)
+        return _ffn_linear1_backward(ctx, x, dz, w1, b1), None, None, None, None
+
+
+def ffn_lrt(x, w1, b1, mu2, lgstd2, noise, kl_lambda=0.0, drop=NO_DROP, link=None):
+    """`ffn` with a Bayesian second linear under local reparameterisation: `_FFNLinear1`, then `bayes_linear_lrt`."""
+    w1, b1 = _weight(w1, "w1", in_place=True), _weight(b1, "b1", in_place=True)
+    return bayes_linear_lrt(_FFNLinear1.apply(x, w1, b1, drop, link), mu2, lgstd2, noise, kl_lambda)
 
 
 class _FFNGP(torch.autograd.Function):

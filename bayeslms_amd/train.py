@@ -54,6 +54,10 @@ def build_parser():
     p.add_argument('--prior2_path', default='steps/pytorchnn/prior/transformer2/', type=str)
     # new, optional
     p.add_argument('--fused-sampling', type=int, default=0, help='1: eps generated inside the GEMM tile loader')
+    p.add_argument('--local-reparam', type=int, default=0, choices=[0, 1],
+                   help='new, optional: 1 trains the Bayesian feed-forward (--uncertainty Bayesian --T_bayes_pos FFN) with the local '
+                        'reparameterisation estimator: noise per row of the batch on the pre-activations instead of one sampled weight '
+                        'per step (DESIGN.md section 4).  Every other variational site refuses it; so does --noise-source torch')
     p.add_argument('--gp-sample', type=int, default=0,
                    help='new, optional: 1 raises GPNN.sample (reference model.py:1799 leaves it False and train.py never sets '
                         'it): the GP coefficients / weights of --uncertainty Gaussian are re-sampled every training step')
@@ -214,6 +218,9 @@ def main(argv=None, history=None):
     """``history`` (optional dict) receives what the log lines print with two decimals at full precision:
     interval_loss, valid_loss, halved_epochs, test_loss."""
     args = build_parser().parse_args(argv)
+    if args.local_reparam and (args.noise_source or os.environ.get("BLM_NOISE_SOURCE", "philox")) == "torch":
+        raise SystemExit("--local-reparam 1 --noise-source torch: the reference has no per-row draw to reproduce "
+                         "(local reparameterisation takes the Philox streams only)")
     if history is None:
         history = {}
     history.update({"interval_loss": [], "valid_loss": [], "halved_epochs": [], "test_loss": None, "ms_per_batch": []})
@@ -277,6 +284,7 @@ def main(argv=None, history=None):
     model.set_fused_sampling(bool(args.fused_sampling))
     if args.noise_source is not None:
         model.set_noise_source(args.noise_source)
+    model.set_local_reparam(bool(args.local_reparam))
     if args.gp_sample:
         from .model import GPNN
         gps = [m for m in model.modules() if isinstance(m, GPNN) and m.draws_noise()]

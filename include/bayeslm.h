@@ -40,6 +40,7 @@ typedef enum blm_status {
  * key = seed.  Must match oracle/philox.py. */
 #define BLM_STREAM_WEIGHT  0x10000000u  /* class in the top 4 bits + tensor id (low 28 bits) */
 #define BLM_STREAM_DROPOUT 0x20000000u  /* + site id */
+#define BLM_STREAM_LRT     0x30000000u  /* + site id: the pre-activation noise of local reparameterisation */
 
 typedef struct blm_rng {
   uint64_t seed;    /* Philox key                                             */
@@ -132,6 +133,33 @@ typedef struct blm_var_item {
 } blm_var_item;
 int blm_variational_group_fwd(const blm_var_item* items, int32_t n, float* kl_out, void* stream);
 int blm_variational_group_bwd(const blm_var_item* items, int32_t n, const float* kl_grad, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Local reparameterisation (opt-in; csrc/lrt.hip).  No reference counterpart: the reference has the one-shared-W estimator
+ * above only.  For a BayesLinear weight (mu, lgstd: N x K) and input rows x (M x K) the layer's PRE-ACTIVATIONS are sampled,
+ *   m = x mu^T,   v = x^2 (sigma^2)^T,   s = sqrt(v),   y = m + s * zeta,    sigma^2 = exp(2 lgstd),
+ * zeta ~ N(0,1) independent per (row, column); backward, given dy, with q = dy * zeta / (2 s) and q = 0 where s == 0:
+ *   dmu = dy^T x,   dlgstd = 2 sigma^2 * (q^T x^2),   dx = dy mu + 2 x * (q sigma^2)          (* elementwise)
+ * The six products are blm_gemm calls of the caller (bayeslms_amd/ops.py: bayes_linear_lrt); the entry points below are the
+ * elementwise passes between them.  None of them reduces anything: results are bit-identical run to run in every mode.
+ *
+ * zeta: an (M, N) tensor handed in (parity tests), or, zeta == NULL, Philox noise from `rng` (stream BLM_STREAM_LRT + site id)
+ * generated in registers and never stored: y is seen as a (rows, B, N) activation, M = rows * B, and element (row, b, n) takes
+ * value ((row * global_cols + col_offset + b) * N + n) of the stream, as the dropout masks are keyed (global_cols 0 = B), so a
+ * data-parallel rank draws the columns of the one-process run and backward regenerates what forward drew.
+ * 16-byte accesses when N % 4 == 0 and the operands are 16-byte aligned, a guarded scalar loop otherwise.
+ * ------------------------------------------------------------------------ */
+/* dst[i] = src[i]^2 (mode 0: x^2) or exp(2 src[i]) (mode 1: sigma^2 from lgstd), i < n. */
+int blm_lrt_prepare(const float* src, float* dst, int64_t n, int mode, void* stream);
+/* In place: y holds m and receives y = m + sqrt(v) * zeta; s holds v and receives s = sqrt(v), which backward needs. */
+int blm_lrt_combine(float* y, float* s, const float* zeta, const blm_rng* rng, int rows, int B, int N, int col_offset,
+                    int global_cols, void* stream);
+/* q = dy * zeta / (2 s), 0 where s == 0; zeta handed in or regenerated exactly as blm_lrt_combine took it. */
+int blm_lrt_bwd_factor(const float* dy, const float* s, float* q, const float* zeta, const blm_rng* rng, int rows, int B, int N,
+                       int col_offset, int global_cols, void* stream);
+/* out[i] = (accumulate ? out[i] : 0) + scale * a[i] * b[i], i < n; out may be a or b.  dlgstd += 2 sigma^2 * (q^T x^2) and
+ * 2 x * (q sigma^2) of the formulas above. */
+int blm_lrt_mul(float* out, const float* a, const float* b, int64_t n, float scale, int accumulate, void* stream);
 
 /* --------------------------------------------------------------------------
  * fp32 MFMA GEMM family (v_mfma_f32_32x32x2_f32, LDS tiled)
