@@ -136,6 +136,7 @@ SIGNATURES = {
     "blm_embed_at": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "blm_log_softmax_rows": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp]),
     "blm_sample_rows": (_i, [_vp, _i64, _i, _i, _f, _rngp, _vp, _vp]),
+    "blm_row_stats": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_topk_rows": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "blm_beam_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "blm_beam_select_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _i, C.POINTER(BeamPoolArgs),

@@ -9,12 +9,15 @@ remaining backward GEMMs; then one fused global-norm clip + SGD-momentum kernel 
 three flat buffers (train.py:419-420,466 semantics, averaged over ranks).
 """
 import contextlib
+import dataclasses
 import datetime
 import math
 import os
 import sys
 import time
+from typing import Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -664,6 +667,8 @@ def evaluate(model, source, seq_len, eval_batch_size=None, rank=0, world=1, grou
     # gives the matrix cores 1280-2560 rows per product, G of them ~16384 (headline model, 12 windows of 20 x 128: 1.085 M tokens/s
     # window by window, 1.178 M in threes, 1.197 M in sixes, tools/eval_windows_probe.py).  total = sum over windows of len * mean is unchanged up
     # to the order of the additions.  BLM_EVAL_WINDOWS=1 walks the windows one by one as train.py:441-458 does.
+    # (_report_windows below restates this grouping for evaluate_report: a change here belongs there too;
+    # tests/test_gpu_eval_report.py compares the batches the two hand to the model)
     n_full = max(0, (source.size(0) - 1) // seq_len)  # windows of exactly seq_len rows; the ragged last one goes alone
     n_win = 1
     if hi > lo:
@@ -711,3 +716,242 @@ def evaluate(model, source, seq_len, eval_batch_size=None, rank=0, world=1, grou
 
 def perplexity(loss):
     return math.exp(loss)
+
+
+# ----------------------------------------------------------------------------
+# evaluation report: model-average perplexity and calibration
+# ----------------------------------------------------------------------------
+# Hidden rows per decoder launch of evaluate_report: the chunk's logits (mean weights) or log pbar (Monte-Carlo) are the only
+# (rows, V) matrix alive at a time -- 270 MB at V 33,000.  The value is unmeasured (tools/eval_report_probe.py times the call,
+# not this constant).
+_REPORT_ROWS = 2048
+
+
+@dataclasses.dataclass
+class EvalReport:
+    """What evaluate_report returns; ``as_dict()`` is what the command lines write as JSON.  Fields that a run does not produce
+    are None: the calibration block without a stored distribution (Monte-Carlo with calibration=False), the Monte-Carlo block
+    at mean weights."""
+    tokens: int                       # tokens that entered the figures
+    skipped: int                      # tokens whose target is outside [0, V): left out of everything, as the cross entropy leaves them out
+    loss: float                       # mean NLL, nats; under Monte-Carlo of the per-token model average pbar
+    ppl: float
+    mc_samples: int = 0
+    accuracy: Optional[float] = None       # share of tokens whose target is the prediction (rank 0)
+    top5_accuracy: Optional[float] = None  # ... is among the five best (rank < 5)
+    mean_conf: Optional[float] = None      # mean largest probability
+    mean_entropy: Optional[float] = None   # mean entropy of the distribution the token was scored with, nats
+    ece: Optional[float] = None            # expected calibration error over `bins`
+    bins: Optional[list] = None            # [count, mean_conf, accuracy] per equal-width confidence bin (zeros in an empty bin)
+    sample_loss: Optional[list] = None     # (S) each weight sample's own mean NLL
+    sample_loss_mean: Optional[float] = None
+    mean_h_pred: Optional[float] = None    # mean predictive entropy H[pbar]
+    mean_mi: Optional[float] = None        # mean mutual information between the word and the weights
+    per_token: Optional[dict] = None       # keep_tokens: float / int arrays in text order, skipped tokens included (NaN / -1)
+
+    def as_dict(self):
+        d = dataclasses.asdict(self)
+        del d["per_token"]
+        return d
+
+
+def report_from_tokens(nll, conf=None, entropy=None, rank=None, valid=None, bins=15, nll_s=None, h_pred=None, mi=None):
+    """The figures of an EvalReport from per-token arrays (host code; numpy or anything numpy converts): every sum in float64.
+    ``valid`` (bool per token, default all): the tokens that count; the others are ``skipped``.  ``rank`` is blm_row_stats':
+    entries ahead of the target.  Calibration needs ``conf`` and ``rank``: B = ``bins`` equal-width confidence bins, a token
+    falls into bin min(B - 1, floor(conf B)) (conf = 1 into the last one), ece = sum_b n_b / N |accuracy_b - mean_conf_b|.
+    ``nll_s`` (tokens, S), ``h_pred`` and ``mi`` make the Monte-Carlo block."""
+    nll = np.asarray(nll, dtype=np.float64).reshape(-1)
+    ok = np.ones(nll.shape[0], dtype=bool) if valid is None else np.asarray(valid, dtype=bool).reshape(-1)
+    n = int(ok.sum())
+    B = int(bins)
+    if B < 1:
+        raise ops.BayesLMError("report_from_tokens: bins must be positive, got %d" % B)
+
+    def mean(a):
+        return float(np.asarray(a, dtype=np.float64).reshape(-1)[ok].sum() / n) if n else float("nan")
+
+    loss = mean(nll)
+    rep = EvalReport(tokens=n, skipped=int(ok.shape[0] - n), loss=loss, ppl=math.exp(min(loss, 700.0)) if loss == loss else loss)
+    if conf is not None:
+        rep.mean_conf = mean(conf)
+    if entropy is not None:
+        rep.mean_entropy = mean(entropy)
+    if rank is not None:
+        r = np.asarray(rank).reshape(-1)[ok]
+        rep.accuracy = float((r == 0).sum() / n) if n else float("nan")
+        rep.top5_accuracy = float(((r >= 0) & (r < 5)).sum() / n) if n else float("nan")
+    if conf is not None and rank is not None:
+        c = np.asarray(conf, dtype=np.float64).reshape(-1)[ok]
+        hit = (np.asarray(rank).reshape(-1)[ok] == 0).astype(np.float64)
+        idx = np.clip(np.floor(np.nan_to_num(c) * B), 0, B - 1).astype(np.int64)
+        cnt = np.bincount(idx, minlength=B)
+        csum, hsum = np.bincount(idx, weights=c, minlength=B), np.bincount(idx, weights=hit, minlength=B)
+        safe = np.maximum(cnt, 1)
+        mconf, acc = csum / safe, hsum / safe
+        rep.ece = float((cnt / n * np.abs(acc - mconf)).sum()) if n else float("nan")
+        rep.bins = [[int(cnt[b]), float(mconf[b]), float(acc[b])] for b in range(B)]
+    if nll_s is not None:
+        s = np.asarray(nll_s, dtype=np.float64)
+        s = s.reshape(nll.shape[0], -1)[ok]
+        rep.mc_samples = int(s.shape[1])
+        rep.sample_loss = [float(v) for v in (s.sum(0) / n)] if n else [float("nan")] * s.shape[1]
+        rep.sample_loss_mean = float(np.mean(rep.sample_loss))
+    if h_pred is not None:
+        rep.mean_h_pred = mean(h_pred)
+    if mi is not None:
+        rep.mean_mi = mean(mi)
+    return rep
+
+
+def _report_windows(source, seq_len, recurrent):
+    """The batches engine.evaluate forms from ``source`` in a single process, in its order -> (data, flat targets, text
+    position of every target): a stateless model gets G full windows side by side as one batch of G x columns and the ragged
+    last window alone; a recurrent one gets G consecutive windows as one longer window (same thresholds, same BLM_EVAL_WINDOWS).
+    Text position: column c of the batchified stream holds the tokens c * rows .. (c + 1) * rows - 1 of the text.
+    This restates the grouping rule inside evaluate (row budgets, BLM_EVAL_WINDOWS, the loop over full windows), which stays as it
+    is: a change to either belongs in both, and tests/test_gpu_eval_report.py compares the batches the two hand to the model."""
+    from .data import get_batch
+    nrows, cols = source.shape
+    n_full = max(0, (nrows - 1) // seq_len)
+    rows = 2400 if recurrent else 16384
+    n_win = int(os.environ.get("BLM_EVAL_WINDOWS", "0")) or max(1, min(max(n_full, 1), rows // max(1, seq_len * cols)))
+    stride = seq_len * (n_win if recurrent else 1)
+    col0 = np.arange(cols, dtype=np.int64) * nrows
+
+    def pos(start, n):
+        return (np.arange(start + 1, start + 1 + n, dtype=np.int64)[:, None] + col0[None, :])
+
+    i, left = 0, n_full
+    while not recurrent and n_win > 1 and left > 1:
+        g = min(n_win, left)
+        starts = range(i, i + g * seq_len, seq_len)
+        data = torch.cat([source[k:k + seq_len] for k in starts], 1)
+        targets = torch.cat([source[k + 1:k + 1 + seq_len] for k in starts], 1).reshape(-1)
+        yield data, targets, np.concatenate([pos(k, seq_len) for k in starts], 1).reshape(-1)
+        i, left = i + g * seq_len, left - g
+    for i in range(i, nrows - 1, stride):
+        data, targets = get_batch(source, i, stride)
+        yield data, targets, pos(i, len(data)).reshape(-1)
+
+
+def evaluate_report(model, source, seq_len, eval_batch_size=None, mc_samples=0, seed=1111, bins=15, calibration=True,
+                    keep_tokens=False):
+    """Held-out loss / perplexity, accuracy and calibration of ``model`` over the batchified stream ``source``, at mean weights
+    (``mc_samples`` 0) or under the average of S = ``mc_samples`` >= 2 Monte-Carlo weight samples -> EvalReport.
+
+    The walk is engine.evaluate's (same windows, same grouping: _report_windows) with the decoder handing back its input rows;
+    those go through the decoder in chunks of _REPORT_ROWS rows and blm_row_stats reduces each chunk's (rows, V) matrix to
+    per-token NLL, confidence, entropy, prediction and rank in one read.  The per-token float32 arrays stay on the device
+    until the walk is over, come to the host in one copy, and every sum is formed there in float64 (report_from_tokens).
+
+    mc_samples = S: S passes per batch in the n-best scorer's sampling state (model.mc_sampling(model, seed, S), sample s
+    selected with set_step(s)): sample s is ONE model for the whole text, and a recurrent model carries S (h, c) sets from window
+    to window.  The model average is taken PER TOKEN, pbar(w | history) = mean_s p_s(w | history) -- a normalised distribution
+    over word sequences, whose NLL is ``loss`` -- not the scorer's sentence-level -log mean_s exp(-NLL_s(sentence)).  One launch
+    per chunk keeps log pbar with nll_s, bma_nll, h_pred and mi (ops.linear_mc_logprobs), and blm_row_stats reads log pbar.
+    ``calibration`` False under Monte-Carlo: ops.linear_mc_stats instead -- nothing of width V is stored, and the report has no
+    accuracy / confidence / calibration block (at mean weights the chunk's logits exist either way and the flag changes nothing).
+    Refused: mc_samples 1; a model without variational sites or with local reparameterisation (mc_sampling's refusals); cells that
+    redraw noise at every time step of a call (as IncrementalLM refuses them).  ``eval_batch_size`` is accepted for symmetry with
+    the reference's evaluate and unused, like there.  Single process only.  The model is left in eval mode with the caller's
+    noise (seed, step, auto_step)."""
+    from . import incremental
+    from .model import inference_decoder, mc_sampling, repackage_hidden
+    S = int(mc_samples)
+    model.eval()
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        raise ops.BayesLMError("evaluate_report runs in a single process (world size %d): sharding the report over ranks is not "
+                               "built; call it on one rank" % dist.get_world_size())
+    if S < 0 or S == 1 or S > 64:
+        raise ops.BayesLMError("evaluate_report: mc_samples must be 0 (mean weights) or 2..64, got %d: one sample is neither the "
+                               "mean-weight model nor an average, and blm_linear_mc_logprobs / blm_linear_mc_stats take at most 64 "
+                               "samples per launch" % S)
+    dec = inference_decoder(model)
+    if dec is None:
+        raise ops.BayesLMError("evaluate_report: %s has no decoder that hands back its input rows" % type(model).__name__)
+    recurrent = hasattr(model, "init_hidden")
+    if S and recurrent:
+        cell = incremental._redraws_per_time_step(model)
+        if cell:
+            raise ops.BayesLMError("evaluate_report: mc_samples on %s: %s draws fresh noise at every time step of a call, so a "
+                                   "sample is not one model over a stream" % (type(model).__name__, cell))
+    V = dec.weight.shape[0]
+    cols = source.shape[1]
+    keep = {k: [] for k in ("tgt", "pos", "nll", "conf", "entropy", "pred", "rank", "nll_s", "h_pred", "mi")}
+
+    def reduce_rows(x, targets):
+        """x: (rows, K) at mean weights, (S, rows, K) under Monte-Carlo"""
+        for a in range(0, targets.numel(), _REPORT_ROWS):
+            t = targets[a:a + _REPORT_ROWS]
+            if S == 0:
+                st = ops.row_stats(ops.linear(x[a:a + _REPORT_ROWS], dec.weight, dec.bias), t, V)
+            elif calibration:
+                mc = ops.linear_mc_logprobs(x[:, a:a + _REPORT_ROWS], dec.weight, dec.bias, tgt=t, dec=mc_dec, stats=True)
+                st = ops.row_stats(mc.logp, t, V)
+            else:
+                mc, st = ops.linear_mc_stats(x[:, a:a + _REPORT_ROWS], dec.weight, dec.bias, t, dec=mc_dec), None
+            if S:
+                keep["nll"].append(mc.bma_nll)
+                keep["nll_s"].append(mc.nll_s)
+                keep["h_pred"].append(mc.h_pred)
+                keep["mi"].append(mc.mi)
+            else:
+                keep["nll"].append(st.nll)
+            if st is not None:
+                keep["conf"].append(st.conf)
+                keep["entropy"].append(st.entropy)
+                keep["pred"].append(st.pred)
+                keep["rank"].append(st.rank)
+
+    with torch.no_grad(), dec.inference(input_rows=True):
+        if S == 0:
+            hidden = model.init_hidden(cols) if recurrent else None
+            for data, targets, pos in _report_windows(source, seq_len, recurrent):
+                if recurrent:
+                    x, hidden = model(data, hidden)
+                    hidden = repackage_hidden(hidden)
+                else:
+                    x = model(data)
+                reduce_rows(x.reshape(-1, x.shape[-1]), targets)
+                keep["tgt"].append(targets)
+                keep["pos"].append(pos)
+        else:
+            with mc_sampling(model, seed, S):
+                mc_dec = ops.McDecoder(dec.weight, dec.bias)  # the vocabulary padded once for the run
+                hidden = [model.init_hidden(cols) for _ in range(S)] if recurrent else None
+                for data, targets, pos in _report_windows(source, seq_len, recurrent):
+                    xs = []
+                    for s in range(S):
+                        model.set_step(s)
+                        if recurrent:
+                            x, h = model(data, hidden[s])
+                            hidden[s] = repackage_hidden(h)
+                        else:
+                            x = model(data)
+                        xs.append(x.reshape(-1, x.shape[-1]))
+                    reduce_rows(torch.stack(xs), targets)
+                    keep["tgt"].append(targets)
+                    keep["pos"].append(pos)
+    # one copy to the host: every float32 array side by side, the integers likewise
+    fl = [k for k in ("nll", "conf", "entropy", "h_pred", "mi") if keep[k]]
+    n_tok = sum(t.numel() for t in keep["tgt"])
+    host = {}
+    if n_tok:
+        packed = torch.stack([torch.cat(keep[k]) for k in fl]).cpu().numpy()
+        host = {k: packed[j] for j, k in enumerate(fl)}
+        host["tgt"] = torch.cat(keep["tgt"]).cpu().numpy()
+        if keep["rank"]:
+            host["pred"], host["rank"] = torch.stack([torch.cat(keep["pred"]), torch.cat(keep["rank"])]).cpu().numpy()
+        if keep["nll_s"]:
+            host["nll_s"] = torch.cat(keep["nll_s"]).cpu().numpy()
+    else:
+        host = {"nll": np.zeros(0, np.float32), "tgt": np.zeros(0, np.int64)}
+    valid = (host["tgt"] >= 0) & (host["tgt"] < V)
+    rep = report_from_tokens(host["nll"], host.get("conf"), host.get("entropy"), host.get("rank"), valid, bins,
+                             host.get("nll_s"), host.get("h_pred"), host.get("mi"))
+    rep.mc_samples = S
+    if keep_tokens:
+        order = np.argsort(np.concatenate(keep["pos"])) if n_tok else np.zeros(0, np.int64)
+        rep.per_token = {k: v[order] for k, v in host.items()}
+    return rep

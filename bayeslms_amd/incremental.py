@@ -37,9 +37,10 @@ continuation still equals the full forward over the history.  step runs the S pa
 of the state, and one decoder launch over all S of them returns log pbar = log mean_s p_s (blm_linear_mc_logprobs; many rows
 of a wide model compose it from the logits instead, _MC_FUSED_MAX_ROWS_K), or with targets their NLL under pbar
 (blm_linear_mc_stats).  The sampling state is entered and left inside step: the model is in eval
-mode whenever the caller holds it.  Not covered: two-model interpolation, the architecture-search super-nets, Monte-Carlo
-perplexity in engine.evaluate, and under mc_samples the LSTM cells that draw fresh noise at every time step of a CALL (the
-Variational LSTM's noise rows, the GP-LSTM's random frequencies: such a sample is not one model over a stream).
+mode whenever the caller holds it.  Not covered: two-model interpolation, the architecture-search super-nets, and under
+mc_samples the LSTM cells that draw fresh noise at every time step of a CALL (the Variational LSTM's noise rows, the GP-LSTM's
+random frequencies: such a sample is not one model over a stream).  Monte-Carlo perplexity of a held-out text is
+engine.evaluate_report.
 """
 import math
 from typing import NamedTuple, Optional

@@ -2133,6 +2133,47 @@ def log_softmax_rows(x, V=None, out=None):
     return out
 
 
+class RowStats(NamedTuple):
+    """What an evaluation keeps of each row of logits or log-probabilities (include/bayeslm.h, blm_row_stats)."""
+    nll: Optional[torch.Tensor]   # (R,) float32 logsumexp - x[target]; NaN where the target is outside [0, V); None without targets
+    conf: torch.Tensor            # (R,) float32 the largest probability of the row
+    entropy: torch.Tensor         # (R,) float32 entropy of the row's distribution, nats
+    pred: torch.Tensor            # (R,) int32 the lowest index that holds the maximum
+    rank: Optional[torch.Tensor]  # (R,) int32 entries ahead of the target (0: it is the prediction; -1: no target); None without targets
+
+
+def row_stats(x, targets=None, V=None):
+    """NLL of the target, confidence, entropy, prediction and rank of the target for every row of the (R, >= V) matrix x of
+    logits or log-probabilities -- the row is normalised by the kernel -- from one read of x (blm_row_stats; row stride honoured:
+    padded rows, and a (R, V) view of padded rows, are read in place).  ``targets`` (R,) int64 or None.  A row that holds a NaN
+    is NaN / -1 throughout.  Bit-identical run to run.  -> RowStats"""
+    if torch.is_tensor(x) and x.dim() == 2 and x.stride(-1) == 1 and x.stride(0) >= x.shape[1] and not x.is_contiguous():
+        dev_tensor(x[:1], "x")  # the device checks of the product path; the view itself is what the kernel reads
+    else:
+        x = _f32(x, "x")
+    if x.dim() != 2 or x.stride(-1) != 1:
+        raise BayesLMError("row_stats: a row-major (R, V) matrix expected")
+    R, V = x.shape[0], int(V if V is not None else x.shape[1])
+    if not 1 <= V <= x.shape[1]:
+        raise BayesLMError("row_stats: V = %d outside [1, %d], the columns of x" % (V, x.shape[1]))
+    dev = x.device
+    conf, entropy = (torch.empty(R, device=dev, dtype=torch.float32) for _ in range(2))
+    pred = torch.empty(R, device=dev, dtype=torch.int32)
+    tgt = nll = rank = None
+    if targets is not None:
+        tgt = dev_tensor(targets.reshape(-1), "targets", torch.int64)
+        if tgt.numel() != R:
+            raise BayesLMError("row_stats: %d targets for %d rows" % (tgt.numel(), R))
+        nll = torch.empty(R, device=dev, dtype=torch.float32)
+        rank = torch.empty(R, device=dev, dtype=torch.int32)
+    if R == 0:
+        return RowStats(nll, conf, entropy, pred, rank)
+    L.require_gfx950()
+    calls().blm_row_stats(ptr(x), x.stride(0) if R > 1 else max(x.stride(0), V), ptr(tgt), R, V, ptr(nll), ptr(conf), ptr(entropy),
+                          ptr(pred), ptr(rank), stream())
+    return RowStats(nll, conf, entropy, pred, rank)
+
+
 def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=1.0):
     """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
     with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64

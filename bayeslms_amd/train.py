@@ -87,7 +87,24 @@ def build_parser():
     p.add_argument('--history', type=str, default='',
                    help='new, optional: rank 0 writes what the log lines print with two decimals (interval / valid / test '
                         'loss, LR-halving epochs, ms per batch) at full precision to this JSON file')
+    p.add_argument('--test-report', type=str, default='', metavar='PATH',
+                   help='new, optional: after the final test pass, write engine.evaluate_report of the test set (loss, perplexity, '
+                        'accuracy, calibration; bayeslms_amd.evaluate\'s JSON) to this file.  Single process only')
+    p.add_argument('--test-mc-samples', type=int, default=0, metavar='S',
+                   help='new, optional (with --test-report): S >= 2 reports the test set under the average of S Monte-Carlo weight '
+                        'samples keyed by --seed (0: mean weights)')
     return p
+
+
+def check_report_args(args, world):
+    """--test-report / --test-mc-samples, refused before anything is loaded."""
+    if args.test_mc_samples and not args.test_report:
+        raise SystemExit("--test-mc-samples needs --test-report")
+    if args.test_mc_samples < 0 or args.test_mc_samples == 1 or args.test_mc_samples > 64:
+        raise SystemExit("--test-mc-samples must be 0 (mean weights) or lie in 2..64, the most one decoder launch averages (got %d)" % args.test_mc_samples)
+    if args.test_report and world > 1:
+        raise SystemExit("--test-report runs in a single process: the report is not sharded over ranks (world size %d); "
+                         "write it with bayeslms_amd.evaluate from the saved model" % world)
 
 
 def build_model(args, ntokens):
@@ -225,6 +242,7 @@ def main(argv=None, history=None):
         history = {}
     history.update({"interval_loss": [], "valid_loss": [], "halved_epochs": [], "test_loss": None, "ms_per_batch": []})
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    check_report_args(args, world)
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     is_main = rank == 0
@@ -384,6 +402,11 @@ def main(argv=None, history=None):
         import json
         with open(args.history, 'w') as f:
             json.dump(history, f)
+    if args.test_report:
+        import json
+        report = engine.evaluate_report(model, test_data, args.seq_len, mc_samples=args.test_mc_samples, seed=args.seed)
+        with open(args.test_report, 'w') as f:
+            json.dump(report.as_dict(), f)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

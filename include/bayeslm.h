@@ -539,6 +539,16 @@ int blm_log_softmax_rows(const float* x, int64_t ldx, float* out, int64_t ldo, i
  * x / temperature with u from Philox: counter (column, row, rng->stream, rng->step), key rng->seed, first word;
  * u = ((w >> 8) + 0.5) * 2^-24, noise -log(-log u).  The same rng gives the same ids. */
 int blm_sample_rows(const float* x, int64_t ldx, int R, int V, float temperature, const blm_rng* rng, int64_t* out, void* stream);
+/* What an evaluation needs of each row of x (R, V; row stride ldx >= V), logits or log-probabilities alike -- the row is
+ * normalised here, read ONCE (csrc/rowstats.hip).  With lse = logsumexp(x[r, :V]) and p = softmax(x[r, :V]):
+ *   nll[r] = lse - x[r, tgt[r]];  conf[r] = exp(max - lse), the largest p;  entropy[r] = lse - sum_v p_v x_v (a column at -inf
+ *   adds 0);  pred[r] = the lowest index that holds the maximum;  rank[r] = the columns strictly greater than the target's
+ *   value + the equal ones at a lower index (0: the target is the prediction).
+ * A target outside [0, V) gives nll NaN and rank -1 in that row only; a row that holds a NaN gives nll = conf = entropy = NaN and
+ * pred = rank = -1.  Every output pointer may be NULL; tgt may be NULL, and nll and rank must then be NULL too.  Folds run in a
+ * fixed order without atomics: the same bits in every run.  No workspace. */
+int blm_row_stats(const float* x, int64_t ldx, const int64_t* tgt, int R, int V, float* nll, float* conf, float* entropy,
+                  int32_t* pred, int32_t* rank, void* stream);
 
 /* --------------------------------------------------------------------------
  * Search on the incremental path (csrc/beam.hip): the k best next words, beam selection, top-k / nucleus sampling.
