@@ -1,0 +1,273 @@
+// Distillation loss: cross entropy of softmax(logits) against a DENSE target distribution q = exp(logq) (the teacher's
+// log pbar, blm_linear_mc_logprobs, or a mean-weight log-softmax), interpolated with the hard-label cross entropy and fused
+// with its gradient the way ce_row_kernel (elementwise.hip) fuses the hard-label one.  Per row m, with z = logits[m, :],
+// l = logq[m, :] (-inf: q = 0), Q = sum q, lse = logsumexp z, p = exp(z - lse), t = tgt[m], valid = 0 <= t < V:
+//   nll  = valid ? lse - z_t : 0
+//   soft = Q lse - sum_{q>0} q z
+//   kl   = sum_{q>0} q (l - (z - lse))          summed term by term: the terms are small where the student is close
+//   loss = (1 - lambda) nll + lambda soft
+//   dz_v = ((1 - lambda) valid (p_v - [v = t]) + lambda (Q p_v - q_v)) grad_scale
+// One workgroup per row, every sum in a fixed order, no atomics: the same bits from every run.
+#include "blm_device.h"
+#include "blm_host.h"
+
+namespace blm {
+
+// Block reductions of a 1024-thread workgroup (16 waves) that cost one register per value: the 16 per-wave partials are read
+// back one per lane and folded by a butterfly (blm_device.h's block_sum<16> reads all 16 into registers of every lane -- three
+// sums are 48 registers, which the register-resident rows below do not leave).  Fixed order: the same bits from every run.
+__device__ __forceinline__ float fold16_sum(float r) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+  return r;
+}
+__device__ __forceinline__ float row_max(float v, float* red) {
+  v = wave_max(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  float r = red[lane & 15];
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) r = fmaxf(r, __shfl_xor(r, o, 64));
+  return r;
+}
+__device__ __forceinline__ float row_sum(float v, float* red) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  return fold16_sum(red[lane & 15]);
+}
+__device__ __forceinline__ void row_sum3(float& a, float& b, float& c, float (*red)[16]) {  // three sums behind one barrier pair
+  a = wave_sum(a);
+  b = wave_sum(b);
+  c = wave_sum(c);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; }
+  __syncthreads();
+  a = fold16_sum(red[0][lane & 15]);
+  b = fold16_sum(red[1][lane & 15]);
+  c = fold16_sum(red[2][lane & 15]);
+}
+
+struct SoftCoef {
+  float p, q, t;  // gradient = p * softmax - q * teacher - t * onehot
+};
+__device__ __forceinline__ SoftCoef soft_coef(float lambda, bool valid, float Q, float gscale) {
+  const float hard = valid ? (1.f - lambda) * gscale : 0.f;
+  return {hard + lambda * Q * gscale, lambda * gscale, hard};
+}
+
+// one element of the second sweep: its KL term (returned) and its gradient (g)
+__device__ __forceinline__ float soft_elem(float z, float l, float lse, const SoftCoef& c, float& g) {
+  const float lp = z - lse, q = __expf(l);
+  g = c.p * __expf(lp) - c.q * q;
+  return q > 0.f ? q * (l - lp) : 0.f;
+}
+
+// Both rows held in registers: 1024 threads x NV float4 of each cover V <= 4096 NV, so the logits and the teacher row are
+// each read from HBM exactly once, all 2 NV loads of a thread in flight together; Q and sum q z need no lse and are formed
+// from the loaded values, the gradient is written from registers (in place over the logits when dlogits == logits).
+// Requires ld, ldq multiples of 4 and 16-byte aligned bases (blm_ce_soft_fwd_bwd selects).  logits / dlogits may alias:
+// not __restrict__.
+template <int NV>
+__global__ __launch_bounds__(1024) void ce_soft_row_kernel(const float* logits, long ld, const float* __restrict__ logq, long ldq,
+                                                           const int64_t* __restrict__ tgt, float lambda, float* __restrict__ loss,
+                                                           float* __restrict__ nll, float* __restrict__ soft,
+                                                           float* __restrict__ kl, float* __restrict__ lse_out, float* dlogits,
+                                                           float gscale, int V) {
+  __shared__ float red[3][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  const float* y = logq + row * ldq;
+  const unsigned t0 = threadIdx.x * 4u, Vu = (unsigned)V;  // unsigned: base + 32-bit offset addressing, no 64-bit address per load
+  // The registers hold the quads that lie wholly inside the row: one compare per quad, float4 loads and stores only, all 2 NV
+  // loads issued back to back (a quad outside reads quad 0 instead -- V >= 4 here -- and is skipped wherever the quads are
+  // used).  The V % 4 columns behind the last whole quad are one extra (z, l) pair in threads 0 .. V % 4 - 1.
+  float4 v[NV], u[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const unsigned j = t0 + 4096u * i;
+    const bool in = j + 3 < Vu;
+    const unsigned js = in ? j : 0u;
+    v[i] = *reinterpret_cast<const float4*>(x + js);
+    u[i] = *reinterpret_cast<const float4*>(y + js);
+  }
+  const unsigned je = (Vu & ~3u) + threadIdx.x;  // this thread's column behind the whole quads, if je < V
+  const bool extra = je < Vu;
+  const float ze = extra ? x[je] : -INFINITY, le = extra ? y[je] : -INFINITY;
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // read before any in-place gradient write (the reductions below have barriers)
+  const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;  // 32-bit from here on
+  const float qe = __expf(le);
+  float m = ze, Q = qe, qz = qe > 0.f ? qe * ze : 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;  // tested where the quad is used, behind the loads: none of them waits for another
+    m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
+    const float q0 = __expf(u[i].x), q1 = __expf(u[i].y), q2 = __expf(u[i].z), q3 = __expf(u[i].w);
+    Q += (q0 + q1) + (q2 + q3);
+    qz += ((q0 > 0.f ? q0 * v[i].x : 0.f) + (q1 > 0.f ? q1 * v[i].y : 0.f)) +
+          ((q2 > 0.f ? q2 * v[i].z : 0.f) + (q3 > 0.f ? q3 * v[i].w : 0.f));
+  }
+  const float M_ = row_max(m, red[0]);
+  float l = __expf(ze - M_);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;
+    l += __expf(v[i].x - M_) + __expf(v[i].y - M_) + __expf(v[i].z - M_) + __expf(v[i].w - M_);
+  }
+  row_sum3(l, Q, qz, red);
+  const float lse = M_ + __logf(l);
+  const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
+  float* d = dlogits ? dlogits + row * ld : nullptr;
+  float ge;
+  float k = soft_elem(ze, le, lse, c, ge);
+  if (d && extra) d[je] = tu == je ? ge - c.t : ge;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const unsigned j = t0 + 4096u * i;
+    if (!(j + 3 < Vu)) continue;
+    float4 g;
+    k += (soft_elem(v[i].x, u[i].x, lse, c, g.x) + soft_elem(v[i].y, u[i].y, lse, c, g.y)) +
+         (soft_elem(v[i].z, u[i].z, lse, c, g.z) + soft_elem(v[i].w, u[i].w, lse, c, g.w));
+    if (d) {
+      g.x -= tu == j ? c.t : 0.f;
+      g.y -= tu == j + 1 ? c.t : 0.f;
+      g.z -= tu == j + 2 ? c.t : 0.f;
+      g.w -= tu == j + 3 ? c.t : 0.f;
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+  }
+  k = row_sum(k, red[0]);
+  if (threadIdx.x == 0) {
+    const float n = valid ? lse - xt : 0.f, s = Q * lse - qz;
+    loss[row] = (1.f - lambda) * n + lambda * s;
+    if (nll) nll[row] = n;
+    if (soft) soft[row] = s;
+    if (kl) kl[row] = k;
+    if (lse_out) lse_out[row] = lse;
+  }
+}
+
+// Any V, any stride, any alignment: an online (max, sum exp) sweep that also forms Q and sum q z, then a second sweep over
+// both rows (from L2 / the Infinity Cache where they still are) for the KL terms and the gradient.  Every element is read
+// and written by the same thread, so the in-place form needs no ordering beyond the barriers of the reductions.
+constexpr int SOFT_TPB = 1024;
+__global__ __launch_bounds__(SOFT_TPB) void ce_soft_kernel(const float* logits, long ld, const float* __restrict__ logq, long ldq,
+                                                           const int64_t* __restrict__ tgt, float lambda, float* __restrict__ loss,
+                                                           float* __restrict__ nll, float* __restrict__ soft,
+                                                           float* __restrict__ kl, float* __restrict__ lse_out, float* dlogits,
+                                                           float gscale, int V, int vec) {
+  __shared__ float red[3][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  const float* y = logq + row * ldq;
+  float m = -INFINITY, l = 0.f, Q = 0.f, qz = 0.f;
+  const int V4 = vec ? (V & ~3) : 0;
+  for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + j), u = *reinterpret_cast<const float4*>(y + j);
+    const float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+    if (mx > m) { l *= __expf(m - mx); m = mx; }
+    if (m > -INFINITY) l += __expf(v.x - m) + __expf(v.y - m) + __expf(v.z - m) + __expf(v.w - m);
+    const float q0 = __expf(u.x), q1 = __expf(u.y), q2 = __expf(u.z), q3 = __expf(u.w);
+    Q += (q0 + q1) + (q2 + q3);
+    qz += ((q0 > 0.f ? q0 * v.x : 0.f) + (q1 > 0.f ? q1 * v.y : 0.f)) + ((q2 > 0.f ? q2 * v.z : 0.f) + (q3 > 0.f ? q3 * v.w : 0.f));
+  }
+  for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) {
+    const float v = x[j], q = __expf(y[j]);
+    if (v > m) { l *= __expf(m - v); m = v; }
+    if (m > -INFINITY) l += __expf(v - m);
+    Q += q;
+    qz += q > 0.f ? q * v : 0.f;
+  }
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // read before any in-place gradient write (block_max has barriers)
+  const float M_ = row_max(m, red[0]);
+  l = m == -INFINITY ? 0.f : l * __expf(m - M_);
+  row_sum3(l, Q, qz, red);
+  const float lse = M_ + __logf(l);
+  const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
+  float* d = dlogits ? dlogits + row * ld : nullptr;
+  float k = 0.f;
+  for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + j), u = *reinterpret_cast<const float4*>(y + j);
+    float4 g;
+    k += (soft_elem(v.x, u.x, lse, c, g.x) + soft_elem(v.y, u.y, lse, c, g.y)) +
+         (soft_elem(v.z, u.z, lse, c, g.z) + soft_elem(v.w, u.w, lse, c, g.w));
+    if (d) {
+      if (valid && t >= j && t < j + 4) {
+        if (t == j) g.x -= c.t; else if (t == j + 1) g.y -= c.t; else if (t == j + 2) g.z -= c.t; else g.w -= c.t;
+      }
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+  }
+  for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) {
+    float g;
+    k += soft_elem(x[j], y[j], lse, c, g);
+    if (d) d[j] = (valid && j == t) ? g - c.t : g;
+  }
+  k = row_sum(k, red[0]);
+  if (threadIdx.x == 0) {
+    const float n = valid ? lse - xt : 0.f, s = Q * lse - qz;
+    loss[row] = (1.f - lambda) * n + lambda * s;
+    if (nll) nll[row] = n;
+    if (soft) soft[row] = s;
+    if (kl) kl[row] = k;
+    if (lse_out) lse_out[row] = lse;
+  }
+}
+
+// deterministic single-block sum: out += sum(x[0..n))  (the fixed-order loss_sum of blm_ce_fwd_bwd)
+__global__ __launch_bounds__(1024) void soft_sum_kernel(const float* __restrict__ x, long n, float* out) {
+  __shared__ float red[16];
+  float a = 0.f;
+  for (long i = threadIdx.x; i < n; i += 1024) a += x[i];
+  const float t = block_sum<16>(a, red);
+  if (threadIdx.x == 0) out[0] += t;
+}
+
+}  // namespace blm
+
+using namespace blm;
+#define ST static_cast<hipStream_t>(stream)
+
+extern "C" int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                                   float* loss, float* nll, float* soft, float* kl, float* lse, float* loss_sum, float* dlogits,
+                                   float grad_scale, int M, int V, void* stream) {
+  if (!logits || !logq || !tgt || !loss) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: logits, logq, tgt and loss are required");
+  if (M < 0 || V <= 0) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: M = %d, V = %d: M >= 0 and V > 0 expected", M, V);
+  if (ld < V || ldq < V || !extents_ok({M, ld}) || !extents_ok({M, ldq}))
+    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: row strides ld = %lld, ldq = %lld must be >= V = %d (and M x stride an addressable extent)",
+                    (long long)ld, (long long)ldq, V);
+  if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: lambda = %g outside [0, 1]", (double)lambda);
+  if (M == 0) return BLM_OK;
+  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), q0 = reinterpret_cast<uintptr_t>(logq), d0 = reinterpret_cast<uintptr_t>(dlogits);
+  if (dlogits) {  // the gradient may be written over the logits it is the gradient of, element for element, and over nothing else read here
+    const uintptr_t zn = ((uintptr_t)(M - 1) * (uintptr_t)ld + (uintptr_t)V) * 4, qn = ((uintptr_t)(M - 1) * (uintptr_t)ldq + (uintptr_t)V) * 4;
+    if (d0 < q0 + qn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: dlogits overlaps logq");
+    if (d0 != z0 && d0 < z0 + zn && z0 < d0 + zn)
+      return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: dlogits overlaps logits without being logits itself (in place means dlogits == logits)");
+  }
+  const bool vec = ((ld & 3) == 0) && ((ldq & 3) == 0) && (((z0 | q0 | d0) & 15) == 0);
+  if (vec && V >= 4 && V <= 4096 * 3)
+    hipLaunchKernelGGL(ce_soft_row_kernel<3>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
+                       lse, dlogits, grad_scale, V);
+  else if (vec && V <= 4096 * 9)
+    hipLaunchKernelGGL(ce_soft_row_kernel<9>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
+                       lse, dlogits, grad_scale, V);
+  else
+    hipLaunchKernelGGL(ce_soft_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
+                       lse, dlogits, grad_scale, V, vec ? 1 : 0);
+  BLM_HIP(hipGetLastError());
+  if (loss_sum) {
+    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
+    BLM_HIP(hipGetLastError());
+  }
+  return BLM_OK;
+}

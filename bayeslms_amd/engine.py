@@ -595,6 +595,7 @@ class Trainer:
         model.set_seed(seed)
         self.fused_kl = fused_kl
         self.kl_layers = self._find_kl_layers()
+        self.last_soft = None  # SoftStats of device scalars: the last distillation step's mean nll, soft loss and KL (step(soft=...))
 
     def _find_kl_layers(self):
         from .model import BayesLinear
@@ -605,10 +606,16 @@ class Trainer:
         self.lr = lr
         self.first = True
 
-    def step(self, data, targets, hidden=None, kl_fn=None, philox_step=None):
+    def step(self, data, targets, hidden=None, kl_fn=None, philox_step=None, soft=None):
         """-> (loss tensor, kl tensor, new hidden).  ``kl_fn(model)`` returns the KL term train.py
         would add for this configuration (train.py:335-399), or None.  ``philox_step`` overrides the
-        noise / dropout stream index (default: the optimisation step count)."""
+        noise / dropout stream index (default: the optimisation step count).  ``soft`` = (teacher_logp, weight): distillation --
+        ops.cross_entropy_soft against the teacher's (T * B, V) log-probabilities takes the place of the hard-label cross entropy
+        (weight 0 is that loss), everything else is the same step; the step's mean hard NLL, soft loss and KL(teacher || student)
+        stay on the device as ``self.last_soft``.  Single process only."""
+        if soft is not None and self.world > 1:
+            raise ops.BayesLMError("Trainer.step: soft targets with world = %d: data-parallel distillation is not built (the teacher's "
+                                   "rows would have to follow each rank's batch columns); train the student in one process" % self.world)
         m = self.model
         m.train()
         m.set_step(self.step_no if philox_step is None else philox_step)
@@ -625,7 +632,11 @@ class Trainer:
         else:
             out, hidden = m(data, hidden)
         V = out.shape[-1]
-        mle, _ = ops.cross_entropy(out.view(-1, V), targets, unit_grad=True)
+        if soft is None:
+            mle, _ = ops.cross_entropy(out.view(-1, V), targets, unit_grad=True)
+        else:
+            mle, parts = ops.cross_entropy_soft(out.view(-1, V), targets, soft[0], soft[1], unit_grad=True)
+            self.last_soft = ops.SoftStats(parts.nll.mean(), parts.soft.mean(), parts.kl.mean())  # no host synchronisation
         kl = None
         if kl_fn is not None:
             kl = kl_fn(m) * self.kl_scale

@@ -29,7 +29,7 @@ from . import _lib as L
 from ._lib import BayesLMError, calls, dev_tensor, ptr, stream
 
 __all__ = ["Drop", "NoiseSpec", "LrtNoise", "ResidualLink", "linear", "bayes_linear", "bayes_linear_lrt", "ffn", "ffn_lrt", "ffn_gp", "attention", "attention_qkv", "add_dropout_ln",
-           "embed", "add_pe", "dropout", "cross_entropy", "kl_mean", "philox_normal", "sample_weight", "sampled", "lstm_layer", "lstm_stack2", "lstm_stack2_ok", "set_lstm_wavefront", "lstm_cell", "gp_mix", "add_rowvec",
+           "embed", "add_pe", "dropout", "cross_entropy", "cross_entropy_soft", "SoftStats", "kl_mean", "philox_normal", "sample_weight", "sampled", "lstm_layer", "lstm_stack2", "lstm_stack2_ok", "set_lstm_wavefront", "lstm_cell", "gp_mix", "add_rowvec",
            "clip_sgd", "gemm", "PtrTable", "set_grad_ready_hook", "set_embed_grad_sink", "rows_gather_add", "KernelTimer", "set_kernel_timer"]
 
 
@@ -1523,6 +1523,101 @@ def cross_entropy(logits, targets, unit_grad=False):
     if type(logits) is not torch.Tensor:
         logits = logits.as_subclass(torch.Tensor)  # model outputs are `Logits` in grad mode (below); the op wants the plain tensor
     return _CrossEntropy.apply(logits, targets, unit_grad)
+
+
+# ----------------------------------------------------------------------------
+# distillation: cross entropy against a teacher's dense distribution, mixed with the hard-label one  (blm_ce_soft_fwd_bwd)
+# ----------------------------------------------------------------------------
+class SoftStats(NamedTuple):
+    """The per-token parts of ops.cross_entropy_soft (include/bayeslm.h, blm_ce_soft_fwd_bwd)."""
+    nll: torch.Tensor   # (M,) hard-label NLL; 0 where the target is outside [0, V)
+    soft: torch.Tensor  # (M,) cross entropy of the student under the teacher's distribution q
+    kl: torch.Tensor    # (M,) KL(q || student), summed term by term
+
+
+class _CrossEntropySoft(torch.autograd.Function):
+    """As _CrossEntropy, for loss = mean_m (1 - weight) nll[m] + weight soft[m].  unit_grad=True (the trainer's case): the forward
+    pass over the logits overwrites them in place with the gradient at scale 1 / M, and backward returns that buffer untouched.
+    unit_grad=False: the same kernel writes the gradient into a buffer of its own in forward, and backward multiplies it by the
+    upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, teacher_logp, weight, unit_grad):
+        V = logits.shape[-1]
+        whole = logits
+        logits, ld = _rows2d(logits, V, "logits")  # rows padded to 4 floats (odd vocabulary, ops._Linear) are taken as they are
+        if whole.data_ptr() != logits.data_ptr():
+            whole = logits.view(whole.shape)
+        targets = dev_tensor(targets, "targets", torch.int64)
+        M = logits.numel() // V
+        if targets.numel() != M:
+            raise BayesLMError("cross_entropy_soft: %d targets for %d rows" % (targets.numel(), M))
+        if M == 0:
+            raise BayesLMError("cross_entropy_soft: no rows (the mean over zero tokens is undefined; torch returns nan here)")
+        if teacher_logp.dim() != 2 or tuple(teacher_logp.shape) != (M, V):
+            raise BayesLMError("cross_entropy_soft: teacher_logp %s against %d rows of %d logits: an (M, V) matrix over the same "
+                               "vocabulary expected" % (tuple(teacher_logp.shape), M, V))
+        logq, ldq = _rows2d(teacher_logp, V, "teacher_logp")  # linear_mc_logprobs' padded rows likewise
+        dev = logits.device
+        rows, nll, soft, kl = (torch.empty(M, device=dev, dtype=torch.float32) for _ in range(4))
+        loss = torch.zeros((), device=dev, dtype=torch.float32)
+        grad_mode = ctx.needs_input_grad[0]  # forward itself runs with grad mode off
+        fuse = grad_mode and unit_grad
+        grad = None
+        if fuse:
+            grad = logits
+        elif grad_mode:  # rows strided as the logits' (one stride serves both in the kernel)
+            if ld == V:
+                grad = torch.empty_like(logits)
+            elif ld == (V + 3) // 4 * 4:  # registered as this module's: ops._Linear may run its padded backward on it
+                grad = _padded_rows((M,), V, dev)[0]
+            else:
+                grad = torch.empty(M, ld, device=dev, dtype=torch.float32)[:, :V]
+        L.require_gfx950()
+        calls().blm_ce_soft_fwd_bwd(ptr(logits), ld, ptr(logq), ldq, ptr(targets), float(weight), ptr(rows), ptr(nll), ptr(soft), ptr(kl),
+                                    None, ptr(loss), ptr(grad), 1.0 / M, M, V, stream())
+        if fuse:  # the buffer now holds the gradient: any other autograd consumer of the logits must fail, not read it
+            torch.autograd.graph.increment_version(whole)
+        ctx.meta = (whole if fuse else grad.view(whole.shape) if grad is not None else None, fuse)
+        ctx.mark_non_differentiable(nll, soft, kl)
+        ctx.set_materialize_grads(False)
+        return loss / M, nll, soft, kl
+
+    @staticmethod
+    def backward(ctx, g, _g_nll, _g_soft, _g_kl):
+        grad, fuse = ctx.meta
+        if g is None:
+            return None, None, None, None, None
+        if fuse:
+            return grad, None, None, None, None
+        if getattr(ctx, "spent", False):  # the buffer was scaled by the first backward's upstream gradient
+            raise BayesLMError("cross_entropy_soft: backward ran already and scaled the gradient buffer by its upstream gradient; a "
+                               "second backward over a retained graph needs a second forward")
+        ctx.spent = True
+        grad.mul_(_f32(g.reshape(()), "g"))
+        return grad, None, None, None, None
+
+
+def cross_entropy_soft(logits, targets, teacher_logp, weight, unit_grad=False):
+    """Distillation loss -> (mean over the M rows of (1 - weight) nll + weight soft, SoftStats(nll, soft, kl)): ``soft`` is the
+    cross entropy of softmax(logits) under the teacher's distribution exp(teacher_logp), ``nll`` the hard-label one against
+    ``targets``, ``kl`` = KL(teacher || student) per row; definitions in include/bayeslm.h, blm_ce_soft_fwd_bwd -- one pass
+    over both matrices, the gradient included.  ``teacher_logp``: (M, V) fp32 log-probabilities on the GPU, no gradient (the
+    padded rows of ops.linear_mc_logprobs are read in place; -inf entries are zeros of the teacher).  ``weight``: a float in
+    [0, 1]; 0 is ops.cross_entropy's loss.  As there, in grad mode with ``unit_grad=True`` (the trainers' contract: the loss
+    enters the objective with coefficient exactly 1) the logits buffer is CONSUMED: it is overwritten with the gradient and
+    its version counter is bumped; with ``unit_grad=False`` the logits stay and the gradient has its own buffer."""
+    if type(logits) is not torch.Tensor:
+        logits = logits.as_subclass(torch.Tensor)  # model outputs are `Logits` in grad mode (below); the op wants the plain tensor
+    if not torch.is_tensor(teacher_logp):
+        raise BayesLMError("cross_entropy_soft: teacher_logp must be a tensor, got %s" % type(teacher_logp).__name__)
+    if teacher_logp.requires_grad:
+        raise BayesLMError("cross_entropy_soft: teacher_logp requires grad; the teacher is a constant of the loss (detach it: "
+                           "no gradient is formed for it)")
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0:
+        raise BayesLMError("cross_entropy_soft: weight must be a float in [0, 1], got %r" % (weight,))
+    loss, nll, soft, kl = _CrossEntropySoft.apply(logits, targets, teacher_logp, float(weight), unit_grad)
+    return loss, SoftStats(nll, soft, kl)
 
 
 class Logits(torch.Tensor):

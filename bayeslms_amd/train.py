@@ -93,7 +93,71 @@ def build_parser():
     p.add_argument('--test-mc-samples', type=int, default=0, metavar='S',
                    help='new, optional (with --test-report): S >= 2 reports the test set under the average of S Monte-Carlo weight '
                         'samples keyed by --seed (0: mean weights)')
+    p.add_argument('--distill-from', type=str, default='', metavar='PATH',
+                   help='new, optional: train this model as the STUDENT of the frozen model saved at PATH (a state_dict, as --save writes '
+                        'it): every batch the teacher\'s next-word distribution is a dense target of the loss (DESIGN.md section 7, '
+                        'bayeslms_amd/distill.py).  Validation, checkpoints and the test pass stay hard-label.  Single process only')
+    p.add_argument('--distill-weight', type=float, default=None, metavar='L',
+                   help='new, optional (with --distill-from): loss = (1 - L) hard-label cross entropy + L cross entropy against the '
+                        'teacher, L in [0, 1] (default 0.5)')
+    p.add_argument('--distill-mc-samples', type=int, default=0, metavar='S',
+                   help='new, optional (with --distill-from): S in 2..64 distils the average of S Monte-Carlo weight samples of the '
+                        'teacher (0: the teacher at mean weights)')
+    p.add_argument('--distill-mc-seed', type=int, default=1111, metavar='N',
+                   help='new, optional (with --distill-from): the key of the teacher\'s weight samples')
+    p.add_argument('--distill-teacher-args', type=str, default=None, metavar='"..."',
+                   help='new, optional (with --distill-from): the flags that shape the TEACHER, as one string of this command line\'s '
+                        'own flags (a checkpoint holds weights, not an architecture).  Only the model-shaping ones are read: %s.  '
+                        'Default: the student\'s own' % ", ".join("--" + f for f in TEACHER_FLAGS))
     return p
+
+
+# the flags build_model reads: what --distill-teacher-args may set for the teacher
+TEACHER_FLAGS = ("model", "emsize", "nhid", "nlayers", "nhead", "uncertainty", "T_bayes_pos", "L_bayes_pos", "L_gauss_pos", "L_v_pos",
+                 "T_gauss_pos", "T_v_pos", "dropout", "tied")
+
+
+def check_distill_args(args, world):
+    """The --distill-* flags, refused before anything is loaded -> the teacher's model-shaping flags (a namespace), or None."""
+    if not args.distill_from:
+        for flag, given in (("--distill-weight", args.distill_weight is not None), ("--distill-mc-samples", args.distill_mc_samples != 0),
+                            ("--distill-teacher-args", args.distill_teacher_args is not None)):
+            if given:
+                raise SystemExit("%s needs --distill-from" % flag)
+        return None
+    if args.distill_weight is None:
+        args.distill_weight = 0.5
+    if not 0.0 <= args.distill_weight <= 1.0:
+        raise SystemExit("--distill-weight must lie in [0, 1] (got %r)" % args.distill_weight)
+    S = args.distill_mc_samples
+    if S < 0 or S == 1 or S > 64:
+        raise SystemExit("--distill-mc-samples must be 0 (mean weights) or lie in 2..64, the most one decoder launch averages (got %d)" % S)
+    if world > 1:
+        raise SystemExit("--distill-from runs in a single process: data-parallel distillation is not built (world size %d)" % world)
+    if (args.noise_source or os.environ.get("BLM_NOISE_SOURCE", "philox")) == "torch":
+        raise SystemExit("--distill-from with --noise-source torch: the parity mode follows the reference's run, which has no teacher")
+    shape = argparse.Namespace(**{f: getattr(args, f) for f in TEACHER_FLAGS})
+    if args.distill_teacher_args is not None:
+        import shlex
+        theirs = build_parser().parse_args(shlex.split(args.distill_teacher_args))
+        shape = argparse.Namespace(**{f: getattr(theirs, f) for f in TEACHER_FLAGS})
+    return shape
+
+
+def load_teacher_state(args):
+    """The teacher's state_dict (on the host) once its vocabulary has been checked against the corpus's words.txt -- before any
+    device is touched."""
+    from .data import Dictionary
+    words = Dictionary()
+    words.read_vocab(os.path.join(args.data, "words.txt"))
+    sd = torch.load(args.distill_from, map_location='cpu')
+    rows = [v.shape[0] for k, v in sd.items() if k in ("decoder.weight", "decoder.bias")] if isinstance(sd, dict) else []
+    if not rows:
+        raise SystemExit("--distill-from %s: not a state_dict of one of this package's language models (no decoder.weight)" % args.distill_from)
+    if rows[0] != len(words):
+        raise SystemExit("--distill-from %s: the teacher's vocabulary has %d words, the corpus at %s has %d: a teacher's distribution "
+                         "must be over the student's words" % (args.distill_from, rows[0], args.data, len(words)))
+    return sd
 
 
 def check_report_args(args, world):
@@ -243,6 +307,8 @@ def main(argv=None, history=None):
     history.update({"interval_loss": [], "valid_loss": [], "halved_epochs": [], "test_loss": None, "ms_per_batch": []})
     world = int(os.environ.get("WORLD_SIZE", "1"))
     check_report_args(args, world)
+    teacher_shape = check_distill_args(args, world)
+    teacher_sd = load_teacher_state(args) if teacher_shape is not None else None
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     is_main = rank == 0
@@ -315,6 +381,25 @@ def main(argv=None, history=None):
     say('Model total parameters: {}'.format(total_params))
     say(str(model.transformerlayers if args.model == 'Transformer' else model.rnn))
 
+    teacher = None
+    if teacher_shape is not None:
+        from . import distill
+        with torch.random.fork_rng(devices=[]):  # the constructors draw from torch's generator: the student's run does not see it
+            teacher_model = build_model(teacher_shape, ntokens)
+        try:
+            teacher_model.load_state_dict(teacher_sd)
+        except RuntimeError as e:
+            raise SystemExit("--distill-from %s does not fit the teacher that --distill-teacher-args (default: this run's own flags) "
+                             "describes: %s" % (args.distill_from, e))
+        teacher_model = teacher_model.to(device).requires_grad_(False)
+        try:
+            teacher = distill.Teacher(teacher_model, args.distill_mc_samples, args.distill_mc_seed)
+        except ops.BayesLMError as e:
+            raise SystemExit("--distill-from %s: %s" % (args.distill_from, e))
+        history.update({"interval_soft": [], "interval_kd_kl": []})
+        say("distilling from %s (%s), weight %g, %s" % (args.distill_from, type(teacher_model).__name__, args.distill_weight,
+                                                       "%d Monte-Carlo samples" % teacher.S if teacher.S else "mean weights"))
+
     kl_fn = kl_selector(args)
     kl_scale = float(args.seq_len) / float(len(train_data))  # KL / len(train_data) * seq_len (train.py:338)
     trainer = engine.Trainer(model, lr=args.lr, clip=args.clip, momentum=0.9, kl_scale=kl_scale, seed=args.seed,
@@ -325,11 +410,19 @@ def main(argv=None, history=None):
         total_loss = 0.
         start = time.time()
         hidden = model.init_hidden(train_data.size(1)) if is_rnn else None
+        total_soft = total_kd = 0.
+        if teacher is not None:
+            teacher.reset(train_data.size(1))
         for batch, i in enumerate(range(0, train_data.size(0) - 1, args.seq_len)):
             data, targets = D.get_batch(train_data, i, args.seq_len)
             if is_rnn:
                 hidden = repackage_hidden(hidden)
-            loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn)
+            if teacher is None:
+                loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn)
+            else:
+                logq, _ = teacher.logprobs(data)
+                loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn, soft=(logq, args.distill_weight))
+                total_soft, total_kd = total_soft + trainer.last_soft.soft, total_kd + trainer.last_soft.kl
             total_loss = total_loss + loss  # stays on the device: one host sync per log interval (train.py:422 syncs per step)
             if batch % args.log_interval == 0 and batch > 0:
                 if world > 1:  # the mean over the GLOBAL batch, as the single-process log line prints it
@@ -342,10 +435,16 @@ def main(argv=None, history=None):
                 history["interval_loss"].append(cur)
                 elapsed = time.time() - start
                 history["ms_per_batch"].append(elapsed * 1000 / args.log_interval)
-                say('| epoch {:3d} | {:5d}/{:5d} batches | lr {:02.3f} | ms/batch {:5.2f} | loss {:5.2f} | '
-                    'kl_loss {:5.4} | ppl {:8.2f}'.format(epoch, batch, len(train_data) // args.seq_len, lr,
-                                                          elapsed * 1000 / args.log_interval, cur,
-                                                          float(kl) if kl is not None else 0., math.exp(min(cur, 80.0))))
+                line = ('| epoch {:3d} | {:5d}/{:5d} batches | lr {:02.3f} | ms/batch {:5.2f} | loss {:5.2f} | '
+                        'kl_loss {:5.4} | ppl {:8.2f}'.format(epoch, batch, len(train_data) // args.seq_len, lr,
+                                                              elapsed * 1000 / args.log_interval, cur,
+                                                              float(kl) if kl is not None else 0., math.exp(min(cur, 80.0))))
+                if teacher is not None:  # `loss` above is the mixed objective; these are its soft part and KL(teacher || student)
+                    history["interval_soft"].append(float(total_soft) / args.log_interval)
+                    history["interval_kd_kl"].append(float(total_kd) / args.log_interval)
+                    line += ' | soft {:5.2f} | kd_kl {:5.4f}'.format(history["interval_soft"][-1], history["interval_kd_kl"][-1])
+                    total_soft = total_kd = 0.
+                say(line)
                 total_loss = 0.
                 start = time.time()
 

@@ -651,6 +651,28 @@ int blm_ce_bwd(const float* logits, int64_t ld, const int64_t* tgt, const float*
 int blm_ce_interp_fwd(const float* logits_a, const float* logits_b, int64_t ld, float alpha, const int64_t* tgt,
                       float* nll, int M, int V, void* stream);
 
+/* Distillation loss (engine only: the reference trains on hard labels alone and has no counterpart): cross entropy of
+ * softmax(logits) against a DENSE target distribution q = exp(logq) -- a teacher's log-probabilities, e.g. the log pbar of
+ * blm_linear_mc_logprobs ("Bayesian dark knowledge": the student learns the posterior predictive) -- interpolated with the
+ * hard-label cross entropy, and its gradient, in one pass.  logits (M, V) row stride ld, logq (M, V) row stride ldq; an entry
+ * of logq may be -inf (q = 0).  Per row, with z = logits[m,:], l = logq[m,:], Q = sum_v q_v (carried, not assumed 1: a teacher
+ * row with masked columns stays exact), lse = logsumexp_v z_v, p_v = exp(z_v - lse), t = tgt[m], valid = 0 <= t < V:
+ *   nll[m]  = valid ? lse - z_t : 0                          (as blm_ce_fwd_bwd)
+ *   soft[m] = Q lse - sum_{q_v > 0} q_v z_v                   (cross entropy of p under q)
+ *   kl[m]   = sum_{q_v > 0} q_v (l_v - z_v + lse)             (KL(q || p) for Q = 1; summed term by term, never as soft - H[q])
+ *   loss[m] = (1 - lambda) nll[m] + lambda soft[m]
+ *   dlogits[m,v] = ((1 - lambda) valid (p_v - [v = t]) + lambda (Q p_v - q_v)) grad_scale
+ * which is the gradient of grad_scale * sum_m loss[m]; a row without a valid hard target still gets its soft part.
+ * loss (M) is required; nll, soft, kl, lse (M each) are optional; loss_sum (optional) += sum_m loss[m], added in a fixed order;
+ * dlogits (optional, row stride ld) may be logits itself (in place).  BLM_ERR_INVALID, before any launch: a NULL required
+ * pointer, ld < V or ldq < V, M < 0 or V <= 0, lambda outside [0, 1] or NaN, dlogits overlapping logq, or overlapping logits
+ * other than exactly in place.  M == 0 is a no-op.  One workgroup per row: for V <= 36864 with both strides multiples of 4 and
+ * 16-byte aligned bases both rows are held in registers and each is read from memory once; otherwise a guarded two-sweep
+ * form.  No floating-point atomics: every run gives the same bits. */
+int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                        float* loss, float* nll, float* soft, float* kl, float* lse, float* loss_sum, float* dlogits,
+                        float grad_scale, int M, int V, void* stream);
+
 
 /* dcoef[i,n] += sum_m g[m,n] * act_i(z[m,n]), i = tanh, sigmoid, relu, gelu: gradient of the GPNN
  * mixture coefficients (autograd of model.py:1885-1899). */
