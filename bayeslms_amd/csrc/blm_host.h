@@ -30,6 +30,9 @@ inline bool extents_ok(std::initializer_list<long> dims) {
   }
   return true;
 }
+// blm_colsum2 with a factor on the sums (out and, if given, out2 alike): the guarded-loader route of blm_gemm's colsum_a, whose
+// sums carry the call's alpha -- the only caller with scale != 1, and it passes no out2
+int colsum_scaled(const float* x, int64_t ld, float* out, float* out2, int M, int N, int accumulate, float scale, void* stream);
 }  // namespace blm
 
 // Kernel-selection options (blm_set_option / blm_get_option, include/bayeslm.h): every switch that picks between two BUILT

@@ -533,7 +533,7 @@ __global__ __launch_bounds__(1024) void sum_kernel(const float* __restrict__ x, 
 // ------------------------------------------------------------------ column sums (bias gradients)
 // block = 32 column-quads x 8 row lanes; grid.y row chunks; partials combined with float atomics.
 __global__ __launch_bounds__(TPB) void colsum_kernel(const float* __restrict__ x, long ld, float* __restrict__ out, int M,
-                                                     int N, float* __restrict__ out2 = nullptr) {
+                                                     int N, float* __restrict__ out2 = nullptr, float scale = 1.f) {
   __shared__ float4 sm[8][32];
   const int cq = threadIdx.x & 31, rl = threadIdx.x >> 5;
   const int col = (blockIdx.x * 32 + cq) * 4;
@@ -559,6 +559,7 @@ __global__ __launch_bounds__(TPB) void colsum_kernel(const float* __restrict__ x
   __syncthreads();
   if (rl == 0 && col < N) {
     for (int k = 1; k < 8; ++k) { a.x += sm[k][cq].x; a.y += sm[k][cq].y; a.z += sm[k][cq].z; a.w += sm[k][cq].w; }
+    a.x *= scale; a.y *= scale; a.z *= scale; a.w *= scale;  // 1 (exact) everywhere but blm_gemm's colsum_a with alpha != 1
     atomicAdd(out + col, a.x);
     if (col + 1 < N) atomicAdd(out + col + 1, a.y);
     if (col + 2 < N) atomicAdd(out + col + 2, a.z);
@@ -1050,7 +1051,8 @@ extern "C" int blm_gp_coef_grad(const float* g, const float* z, float* dcoef, in
   return BLM_OK;
 }
 
-extern "C" int blm_colsum2(const float* x, int64_t ld, float* out, float* out2, int M, int N, int accumulate, void* stream) {
+// blm_colsum2 with the sums scaled (blm_host.h): out (+)= scale * column sums
+int blm::colsum_scaled(const float* x, int64_t ld, float* out, float* out2, int M, int N, int accumulate, float scale, void* stream) {
   if (!x || !out || !blm::extents_ok({M, N}) || ld < N || !blm::extents_ok({M, ld}) || out == out2) return blm_fail(BLM_ERR_INVALID, "blm_colsum: bad arguments");
   if (N == 0) return BLM_OK;
   if (!accumulate) {
@@ -1061,9 +1063,13 @@ extern "C" int blm_colsum2(const float* x, int64_t ld, float* out, float* out2, 
   int gy = (M + 255) / 256;
   if (gy > 64) gy = 64;
   if (blm::option(blm::OPT_DETERMINISTIC)) gy = 1;  // one row chunk: each sum has one writer, rows added in a fixed order
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 127) / 128, gy), dim3(TPB), 0, ST, x, (long)ld, out, M, N, out2);
+  hipLaunchKernelGGL(colsum_kernel, dim3((N + 127) / 128, gy), dim3(TPB), 0, ST, x, (long)ld, out, M, N, out2, scale);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
+}
+
+extern "C" int blm_colsum2(const float* x, int64_t ld, float* out, float* out2, int M, int N, int accumulate, void* stream) {
+  return blm::colsum_scaled(x, ld, out, out2, M, N, accumulate, 1.f, stream);
 }
 
 extern "C" int blm_colsum(const float* x, int64_t ld, float* out, int M, int N, int accumulate, void* stream) {

@@ -115,7 +115,7 @@ extern "C" int blm_gemm(const blm_gemm_args* a, void* stream) {
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (p.colsum_a && !p.fast) {  // odd shapes: the guarded-loader kernel does not fuse it
-    const int rc = blm_colsum(a->A, a->lda, a->colsum_a, a->K, a->M, 1, stream);
+    const int rc = blm::colsum_scaled(a->A, a->lda, a->colsum_a, nullptr, a->K, a->M, 1, a->alpha, stream);
     if (rc) return rc;
     p.colsum_a = nullptr;
   }

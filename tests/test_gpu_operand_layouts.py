@@ -8,7 +8,9 @@ tensors, strided leaves, leaves that already hold a (possibly strided) .grad and
 must match the float64 reference within the bounds of the aligned case, or the op must raise BayesLMError before any
 launch -- never a different number.  Forward inputs and sibling gradients must come out bitwise unchanged (the documented
 consumption of the logits by ops.cross_entropy aside), and a second backward over a retained graph adds the gradient again
-or raises.
+or raises.  The feed-forward ops (ffn, ffn_bayes, ffn_gp, ffn_lrt, dropout on) accumulate some weight gradients straight into
+.grad (Case.in_place): for those weights a strided tensor, a non-leaf or a strided .grad must raise BayesLMError before any
+launch, and the tests assert that it does.
 
 Every strided or offset operand is a view into a storage at least (offset + numel) floats long, on the GPU; no operand is
 host-resident, half-width or expanded (stride 0) in a forward call."""
@@ -91,11 +93,14 @@ class Case:
     """``make(g)`` -> dict of CPU tensors (float32 operands, int64 indices); ``diff``: the names that get gradients;
     ``weights``: the weight-like names; ``fwd(ops, t)`` the GPU call; ``ref(t)`` the same operation in float64 on the CPU;
     ``unit``: the op ignores the upstream gradient's value (cross_entropy unit_grad: it must be exactly 1);
-    ``consumes``: inputs the op documents as overwritten."""
+    ``consumes``: inputs the op documents as overwritten; ``in_place``: weights whose gradient the op can only accumulate
+    straight into .grad (ops._weight(in_place=True)): anything but the caller's contiguous leaf with a contiguous .grad
+    must raise BayesLMError before any launch."""
 
-    def __init__(self, name, make, diff, fwd, ref, weights=(), tol=(1e-5, 2e-5), unit=False, consumes=(), scalar=False):
+    def __init__(self, name, make, diff, fwd, ref, weights=(), tol=(1e-5, 2e-5), unit=False, consumes=(), scalar=False, in_place=()):
         self.name, self.make, self.diff, self.fwd, self.ref = name, make, tuple(diff), fwd, ref
         self.weights, self.tol, self.unit, self.consumes, self.scalar = tuple(weights), tol, unit, tuple(consumes), scalar
+        self.in_place = tuple(in_place)
 
     def shapes(self):
         return {k: tuple(v.shape) for k, v in self.make(torch.Generator().manual_seed(0)).items()}
@@ -237,6 +242,52 @@ CASES += [
          lambda ops, t: ops.mix2(t["a"], t["b"], t["probs"], ops.Drop(0.2, 6, 7, 3, 0, 3)),
          lambda t: (t["probs"][0] * t["a"] + t["probs"][1] * t["b"]) * keep((5, 3, 32), 0.2, 6, 7, 3), weights=("probs",)),
 ]
+
+
+# the feed-forward ops with dropout on (a column window: 5 of 9 global columns from 2): the GELU and GP-mixture epilogues of the
+# first product, its backward epilogue, and the second linear plain, Bayesian (injected eps) and under local reparameterisation
+def _ffn(kind, T=6, B=5, D=32, Fd=40):
+    site = {"plain": 4, "bayes": 5, "gp": 6, "lrt": 7}[kind]
+    noise = torch.randn(T * B * D if kind == "lrt" else D * Fd, generator=torch.Generator().manual_seed(40 + site))
+
+    def make(g):
+        rn = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+        t = {"x": rn(T, B, D), "w1": rn(Fd, D) * D ** -0.5, "b1": rn(Fd) * 0.5}
+        if kind == "gp":
+            t["coef"] = torch.rand(4, Fd, generator=g) + 0.25
+        t["w2"] = rn(D, Fd) * Fd ** -0.5
+        if kind in ("plain", "gp"):
+            t["b2"] = rn(D) * 0.5
+        else:
+            t["lgstd2"] = torch.rand(D, Fd, generator=g) - 3.0
+        return t
+
+    def fwd(ops, t):
+        drop = ops.Drop(0.3, 21, site, 3, 2, 9)
+        if kind == "plain":
+            return ops.ffn(t["x"], t["w1"], t["b1"], t["w2"], t["b2"], drop=drop)
+        if kind == "gp":
+            return ops.ffn_gp(t["x"], t["w1"], t["b1"], t["coef"], t["w2"], t["b2"], drop=drop)
+        if kind == "lrt":
+            return ops.ffn_lrt(t["x"], t["w1"], t["b1"], t["w2"], t["lgstd2"], ops.LrtNoise(eps=noise.view(T * B, D).to(DEV)), drop=drop)
+        return ops.ffn(t["x"], t["w1"], t["b1"], t["w2"], None, t["lgstd2"], ops.NoiseSpec(eps=noise.view(D, Fd).to(DEV)), drop=drop)
+
+    def ref(t):
+        z = F.linear(t["x"], t["w1"], t["b1"])
+        h = O.gp_mixture(z, t["coef"], ("tanh", "sigmoid", "relu", "gelu")) if kind == "gp" else F.gelu(z)
+        h = h * keep((T, 9, Fd), 0.3, 21, site, 3)[:, 2:2 + B]
+        if kind in ("plain", "gp"):
+            return F.linear(h, t["w2"], t["b2"])
+        if kind == "lrt":
+            return F.linear(h, t["w2"]) + torch.sqrt(F.linear(h * h, torch.exp(2 * t["lgstd2"]))) * noise.double().view(T, B, D)
+        return F.linear(h, t["w2"] + torch.exp(t["lgstd2"]) * noise.double().view(D, Fd))
+    names = list(make(torch.Generator().manual_seed(0)))
+    in_place = {"plain": ("w1", "b1", "w2", "b2"), "bayes": ("w1", "b1", "w2", "lgstd2"), "gp": ("w2", "b2"), "lrt": ("w1", "b1")}[kind]
+    return Case({"plain": "ffn", "bayes": "ffn_bayes", "gp": "ffn_gp", "lrt": "ffn_lrt"}[kind], make, names, fwd, ref,
+                weights=names[1:], in_place=in_place)
+
+
+CASES += [_ffn("plain"), _ffn("bayes"), _ffn("gp"), _ffn("lrt")]
 BY_NAME = {c.name: c for c in CASES}
 
 
@@ -292,6 +343,12 @@ def test_operand_layout(name, arg, layout):
     cpu = _inputs(case, 1)
     t = _gpu_leaves(case, cpu, {arg: LAYOUTS[layout]})
     before = {k: v.detach().clone() for k, v in t.items()}
+    if layout == "strided" and arg in case.in_place:  # a gradient that can only go straight into .grad: refused, nothing launched
+        with pytest.raises(BayesLMError()):
+            case.fwd(ops, t)
+        for k, v in before.items():  # nothing was launched: no input was written
+            assert torch.equal(t[k].detach(), v), "%s: input %s changed by a refused call" % (name, k)
+        return
     try:
         out = case.fwd(ops, t)
     except BayesLMError():
@@ -387,6 +444,15 @@ def test_weight_gradient_routing(name, wname, mode):
     call = dict(t)
     if mode == "nonleaf":
         call[wname] = leaf * 1.0
+    if wname in case.in_place and mode in ("nonleaf", "strided_leaf", "strided_grad"):
+        before = {k: v.detach().clone() for k, v in call.items()}
+        held = None if leaf.grad is None else leaf.grad.clone()
+        with pytest.raises(BayesLMError()):
+            case.fwd(ops, call)
+        for k, v in before.items():  # nothing was launched: no input and no held gradient was written
+            assert torch.equal(call[k].detach(), v), "%s: input %s changed by a refused call" % (name, k)
+        assert held is None or torch.equal(leaf.grad, held)
+        return
     out = case.fwd(ops, call)
     g = torch.Generator().manual_seed(7)
     go = _go_for(case, out, g)
