@@ -8,6 +8,7 @@
 //   loss = (1 - lambda) nll + lambda soft
 //   dz_v = ((1 - lambda) valid (p_v - [v = t]) + lambda (Q p_v - q_v)) grad_scale
 // One workgroup per row, every sum in a fixed order, no atomics: the same bits from every run.
+// blm_ce_soft_topk_fwd_bwd (below): the same loss against a SPARSE teacher row, the K best entries per token.
 #include "blm_device.h"
 #include "blm_host.h"
 
@@ -223,6 +224,164 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_soft_kernel(const float* logits, 
   }
 }
 
+// ---- top-k teacher targets: the same loss against a SPARSE row per token, K (id, logq) pairs (blm_ce_soft_topk_fwd_bwd) ----
+// Thread j < K owns entry j of its row for the whole kernel: it reads the pair once, gathers z[ids_j] BEFORE the first
+// barrier (so before any in-place gradient store of any thread), contributes q_j, q_j z_j and the KL term to the row's sums,
+// and -- behind a barrier that follows the dense sweep's stores -- OVERWRITES column ids_j with the full gradient of that
+// column, formed from the values it holds: Q p - q_j and, where ids_j is also the target, the one-hot term too.  No thread
+// reads a gradient back, no atomics; with duplicate live ids the last writer wins (unspecified, in bounds).
+struct TopkEntry {
+  unsigned id;  // 0xFFFFFFFF: not live
+  float l, q, z;
+};
+__device__ __forceinline__ TopkEntry topk_entry(const int* __restrict__ ids, const float* __restrict__ logq, const float* x, int K, int V) {
+  TopkEntry e = {0xFFFFFFFFu, 0.f, 0.f, 0.f};
+  if ((int)threadIdx.x < K) {
+    const int id = ids[threadIdx.x];
+    if (id >= 0 && id < V) {
+      e.id = (unsigned)id;
+      e.l = logq[threadIdx.x];
+      e.q = __expf(e.l);
+      e.z = x[id];
+    }
+  }
+  return e;
+}
+__device__ __forceinline__ float topk_kl(const TopkEntry& e, float lse) { return e.q > 0.f ? e.q * (e.l - (e.z - lse)) : 0.f; }
+__device__ __forceinline__ void topk_fix(const TopkEntry& e, float lse, const SoftCoef& c, unsigned tu, float* d) {
+  if (e.id != 0xFFFFFFFFu) d[e.id] = (c.p * __expf(e.z - lse) - c.q * e.q) - (tu == e.id ? c.t : 0.f);
+}
+__device__ __forceinline__ void topk_finish(long row, bool valid, float xt, float lse, float Q, float qz, float k, float lambda,
+                                            float* __restrict__ loss, float* __restrict__ nll, float* __restrict__ soft,
+                                            float* __restrict__ kl, float* __restrict__ lse_out) {
+  const float n = valid ? lse - xt : 0.f, s = Q * lse - qz;
+  loss[row] = (1.f - lambda) * n + lambda * s;
+  if (nll) nll[row] = n;
+  if (soft) soft[row] = s;
+  if (kl) kl[row] = k;
+  if (lse_out) lse_out[row] = lse;
+}
+
+// The logit row held in registers as in ce_soft_row_kernel, and no second dense row beside it: NV = 3 / 9 / 16 as the hard-label
+// ce_row_kernel, V <= 65536.  Requires V >= 4, ld a multiple of 4 and 16-byte aligned logits / dlogits (the entry point
+// selects); ids / logq rows are read one element per thread and need no alignment.  logits / dlogits may alias.
+template <int NV>
+__global__ __launch_bounds__(1024) void ce_topk_row_kernel(const float* logits, long ld, const int* __restrict__ ids,
+                                                           const float* __restrict__ logq, long ldk, int K,
+                                                           const int64_t* __restrict__ tgt, float lambda, float* __restrict__ loss,
+                                                           float* __restrict__ nll, float* __restrict__ soft,
+                                                           float* __restrict__ kl, float* __restrict__ lse_out, float* dlogits,
+                                                           float gscale, int V) {
+  __shared__ float red[3][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  const unsigned t0 = threadIdx.x * 4u, Vu = (unsigned)V;
+  float4 v[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {  // whole quads only; a quad outside the row reads quad 0 and is skipped wherever it is used
+    const unsigned j = t0 + 4096u * i;
+    v[i] = *reinterpret_cast<const float4*>(x + (j + 3 < Vu ? j : 0u));
+  }
+  const unsigned je = (Vu & ~3u) + threadIdx.x;  // this thread's column behind the whole quads, if je < V
+  const bool extra = je < Vu;
+  const float ze = extra ? x[je] : -INFINITY;
+  const TopkEntry e = topk_entry(ids + row * ldk, logq + row * ldk, x, K, V);
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (the reductions below have barriers)
+  const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;
+  float m = ze;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;
+    m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
+  }
+  const float M_ = row_max(m, red[0]);
+  float l = __expf(ze - M_);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;
+    l += __expf(v[i].x - M_) + __expf(v[i].y - M_) + __expf(v[i].z - M_) + __expf(v[i].w - M_);
+  }
+  float Q = e.q, qz = e.q > 0.f ? e.q * e.z : 0.f;
+  row_sum3(l, Q, qz, red);
+  const float lse = M_ + __logf(l);
+  const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
+  const float k = row_sum(topk_kl(e, lse), red[0]);
+  if (dlogits) {
+    float* d = dlogits + row * ld;
+    if (extra) d[je] = c.p * __expf(ze - lse) - (tu == je ? c.t : 0.f);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const unsigned j = t0 + 4096u * i;
+      if (!(j + 3 < Vu)) continue;
+      float4 g;
+      g.x = c.p * __expf(v[i].x - lse) - (tu == j ? c.t : 0.f);
+      g.y = c.p * __expf(v[i].y - lse) - (tu == j + 1 ? c.t : 0.f);
+      g.z = c.p * __expf(v[i].z - lse) - (tu == j + 2 ? c.t : 0.f);
+      g.w = c.p * __expf(v[i].w - lse) - (tu == j + 3 ? c.t : 0.f);
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+    __syncthreads();  // every dense store of the row is behind this barrier; the K columns of the teacher are written after it
+    topk_fix(e, lse, c, tu, d);
+  }
+  if (threadIdx.x == 0) topk_finish(row, valid, xt, lse, Q, qz, k, lambda, loss, nll, soft, kl, lse_out);
+}
+
+// Any V, any stride, any alignment: ce_soft_kernel's two sweeps over the logit row alone.
+__global__ __launch_bounds__(SOFT_TPB) void ce_topk_kernel(const float* logits, long ld, const int* __restrict__ ids,
+                                                           const float* __restrict__ logq, long ldk, int K,
+                                                           const int64_t* __restrict__ tgt, float lambda, float* __restrict__ loss,
+                                                           float* __restrict__ nll, float* __restrict__ soft,
+                                                           float* __restrict__ kl, float* __restrict__ lse_out, float* dlogits,
+                                                           float gscale, int V, int vec) {
+  __shared__ float red[3][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  float m = -INFINITY, l = 0.f;
+  const int V4 = vec ? (V & ~3) : 0;
+  for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + j);
+    const float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+    if (mx > m) { l *= __expf(m - mx); m = mx; }
+    if (m > -INFINITY) l += __expf(v.x - m) + __expf(v.y - m) + __expf(v.z - m) + __expf(v.w - m);
+  }
+  for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) {
+    const float v = x[j];
+    if (v > m) { l *= __expf(m - v); m = v; }
+    if (m > -INFINITY) l += __expf(v - m);
+  }
+  const TopkEntry e = topk_entry(ids + row * ldk, logq + row * ldk, x, K, V);
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (row_max has barriers)
+  const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;
+  const float M_ = row_max(m, red[0]);
+  l = m == -INFINITY ? 0.f : l * __expf(m - M_);
+  float Q = e.q, qz = e.q > 0.f ? e.q * e.z : 0.f;
+  row_sum3(l, Q, qz, red);
+  const float lse = M_ + __logf(l);
+  const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
+  const float k = row_sum(topk_kl(e, lse), red[0]);
+  if (dlogits) {
+    float* d = dlogits + row * ld;
+    for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {  // each element read and written by the same thread
+      const float4 v = *reinterpret_cast<const float4*>(x + j);
+      const unsigned ju = (unsigned)j;
+      float4 g;
+      g.x = c.p * __expf(v.x - lse) - (tu == ju ? c.t : 0.f);
+      g.y = c.p * __expf(v.y - lse) - (tu == ju + 1 ? c.t : 0.f);
+      g.z = c.p * __expf(v.z - lse) - (tu == ju + 2 ? c.t : 0.f);
+      g.w = c.p * __expf(v.w - lse) - (tu == ju + 3 ? c.t : 0.f);
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+    for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) d[j] = c.p * __expf(x[j] - lse) - (tu == (unsigned)j ? c.t : 0.f);
+    __syncthreads();  // as in ce_topk_row_kernel
+    topk_fix(e, lse, c, tu, d);
+  }
+  if (threadIdx.x == 0) topk_finish(row, valid, xt, lse, Q, qz, k, lambda, loss, nll, soft, kl, lse_out);
+}
+
 // deterministic single-block sum: out += sum(x[0..n))  (the fixed-order loss_sum of blm_ce_fwd_bwd)
 __global__ __launch_bounds__(1024) void soft_sum_kernel(const float* __restrict__ x, long n, float* out) {
   __shared__ float red[16];
@@ -264,6 +423,51 @@ extern "C" int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float*
   else
     hipLaunchKernelGGL(ce_soft_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
                        lse, dlogits, grad_scale, V, vec ? 1 : 0);
+  BLM_HIP(hipGetLastError());
+  if (loss_sum) {
+    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
+    BLM_HIP(hipGetLastError());
+  }
+  return BLM_OK;
+}
+
+extern "C" int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
+                                        const int64_t* tgt, float lambda, float* loss, float* nll, float* soft, float* kl, float* lse,
+                                        float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream) {
+  const char* missing = !logits ? "logits" : !ids ? "ids" : !logq ? "logq" : !tgt ? "tgt" : !loss ? "loss" : nullptr;
+  if (missing) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: %s is NULL (logits, ids, logq, tgt and loss are required)", missing);
+  if (M < 0 || V <= 0) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: M = %d, V = %d: M >= 0 and V > 0 expected", M, V);
+  if (K < 1 || K > BLM_TOPK_MAX)
+    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: K = %d outside [1, BLM_TOPK_MAX = %d]", K, BLM_TOPK_MAX);
+  if (ld < V || !extents_ok({M, ld}))
+    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: row stride ld = %lld must be >= V = %d (and M x ld an addressable extent)",
+                    (long long)ld, V);
+  if (ldk < K || !extents_ok({M, ldk}))
+    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: row stride ldk = %lld must be >= K = %d (and M x ldk an addressable extent)",
+                    (long long)ldk, K);
+  if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: lambda = %g outside [0, 1]", (double)lambda);
+  if (M == 0) return BLM_OK;
+  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), d0 = reinterpret_cast<uintptr_t>(dlogits);
+  if (dlogits) {  // the gradient may be written over the logits it is the gradient of, element for element, and over nothing else read here
+    const uintptr_t zn = ((uintptr_t)(M - 1) * (uintptr_t)ld + (uintptr_t)V) * 4, kn = ((uintptr_t)(M - 1) * (uintptr_t)ldk + (uintptr_t)K) * 4;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(ids), q0 = reinterpret_cast<uintptr_t>(logq);
+    if (d0 < i0 + kn && i0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: dlogits overlaps ids");
+    if (d0 < q0 + kn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: dlogits overlaps logq");
+    if (d0 != z0 && d0 < z0 + zn && z0 < d0 + zn)
+      return blm_fail(BLM_ERR_INVALID,
+                      "blm_ce_soft_topk_fwd_bwd: dlogits overlaps logits without being logits itself (in place means dlogits == logits)");
+  }
+  const bool vec = ((ld & 3) == 0) && (((z0 | d0) & 15) == 0);
+#define TOPK_ROW(NV)                                                                                                                  \
+  hipLaunchKernelGGL(ce_topk_row_kernel<NV>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, loss, \
+                     nll, soft, kl, lse, dlogits, grad_scale, V)
+  if (vec && V >= 4 && V <= 4096 * 3) TOPK_ROW(3);
+  else if (vec && V >= 4 && V <= 4096 * 9) TOPK_ROW(9);
+  else if (vec && V >= 4 && V <= 4096 * 16) TOPK_ROW(16);
+  else
+    hipLaunchKernelGGL(ce_topk_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, loss, nll,
+                       soft, kl, lse, dlogits, grad_scale, V, vec ? 1 : 0);
+#undef TOPK_ROW
   BLM_HIP(hipGetLastError());
   if (loss_sum) {
     hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);

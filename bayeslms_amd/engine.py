@@ -612,7 +612,8 @@ class Trainer:
         noise / dropout stream index (default: the optimisation step count).  ``soft`` = (teacher_logp, weight): distillation --
         ops.cross_entropy_soft against the teacher's (T * B, V) log-probabilities takes the place of the hard-label cross entropy
         (weight 0 is that loss), everything else is the same step; the step's mean hard NLL, soft loss and KL(teacher || student)
-        stay on the device as ``self.last_soft``.  Single process only."""
+        stay on the device as ``self.last_soft``.  ``soft`` = (ops.SparseTargets, weight): the same against the teacher's K best
+        entries per token (ops.cross_entropy_soft_topk).  Single process only."""
         if soft is not None and self.world > 1:
             raise ops.BayesLMError("Trainer.step: soft targets with world = %d: data-parallel distillation is not built (the teacher's "
                                    "rows would have to follow each rank's batch columns); train the student in one process" % self.world)
@@ -635,7 +636,8 @@ class Trainer:
         if soft is None:
             mle, _ = ops.cross_entropy(out.view(-1, V), targets, unit_grad=True)
         else:
-            mle, parts = ops.cross_entropy_soft(out.view(-1, V), targets, soft[0], soft[1], unit_grad=True)
+            soft_loss = ops.cross_entropy_soft_topk if isinstance(soft[0], ops.SparseTargets) else ops.cross_entropy_soft
+            mle, parts = soft_loss(out.view(-1, V), targets, soft[0], soft[1], unit_grad=True)
             self.last_soft = ops.SoftStats(parts.nll.mean(), parts.soft.mean(), parts.kl.mean())  # no host synchronisation
         kl = None
         if kl_fn is not None:

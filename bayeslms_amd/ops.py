@@ -29,7 +29,7 @@ from . import _lib as L
 from ._lib import BayesLMError, calls, dev_tensor, ptr, stream
 
 __all__ = ["Drop", "NoiseSpec", "LrtNoise", "ResidualLink", "linear", "bayes_linear", "bayes_linear_lrt", "ffn", "ffn_lrt", "ffn_gp", "attention", "attention_qkv", "add_dropout_ln",
-           "embed", "add_pe", "dropout", "cross_entropy", "cross_entropy_soft", "SoftStats", "kl_mean", "philox_normal", "sample_weight", "sampled", "lstm_layer", "lstm_stack2", "lstm_stack2_ok", "set_lstm_wavefront", "lstm_cell", "gp_mix", "add_rowvec",
+           "embed", "add_pe", "dropout", "cross_entropy", "cross_entropy_soft", "SoftStats", "cross_entropy_soft_topk", "SparseTargets", "kl_mean", "philox_normal", "sample_weight", "sampled", "lstm_layer", "lstm_stack2", "lstm_stack2_ok", "set_lstm_wavefront", "lstm_cell", "gp_mix", "add_rowvec",
            "clip_sgd", "gemm", "PtrTable", "set_grad_ready_hook", "set_embed_grad_sink", "rows_gather_add", "KernelTimer", "set_kernel_timer"]
 
 
@@ -1620,6 +1620,102 @@ def cross_entropy_soft(logits, targets, teacher_logp, weight, unit_grad=False):
     return loss, SoftStats(nll, soft, kl)
 
 
+# ----------------------------------------------------------------------------
+# distillation from top-k teacher targets: the same loss against K (id, log-probability) pairs per token  (blm_ce_soft_topk_fwd_bwd)
+# ----------------------------------------------------------------------------
+class SparseTargets(NamedTuple):
+    """A teacher's K best next words per token (distill.Teacher.topk, distill.TeacherCache.load): what
+    ops.cross_entropy_soft_topk is trained against.  An id outside [0, V) (-1 by convention) marks an empty slot."""
+    ids: torch.Tensor   # (M, K) int32, the live ids of a row distinct
+    logq: torch.Tensor  # (M, K) float32 log-probabilities; -inf: a zero of the teacher
+
+
+class _CrossEntropySoftTopk(torch.autograd.Function):
+    """_CrossEntropySoft with the teacher's dense rows replaced by SparseTargets: the same buffers, the same two gradient forms."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, ids, logq, weight, unit_grad):
+        V = logits.shape[-1]
+        whole = logits
+        logits, ld = _rows2d(logits, V, "logits")  # rows padded to 4 floats (odd vocabulary, ops._Linear) are taken as they are
+        if whole.data_ptr() != logits.data_ptr():
+            whole = logits.view(whole.shape)
+        targets = dev_tensor(targets, "targets", torch.int64)
+        M = logits.numel() // V
+        if targets.numel() != M:
+            raise BayesLMError("cross_entropy_soft_topk: %d targets for %d rows" % (targets.numel(), M))
+        if M == 0:
+            raise BayesLMError("cross_entropy_soft_topk: no rows (the mean over zero tokens is undefined; torch returns nan here)")
+        if ids.dim() != 2 or ids.shape[0] != M or tuple(logq.shape) != tuple(ids.shape):
+            raise BayesLMError("cross_entropy_soft_topk: sparse ids %s, logq %s against %d rows of logits: two (M, K) matrices expected"
+                               % (tuple(ids.shape), tuple(logq.shape), M))
+        K = ids.shape[1]
+        if not 1 <= K <= L.TOPK_MAX:
+            raise BayesLMError("cross_entropy_soft_topk: K = %d targets per row outside [1, BLM_TOPK_MAX = %d]" % (K, L.TOPK_MAX))
+        ids, logq = dev_tensor(ids, "sparse.ids", torch.int32), dev_tensor(logq, "sparse.logq", torch.float32)
+        dev = logits.device
+        rows, nll, soft, kl = (torch.empty(M, device=dev, dtype=torch.float32) for _ in range(4))
+        loss = torch.zeros((), device=dev, dtype=torch.float32)
+        grad_mode = ctx.needs_input_grad[0]  # forward itself runs with grad mode off
+        fuse = grad_mode and unit_grad
+        grad = None
+        if fuse:
+            grad = logits
+        elif grad_mode:  # rows strided as the logits' (one stride serves both in the kernel)
+            if ld == V:
+                grad = torch.empty_like(logits)
+            elif ld == (V + 3) // 4 * 4:  # registered as this module's: ops._Linear may run its padded backward on it
+                grad = _padded_rows((M,), V, dev)[0]
+            else:
+                grad = torch.empty(M, ld, device=dev, dtype=torch.float32)[:, :V]
+        L.require_gfx950()
+        calls().blm_ce_soft_topk_fwd_bwd(ptr(logits), ld, ptr(ids), ptr(logq), K, K, ptr(targets), float(weight), ptr(rows), ptr(nll),
+                                         ptr(soft), ptr(kl), None, ptr(loss), ptr(grad), 1.0 / M, M, V, stream())
+        if fuse:  # the buffer now holds the gradient: any other autograd consumer of the logits must fail, not read it
+            torch.autograd.graph.increment_version(whole)
+        ctx.meta = (whole if fuse else grad.view(whole.shape) if grad is not None else None, fuse)
+        ctx.mark_non_differentiable(nll, soft, kl)
+        ctx.set_materialize_grads(False)
+        return loss / M, nll, soft, kl
+
+    @staticmethod
+    def backward(ctx, g, _g_nll, _g_soft, _g_kl):
+        grad, fuse = ctx.meta
+        if g is None:
+            return None, None, None, None, None, None
+        if fuse:
+            return grad, None, None, None, None, None
+        if getattr(ctx, "spent", False):  # the buffer was scaled by the first backward's upstream gradient
+            raise BayesLMError("cross_entropy_soft_topk: backward ran already and scaled the gradient buffer by its upstream gradient; "
+                               "a second backward over a retained graph needs a second forward")
+        ctx.spent = True
+        grad.mul_(_f32(g.reshape(()), "g"))
+        return grad, None, None, None, None, None
+
+
+def cross_entropy_soft_topk(logits, targets, sparse, weight, unit_grad=False):
+    """ops.cross_entropy_soft against the K best entries of the teacher per token instead of its dense rows -> (loss,
+    SoftStats(nll, soft, kl)); definitions in include/bayeslm.h, blm_ce_soft_topk_fwd_bwd.  ``sparse``: SparseTargets(ids (M, K)
+    int32, logq (M, K) float32) on the GPU, no gradient, 1 <= K <= BLM_TOPK_MAX, the live ids of a row distinct (ops.topk_rows'
+    are); an id outside [0, V) is an empty slot.  The teacher's mass Q = sum_j exp(logq_j) of a row is carried as it is: with
+    Q < 1 (top-k of a normalised teacher) the soft term weighs Q, and the tail of the teacher is dropped.  ``weight``,
+    ``unit_grad`` and what happens to the logits buffer: as ops.cross_entropy_soft."""
+    if type(logits) is not torch.Tensor:
+        logits = logits.as_subclass(torch.Tensor)  # model outputs are `Logits` in grad mode (below); the op wants the plain tensor
+    if not (isinstance(sparse, tuple) and len(sparse) == 2 and torch.is_tensor(sparse[0]) and torch.is_tensor(sparse[1])):
+        raise BayesLMError("cross_entropy_soft_topk: sparse must be SparseTargets(ids, logq), got %s" % type(sparse).__name__)
+    ids, logq = sparse
+    if ids.dtype != torch.int32:
+        raise BayesLMError("cross_entropy_soft_topk: sparse.ids must be int32, got %s" % ids.dtype)
+    if logq.requires_grad:
+        raise BayesLMError("cross_entropy_soft_topk: sparse.logq requires grad; the teacher is a constant of the loss (detach it: "
+                           "no gradient is formed for it)")
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0:
+        raise BayesLMError("cross_entropy_soft_topk: weight must be a float in [0, 1], got %r" % (weight,))
+    loss, nll, soft, kl = _CrossEntropySoftTopk.apply(logits, targets, ids, logq, float(weight), unit_grad)
+    return loss, SoftStats(nll, soft, kl)
+
+
 class Logits(torch.Tensor):
     """What a language model's decoder returns in grad mode: a plain fp32 tensor to every consumer, except that
     ``torch.nn.functional.cross_entropy`` on it (the reference loop's ``criterion(output.view(-1, ntokens), targets)``,
@@ -2296,7 +2392,10 @@ def topk_rows(x, k):
     """The k best entries of every row of the (R, V) matrix x, best first (blm_topk_rows): value descending, then index
     ascending, NaN below -inf; values are copied bit for bit.  1 <= k <= min(V, _lib.TOPK_MAX).
     -> (vals (R, k) float32, ids (R, k) int64)"""
-    x = _f32(x, "x")
+    if torch.is_tensor(x) and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.dtype == torch.float32:
+        dev_tensor(x[:1], "x", torch.float32)  # rows with a stride of their own (padded odd-vocabulary rows) are read in place
+    else:
+        x = _f32(x, "x")
     if x.dim() != 2 or x.stride(-1) != 1:
         raise BayesLMError("topk_rows: a row-major (R, V) matrix expected")
     R, V = x.shape

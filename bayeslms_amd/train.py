@@ -17,6 +17,8 @@ import time
 import torch
 import torch.distributed as dist
 
+from ._lib import TOPK_MAX
+
 
 def build_parser():
     p = argparse.ArgumentParser(description="Train and evaluate a neural language model (MI355X engine).")
@@ -109,6 +111,17 @@ def build_parser():
                    help='new, optional (with --distill-from): the flags that shape the TEACHER, as one string of this command line\'s '
                         'own flags (a checkpoint holds weights, not an architecture).  Only the model-shaping ones are read: %s.  '
                         'Default: the student\'s own' % ", ".join("--" + f for f in TEACHER_FLAGS))
+    p.add_argument('--distill-top-k', type=int, default=0, metavar='K',
+                   help='new, optional (with --distill-from): train against the K best entries of the teacher per token (1..%d, at '
+                        'most the vocabulary) instead of its dense rows: the soft term of a token is weighted by the teacher mass '
+                        'its K entries hold and the tail is dropped (0: dense)' % TOPK_MAX)
+    p.add_argument('--distill-top-k-renorm', type=int, default=0, choices=[0, 1],
+                   help='new, optional (with --distill-top-k): 1 = renormalise the K entries of every token to sum to one')
+    p.add_argument('--distill-cache', type=str, default='', metavar='PATH',
+                   help='new, optional (with --distill-top-k): keep the teacher\'s top-K targets of the training walk in this file.  '
+                        'The first epoch computes and stores them, every later epoch -- and every later run against the same '
+                        'teacher, corpus, K and batch shape -- loads them and runs no teacher; a file written for anything else is '
+                        'refused')
     return p
 
 
@@ -121,7 +134,9 @@ def check_distill_args(args, world):
     """The --distill-* flags, refused before anything is loaded -> the teacher's model-shaping flags (a namespace), or None."""
     if not args.distill_from:
         for flag, given in (("--distill-weight", args.distill_weight is not None), ("--distill-mc-samples", args.distill_mc_samples != 0),
-                            ("--distill-teacher-args", args.distill_teacher_args is not None)):
+                            ("--distill-teacher-args", args.distill_teacher_args is not None),
+                            ("--distill-top-k", args.distill_top_k != 0), ("--distill-top-k-renorm", args.distill_top_k_renorm != 0),
+                            ("--distill-cache", bool(args.distill_cache))):
             if given:
                 raise SystemExit("%s needs --distill-from" % flag)
         return None
@@ -132,6 +147,13 @@ def check_distill_args(args, world):
     S = args.distill_mc_samples
     if S < 0 or S == 1 or S > 64:
         raise SystemExit("--distill-mc-samples must be 0 (mean weights) or lie in 2..64, the most one decoder launch averages (got %d)" % S)
+    if args.distill_top_k == 0:
+        for flag, given in (("--distill-top-k-renorm", args.distill_top_k_renorm != 0), ("--distill-cache", bool(args.distill_cache))):
+            if given:
+                raise SystemExit("%s needs --distill-top-k" % flag)
+    elif not 1 <= args.distill_top_k <= TOPK_MAX:
+        raise SystemExit("--distill-top-k must lie in 1..%d, the most entries per token the sparse loss takes (got %d)"
+                         % (TOPK_MAX, args.distill_top_k))
     if world > 1:
         raise SystemExit("--distill-from runs in a single process: data-parallel distillation is not built (world size %d)" % world)
     if (args.noise_source or os.environ.get("BLM_NOISE_SOURCE", "philox")) == "torch":
@@ -157,6 +179,8 @@ def load_teacher_state(args):
     if rows[0] != len(words):
         raise SystemExit("--distill-from %s: the teacher's vocabulary has %d words, the corpus at %s has %d: a teacher's distribution "
                          "must be over the student's words" % (args.distill_from, rows[0], args.data, len(words)))
+    if args.distill_top_k > len(words):
+        raise SystemExit("--distill-top-k %d: the vocabulary at %s has %d words only" % (args.distill_top_k, args.data, len(words)))
     return sd
 
 
@@ -381,7 +405,7 @@ def main(argv=None, history=None):
     say('Model total parameters: {}'.format(total_params))
     say(str(model.transformerlayers if args.model == 'Transformer' else model.rnn))
 
-    teacher = None
+    teacher, topk, cache = None, 0, None
     if teacher_shape is not None:
         from . import distill
         with torch.random.fork_rng(devices=[]):  # the constructors draw from torch's generator: the student's run does not see it
@@ -397,8 +421,24 @@ def main(argv=None, history=None):
         except ops.BayesLMError as e:
             raise SystemExit("--distill-from %s: %s" % (args.distill_from, e))
         history.update({"interval_soft": [], "interval_kd_kl": []})
+        topk = args.distill_top_k
+        if args.distill_cache:
+            fields = distill.TeacherCache.describe(ntokens, topk, args.distill_top_k_renorm, args.seq_len, train_data.size(0),
+                                                   train_data.size(1), distill.sha256_tensor(train_data),
+                                                   distill.sha256_file(args.distill_from), vars(teacher_shape),
+                                                   args.distill_mc_samples, args.distill_mc_seed)
+            try:
+                cache = distill.TeacherCache(args.distill_cache, fields)
+            except distill.CacheMismatch as e:
+                raise SystemExit("--distill-cache: %s" % e)
         say("distilling from %s (%s), weight %g, %s" % (args.distill_from, type(teacher_model).__name__, args.distill_weight,
                                                        "%d Monte-Carlo samples" % teacher.S if teacher.S else "mean weights"))
+        if topk:
+            say("top-%d teacher targets%s: %s" % (
+                topk, " (renormalised)" if args.distill_top_k_renorm else "",
+                "computed every batch, no cache" if cache is None else
+                "loaded from the complete cache %s, the teacher does not run" % args.distill_cache if cache.complete else
+                "the first epoch computes them and fills the cache %s, later epochs load them" % args.distill_cache))
 
     kl_fn = kl_selector(args)
     kl_scale = float(args.seq_len) / float(len(train_data))  # KL / len(train_data) * seq_len (train.py:338)
@@ -411,7 +451,8 @@ def main(argv=None, history=None):
         start = time.time()
         hidden = model.init_hidden(train_data.size(1)) if is_rnn else None
         total_soft = total_kd = 0.
-        if teacher is not None:
+        cached = teacher is not None and cache is not None and cache.complete  # this epoch's targets come from disk
+        if teacher is not None and not cached:
             teacher.reset(train_data.size(1))
         for batch, i in enumerate(range(0, train_data.size(0) - 1, args.seq_len)):
             data, targets = D.get_batch(train_data, i, args.seq_len)
@@ -420,7 +461,14 @@ def main(argv=None, history=None):
             if teacher is None:
                 loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn)
             else:
-                logq, _ = teacher.logprobs(data)
+                if cached:
+                    logq = cache.load(i * train_data.size(1), data.numel(), device)
+                elif topk:
+                    logq, _ = teacher.topk(data, topk, bool(args.distill_top_k_renorm))
+                    if cache is not None:
+                        cache.store(i * train_data.size(1), logq)
+                else:
+                    logq, _ = teacher.logprobs(data)
                 loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn, soft=(logq, args.distill_weight))
                 total_soft, total_kd = total_soft + trainer.last_soft.soft, total_kd + trainer.last_soft.kl
             total_loss = total_loss + loss  # stays on the device: one host sync per log interval (train.py:422 syncs per step)
@@ -447,6 +495,8 @@ def main(argv=None, history=None):
                 say(line)
                 total_loss = 0.
                 start = time.time()
+        if teacher is not None and cache is not None and not cache.complete:
+            cache.finish()  # every window of the walk is stored: the file is marked complete, the next epoch reads it
 
     sched = ValidationSchedule(args.lr, world, device)
     say("Start training")

@@ -672,6 +672,29 @@ int blm_ce_interp_fwd(const float* logits_a, const float* logits_b, int64_t ld, 
 int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
                         float* loss, float* nll, float* soft, float* kl, float* lse, float* loss_sum, float* dlogits,
                         float grad_scale, int M, int V, void* stream);
+/* The same loss against TOP-K teacher targets: the dense logq, ldq of blm_ce_soft_fwd_bwd replaced by a sparse row per token,
+ * ids (M, K) int32 and logq (M, K) float32, both with row stride ldk >= K (in elements), 1 <= K <= BLM_TOPK_MAX; every other
+ * argument as there and in the same order.  Per row m, with z, lse, p, t, valid as above:
+ *   entry j is LIVE when 0 <= ids[m,j] < V; any other id marks an empty slot (-1 by convention) whose logq is never read
+ *   q_j = exp(logq[m,j]) (-inf: q_j = 0),  Q = sum_{j live} q_j   (carried, not assumed 1: the K best entries of a teacher
+ *                                                                   hold less than all of its mass)
+ *   nll[m]  = valid ? lse - z_t : 0
+ *   soft[m] = Q lse - sum_{q_j > 0} q_j z[ids_j]
+ *   kl[m]   = sum_{q_j > 0} q_j (logq_j - z[ids_j] + lse)           (summed term by term)
+ *   loss[m] = (1 - lambda) nll[m] + lambda soft[m]
+ *   dlogits[m,v] = ((1 - lambda) valid (p_v - [v = t]) + lambda (Q p_v - sum_{j live, ids_j = v} q_j)) grad_scale
+ * On a dense teacher that is -inf outside the live ids this is blm_ce_soft_fwd_bwd.  The live ids of one row must be distinct
+ * (blm_topk_rows' are); with duplicates the values at that column are unspecified, and nothing is read or written out of
+ * bounds.  loss is required; nll, soft, kl, lse are optional; loss_sum (optional) += sum_m loss[m], added in a fixed order;
+ * dlogits (optional, row stride ld) may be logits itself (in place).  BLM_ERR_INVALID, before any launch: NULL logits, ids, logq,
+ * tgt or loss, M < 0 or V <= 0, K < 1 or K > BLM_TOPK_MAX, ld < V or ldk < K (or M x stride not an addressable extent), lambda
+ * outside [0, 1] or NaN, dlogits overlapping ids or logq, or overlapping logits other than exactly in place.  M == 0 is a no-op.
+ * One workgroup per row; the logit row is read from memory once, the 2 K teacher values once: for 4 <= V <= 65536 with ld a
+ * multiple of 4 and 16-byte aligned logits / dlogits the row is held in registers, otherwise a guarded two-sweep form; ids and
+ * logq rows need no alignment beyond their element type.  No floating-point atomics: every run gives the same bits. */
+int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
+                             const int64_t* tgt, float lambda, float* loss, float* nll, float* soft, float* kl, float* lse,
+                             float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream);
 
 
 /* dcoef[i,n] += sum_m g[m,n] * act_i(z[m,n]), i = tanh, sigmoid, relu, gelu: gradient of the GPNN

@@ -9,17 +9,26 @@ B. step: the configs[2] Bayesian Transformer (6 x d 512, ff 4096, 64 x 128 token
    teacher of the same architecture at mean weights (S = 0) and under S = 2 and 8 Monte-Carlo samples: ms per step (teacher
    pass + student step), median of 10 after 3 warm-up steps, a device synchronise inside each timed step.
 
-usage: distill_probe.py [kernel|step ...]   (default: both)"""
+--top-k K adds the sparse path beside both:
+A. blm_ce_soft_topk_fwd_bwd against the K best entries of the same teacher rows, as a third leg on the same logit buffers in the
+   same rotation (it must move the logits twice and 2 K values per row), and ops.topk_rows on the 8192 x V teacher alone: what
+   extracting the targets on the fly costs per batch.
+B. the step with the targets extracted ON THE FLY (teacher pass + top-k + student step; mean weights and S = 8) and from a
+   complete CACHE on disk (distill.TeacherCache.load + student step, no teacher): the second is what every epoch after the
+   first, and every later run against the same teacher, pays.
+
+usage: distill_probe.py [--top-k K] [kernel|step ...]   (default: both)"""
 import os
 import statistics
 import sys
+import tempfile
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from bayeslms_amd import distill, engine, model as M  # noqa: E402
+from bayeslms_amd import distill, engine, model as M, ops  # noqa: E402
 from bayeslms_amd.data import synthetic_corpus  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -29,7 +38,7 @@ def say(*a):
     print(*a, flush=True)
 
 
-def kernel_legs(V):
+def kernel_legs(V, top_k=0):
     from bayeslms_amd import _lib as L
     L.require_gfx950()
     R, NB, N = 8192, 3, 30
@@ -49,6 +58,13 @@ def kernel_legs(V):
             ("blm_ce_soft_fwd_bwd", 3, lambda k: c.blm_ce_soft_fwd_bwd(zs[k].data_ptr(), ld, qs[k].data_ptr(), ld, tgt.data_ptr(), 0.5,
                                                                        f[0].data_ptr(), f[1].data_ptr(), f[2].data_ptr(), f[3].data_ptr(),
                                                                        None, total.data_ptr(), zs[k].data_ptr(), 1.0 / R, R, V, st)))
+    if top_k:
+        best = [torch.topk(q[:, :V], top_k, dim=1) for q in qs]
+        ks = [(b.indices.to(torch.int32).contiguous(), b.values.contiguous()) for b in best]
+        legs += (("blm_ce_soft_topk_fwd_bwd", 2, lambda k: c.blm_ce_soft_topk_fwd_bwd(
+            zs[k].data_ptr(), ld, ks[k][0].data_ptr(), ks[k][1].data_ptr(), top_k, top_k, tgt.data_ptr(), 0.5, f[0].data_ptr(),
+            f[1].data_ptr(), f[2].data_ptr(), f[3].data_ptr(), None, total.data_ptr(), zs[k].data_ptr(), 1.0 / R, R, V, st)),
+                 ("ops.topk_rows k = %d" % top_k, 1, lambda k: ops.topk_rows(qs[k][:, :V], top_k)))
     us = {}
     for name, passes, fn in legs:
         for k in range(NB):
@@ -63,12 +79,17 @@ def kernel_legs(V):
             torch.cuda.synchronize()
             times.append(1e3 * e0.elapsed_time(e1) / N)
         us[name] = statistics.median(times)
-        nbytes = passes * R * V * 4
-        say("%-22s V %5d %8.1f us  %5.2f TB/s of the %d MB it must move" % (name, V, us[name], nbytes / us[name] / 1e6, nbytes // 10 ** 6))
+        nbytes = passes * R * V * 4 + (2 * top_k * R * 4 if "soft_topk" in name else 0)
+        say("%-24s V %5d %8.1f us  %5.2f TB/s of the %d MB it must move" % (name, V, us[name], nbytes / us[name] / 1e6, nbytes // 10 ** 6))
     say("soft / hard at V %d: %.2f x  (3 matrices against 2: 1.5 by bytes)" % (V, us["blm_ce_soft_fwd_bwd"] / us["blm_ce_fwd_bwd"]))
+    if top_k:
+        t = us["blm_ce_soft_topk_fwd_bwd"]
+        say("top-%d / hard at V %d: %.2f x  (%.3f by bytes);  top-%d / dense soft: %.2f x%s" % (
+            top_k, V, t / us["blm_ce_fwd_bwd"], (2 * V + 2 * top_k) / (2.0 * V), top_k, t / us["blm_ce_soft_fwd_bwd"],
+            "" if t <= us["blm_ce_soft_fwd_bwd"] else "  SLOWER THAN THE DENSE KERNEL: the gather or the correction step is wrong, no result"))
 
 
-def step_legs():
+def step_legs(top_k=0):
     T, B, V = 128, 64, bench.V
 
     def build():
@@ -83,7 +104,21 @@ def step_legs():
     say("# B. configs[2] Bayesian Transformer, %d x %d tokens per step, V %d; ms per step (teacher pass + student step), median of 10 "
         "after 3 warm-up steps" % (B, T, V))
     base = None
-    for S in (None, 0, 2, 8):
+    cache = None
+    if top_k:  # the cache of this walk, filled once from the mean-weight teacher: what a later epoch or run finds on disk
+        path = os.path.join(tempfile.mkdtemp(), "teacher.cache")
+        cache = distill.TeacherCache(path, distill.TeacherCache.describe(V, top_k, False, T, src.size(0), B, "probe", "probe", {}, 0, 1111))
+        filler = distill.Teacher(teacher_model)
+        for k in range(14):
+            sparse, kept = filler.topk(src[k * T:(k + 1) * T], top_k)
+            cache.store(k * T * B, sparse)
+        cache.finish()
+        say("# top-%d targets: mean kept teacher mass %.3f (an untrained teacher's: no statement about a trained one); cache of %d rows, %.1f MB, %.2f MB per "
+            "batch" % (top_k, float(kept.mean()), cache.n, os.path.getsize(path) / 1e6, T * B * top_k * 8 / 1e6))
+    legs = [(None, "plain"), (0, "dense"), (2, "dense"), (8, "dense")]
+    if top_k:
+        legs += [(0, "topk"), (8, "topk"), (0, "cache")]
+    for S, how in legs:
         torch.manual_seed(7)
         student = build()
         tr = engine.Trainer(student, lr=0.1, clip=1.0, kl_scale=T / float(src.size(0)), seed=1111)
@@ -95,6 +130,10 @@ def step_legs():
             t0 = time.perf_counter()
             if teacher is None:
                 tr.step(data, tgt, None, kl_fn)
+            elif how == "cache":
+                tr.step(data, tgt, None, kl_fn, soft=(cache.load(k * T * B, T * B, dev), 0.5))
+            elif how == "topk":
+                tr.step(data, tgt, None, kl_fn, soft=(teacher.topk(data, top_k)[0], 0.5))
             else:
                 logq, _ = teacher.logprobs(data)
                 tr.step(data, tgt, None, kl_fn, soft=(logq, 0.5))
@@ -102,15 +141,22 @@ def step_legs():
             times.append(1e3 * (time.perf_counter() - t0))
         ms = statistics.median(times[3:])
         base = base or ms
-        say("%-28s %8.2f ms per step  %5.2f x plain" % ("plain" if S is None else "teacher S = %d" % S, ms, ms / base))
+        name = ("plain" if S is None else "top-%d from the cache, no teacher" % top_k if how == "cache" else
+                "teacher S = %d%s" % (S, ", top-%d on the fly" % top_k if how == "topk" else ""))
+        say("%-36s %8.2f ms per step  %5.2f x plain" % (name, ms, ms / base))
         del student, tr, teacher
 
 
 if __name__ == "__main__":
-    for w in (sys.argv[1:] or ["kernel", "step"]):
+    argv, top_k = sys.argv[1:], 0
+    if "--top-k" in argv:
+        i = argv.index("--top-k")
+        top_k = int(argv[i + 1])
+        del argv[i:i + 2]
+    for w in (argv or ["kernel", "step"]):
         if w == "kernel":
             with torch.no_grad():
-                kernel_legs(33000)
-                kernel_legs(33278)
+                kernel_legs(33000, top_k)
+                kernel_legs(33278, top_k)
         else:
-            step_legs()
+            step_legs(top_k)
