@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("BLM_LIB") or os.path.join(_HERE, "libbayeslm_hip.so")
 
 ABI_VERSION = 1
 TOPK_MAX = 256  # BLM_TOPK_MAX (include/bayeslm.h)
+ROW_TEMPS_MAX = 8  # BLM_ROW_TEMPS_MAX
 OK = 0
 ERR_INVALID, ERR_ABI, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4  # blm_status (include/bayeslm.h)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -70,6 +71,11 @@ class BeamPoolArgs(C.Structure):
     """blm_beam_pool (include/bayeslm.h)."""
     _fields_ = ([("abi_version", C.c_uint32), ("P", C.c_int32)]
                 + [(n, C.c_void_p) for n in ("norm", "raw", "len", "step", "parent", "finished", "count", "inserted")])
+
+
+class RowTemps(C.Structure):
+    """blm_row_temps (include/bayeslm.h)."""
+    _fields_ = [("abi_version", C.c_uint32), ("count", C.c_int32), ("beta", C.c_float * ROW_TEMPS_MAX)]
 
 
 class GemmPlan(C.Structure):
@@ -137,6 +143,7 @@ SIGNATURES = {
     "blm_log_softmax_rows": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp]),
     "blm_sample_rows": (_i, [_vp, _i64, _i, _i, _f, _rngp, _vp, _vp]),
     "blm_row_stats": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "blm_row_stats_temps": (_i, [_vp, _i64, _vp, _i, _i, C.POINTER(RowTemps), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_topk_rows": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "blm_beam_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "blm_beam_select_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _i, C.POINTER(BeamPoolArgs),

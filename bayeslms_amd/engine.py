@@ -761,10 +761,13 @@ class EvalReport:
     mean_h_pred: Optional[float] = None    # mean predictive entropy H[pbar]
     mean_mi: Optional[float] = None        # mean mutual information between the word and the weights
     per_token: Optional[dict] = None       # keep_tokens: float / int arrays in text order, skipped tokens included (NaN / -1)
+    temperature: Optional[dict] = None     # temperature scaling (temperature_block); None: the distribution as the model gives it
 
     def as_dict(self):
         d = dataclasses.asdict(self)
         del d["per_token"]
+        if d["temperature"] is None:  # a run without a temperature writes what it wrote before there was one
+            del d["temperature"]
         return d
 
 
@@ -848,64 +851,65 @@ def _report_windows(source, seq_len, recurrent):
         yield data, targets, pos(i, len(data)).reshape(-1)
 
 
-def evaluate_report(model, source, seq_len, eval_batch_size=None, mc_samples=0, seed=1111, bins=15, calibration=True,
-                    keep_tokens=False):
-    """Held-out loss / perplexity, accuracy and calibration of ``model`` over the batchified stream ``source``, at mean weights
-    (``mc_samples`` 0) or under the average of S = ``mc_samples`` >= 2 Monte-Carlo weight samples -> EvalReport.
+def temperature_block(beta, fitted_on=None, at_bound=False, before=None, after=None, curve=None):
+    """EvalReport.temperature: the scaling a report was made with -- T, beta = 1 / T as the kernel got it (float32), and, after a
+    fit, the text it was fitted on, whether it ended at a bound of the search, the FIT text's loss and ECE at T = 1 and at T, and
+    the curve of fit_temperature."""
+    beta = float(beta)
+    return {"temperature": 1.0 / beta, "beta": beta, "fitted_on": fitted_on, "at_bound": bool(at_bound),
+            "loss_before": None if before is None else before.loss, "loss_after": None if after is None else after.loss,
+            "ece_before": None if before is None else before.ece, "ece_after": None if after is None else after.ece,
+            "curve": curve}
 
-    The walk is engine.evaluate's (same windows, same grouping: _report_windows) with the decoder handing back its input rows;
-    those go through the decoder in chunks of _REPORT_ROWS rows and blm_row_stats reduces each chunk's (rows, V) matrix to
-    per-token NLL, confidence, entropy, prediction and rank in one read.  The per-token float32 arrays stay on the device
-    until the walk is over, come to the host in one copy, and every sum is formed there in float64 (report_from_tokens).
 
-    mc_samples = S: S passes per batch in the n-best scorer's sampling state (model.mc_sampling(model, seed, S), sample s
-    selected with set_step(s)): sample s is ONE model for the whole text, and a recurrent model carries S (h, c) sets from window
-    to window.  The model average is taken PER TOKEN, pbar(w | history) = mean_s p_s(w | history) -- a normalised distribution
-    over word sequences, whose NLL is ``loss`` -- not the scorer's sentence-level -log mean_s exp(-NLL_s(sentence)).  One launch
-    per chunk keeps log pbar with nll_s, bma_nll, h_pred and mi (ops.linear_mc_logprobs), and blm_row_stats reads log pbar.
-    ``calibration`` False under Monte-Carlo: ops.linear_mc_stats instead -- nothing of width V is stored, and the report has no
-    accuracy / confidence / calibration block (at mean weights the chunk's logits exist either way and the flag changes nothing).
-    Refused: mc_samples 1; a model without variational sites or with local reparameterisation (mc_sampling's refusals); cells that
-    redraw noise at every time step of a call (as IncrementalLM refuses them).  ``eval_batch_size`` is accepted for symmetry with
-    the reference's evaluate and unused, like there.  Single process only.  The model is left in eval mode with the caller's
-    noise (seed, step, auto_step)."""
+def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, betas):
+    """The walk evaluate_report and evaluate_temperatures share -> (host arrays, text positions per window, V, S).
+    ``betas`` None: blm_row_stats reduces each chunk and the float arrays are (tokens,).  A list of J float32 inverse
+    temperatures: blm_row_stats_temps reduces it, and nll, conf, entropy and dnll are (J, tokens), those of the tempered
+    distributions; nll_s, h_pred and mi stay the untempered (tokens, ...) quantities of ops.linear_mc_logprobs."""
     from . import incremental
     from .model import inference_decoder, mc_sampling, repackage_hidden
     S = int(mc_samples)
     model.eval()
     if dist.is_initialized() and dist.get_world_size() > 1:
-        raise ops.BayesLMError("evaluate_report runs in a single process (world size %d): sharding the report over ranks is not "
-                               "built; call it on one rank" % dist.get_world_size())
+        raise ops.BayesLMError("%s runs in a single process (world size %d): sharding the report over ranks is not "
+                               "built; call it on one rank" % (who, dist.get_world_size()))
     if S < 0 or S == 1 or S > 64:
-        raise ops.BayesLMError("evaluate_report: mc_samples must be 0 (mean weights) or 2..64, got %d: one sample is neither the "
+        raise ops.BayesLMError("%s: mc_samples must be 0 (mean weights) or 2..64, got %d: one sample is neither the "
                                "mean-weight model nor an average, and blm_linear_mc_logprobs / blm_linear_mc_stats take at most 64 "
-                               "samples per launch" % S)
+                               "samples per launch" % (who, S))
+    if betas is not None and S and not calibration:
+        raise ops.BayesLMError("%s: a temperature with mc_samples = %d and calibration=False: that path stores no row of width V, "
+                               "so there is nothing to temper" % (who, S))
     dec = inference_decoder(model)
     if dec is None:
-        raise ops.BayesLMError("evaluate_report: %s has no decoder that hands back its input rows" % type(model).__name__)
+        raise ops.BayesLMError("%s: %s has no decoder that hands back its input rows" % (who, type(model).__name__))
     recurrent = hasattr(model, "init_hidden")
     if S and recurrent:
         cell = incremental._redraws_per_time_step(model)
         if cell:
-            raise ops.BayesLMError("evaluate_report: mc_samples on %s: %s draws fresh noise at every time step of a call, so a "
-                                   "sample is not one model over a stream" % (type(model).__name__, cell))
+            raise ops.BayesLMError("%s: mc_samples on %s: %s draws fresh noise at every time step of a call, so a "
+                                   "sample is not one model over a stream" % (who, type(model).__name__, cell))
     V = dec.weight.shape[0]
     cols = source.shape[1]
-    keep = {k: [] for k in ("tgt", "pos", "nll", "conf", "entropy", "pred", "rank", "nll_s", "h_pred", "mi")}
+    keep = {k: [] for k in ("tgt", "pos", "nll", "conf", "entropy", "dnll", "pred", "rank", "nll_s", "h_pred", "mi")}
+
+    def row_stats(x, t):
+        return ops.row_stats(x, t, V) if betas is None else ops.row_stats_temps(x, betas, t, V)
 
     def reduce_rows(x, targets):
         """x: (rows, K) at mean weights, (S, rows, K) under Monte-Carlo"""
         for a in range(0, targets.numel(), _REPORT_ROWS):
             t = targets[a:a + _REPORT_ROWS]
             if S == 0:
-                st = ops.row_stats(ops.linear(x[a:a + _REPORT_ROWS], dec.weight, dec.bias), t, V)
+                st = row_stats(ops.linear(x[a:a + _REPORT_ROWS], dec.weight, dec.bias), t)
             elif calibration:
                 mc = ops.linear_mc_logprobs(x[:, a:a + _REPORT_ROWS], dec.weight, dec.bias, tgt=t, dec=mc_dec, stats=True)
-                st = ops.row_stats(mc.logp, t, V)
+                st = row_stats(mc.logp, t)
             else:
                 mc, st = ops.linear_mc_stats(x[:, a:a + _REPORT_ROWS], dec.weight, dec.bias, t, dec=mc_dec), None
             if S:
-                keep["nll"].append(mc.bma_nll)
+                keep["nll"].append(mc.bma_nll if betas is None else st.nll)
                 keep["nll_s"].append(mc.nll_s)
                 keep["h_pred"].append(mc.h_pred)
                 keep["mi"].append(mc.mi)
@@ -916,6 +920,8 @@ def evaluate_report(model, source, seq_len, eval_batch_size=None, mc_samples=0, 
                 keep["entropy"].append(st.entropy)
                 keep["pred"].append(st.pred)
                 keep["rank"].append(st.rank)
+                if betas is not None:
+                    keep["dnll"].append(st.dnll)
 
     with torch.no_grad(), dec.inference(input_rows=True):
         if S == 0:
@@ -947,24 +953,219 @@ def evaluate_report(model, source, seq_len, eval_batch_size=None, mc_samples=0, 
                     keep["tgt"].append(targets)
                     keep["pos"].append(pos)
     # one copy to the host: every float32 array side by side, the integers likewise
-    fl = [k for k in ("nll", "conf", "entropy", "h_pred", "mi") if keep[k]]
+    fl = [k for k in ("nll", "conf", "entropy", "dnll", "h_pred", "mi") if keep[k]]
     n_tok = sum(t.numel() for t in keep["tgt"])
     host = {}
     if n_tok:
-        packed = torch.stack([torch.cat(keep[k]) for k in fl]).cpu().numpy()
-        host = {k: packed[j] for j, k in enumerate(fl)}
+        if betas is None:
+            packed = torch.stack([torch.cat(keep[k]) for k in fl]).cpu().numpy()
+            host = {k: packed[j] for j, k in enumerate(fl)}
+        else:  # the tempered fields are (J, tokens), the Monte-Carlo ones one row each
+            rows = [torch.cat(keep[k], -1).reshape(-1, n_tok) for k in fl]
+            packed, at = torch.cat(rows).cpu().numpy(), 0
+            for k, r in zip(fl, rows):
+                host[k] = packed[at:at + r.shape[0]] if k in ("nll", "conf", "entropy", "dnll") else packed[at]
+                at += r.shape[0]
         host["tgt"] = torch.cat(keep["tgt"]).cpu().numpy()
         if keep["rank"]:
             host["pred"], host["rank"] = torch.stack([torch.cat(keep["pred"]), torch.cat(keep["rank"])]).cpu().numpy()
         if keep["nll_s"]:
             host["nll_s"] = torch.cat(keep["nll_s"]).cpu().numpy()
     else:
-        host = {"nll": np.zeros(0, np.float32), "tgt": np.zeros(0, np.int64)}
+        z = np.zeros(0, np.float32) if betas is None else np.zeros((len(betas), 0), np.float32)
+        host = {"nll": z, "tgt": np.zeros(0, np.int64)}
+        if betas is not None:
+            host.update(conf=z, entropy=z, dnll=z, rank=np.zeros(0, np.int32), pred=np.zeros(0, np.int32))
+    return host, keep["pos"], V, S
+
+
+def _float32_beta(who, value, name):
+    """``value`` as the float32 inverse temperature the kernel is given; refuses what is not positive and finite."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    with np.errstate(over="ignore"):  # a value past float32 becomes inf and is refused below
+        b = float(np.float32(v)) if math.isfinite(v) else v
+    if not (math.isfinite(v) and v > 0.0 and math.isfinite(b) and b > 0.0):
+        raise ops.BayesLMError("%s: %s = %r is not a positive finite number (in float32)" % (who, name, value))
+    return b
+
+
+def evaluate_report(model, source, seq_len, eval_batch_size=None, mc_samples=0, seed=1111, bins=15, calibration=True,
+                    keep_tokens=False, temperature=1.0):
+    """Held-out loss / perplexity, accuracy and calibration of ``model`` over the batchified stream ``source``, at mean weights
+    (``mc_samples`` 0) or under the average of S = ``mc_samples`` >= 2 Monte-Carlo weight samples -> EvalReport.
+
+    The walk is engine.evaluate's (same windows, same grouping: _report_windows) with the decoder handing back its input rows;
+    those go through the decoder in chunks of _REPORT_ROWS rows and blm_row_stats reduces each chunk's (rows, V) matrix to
+    per-token NLL, confidence, entropy, prediction and rank in one read.  The per-token float32 arrays stay on the device
+    until the walk is over, come to the host in one copy, and every sum is formed there in float64 (report_from_tokens).
+
+    mc_samples = S: S passes per batch in the n-best scorer's sampling state (model.mc_sampling(model, seed, S), sample s
+    selected with set_step(s)): sample s is ONE model for the whole text, and a recurrent model carries S (h, c) sets from window
+    to window.  The model average is taken PER TOKEN, pbar(w | history) = mean_s p_s(w | history) -- a normalised distribution
+    over word sequences, whose NLL is ``loss`` -- not the scorer's sentence-level -log mean_s exp(-NLL_s(sentence)).  One launch
+    per chunk keeps log pbar with nll_s, bma_nll, h_pred and mi (ops.linear_mc_logprobs), and blm_row_stats reads log pbar.
+    ``calibration`` False under Monte-Carlo: ops.linear_mc_stats instead -- nothing of width V is stored, and the report has no
+    accuracy / confidence / calibration block (at mean weights the chunk's logits exist either way and the flag changes nothing).
+
+    ``temperature`` T: exactly 1.0 launches what is described above.  Any other positive finite T sends each chunk through
+    blm_row_stats_temps with beta = float32(1 / T) instead, and loss, ppl, mean_conf, mean_entropy, ece and bins are those of the
+    tempered distribution p_beta ~ exp(beta x) -- for a model average pbar^beta / Z, one parameter on top of the average; under
+    Monte-Carlo ``loss`` is then the kernel's tempered NLL of log pbar, not bma_nll.  accuracy and top5_accuracy do not depend on
+    T; sample_loss*, mean_h_pred and mean_mi stay the UNTEMPERED quantities of ops.linear_mc_logprobs.  The report's
+    ``temperature`` block (temperature_block) names T and beta.
+
+    Refused: mc_samples 1; a model without variational sites or with local reparameterisation (mc_sampling's refusals); cells that
+    redraw noise at every time step of a call (as IncrementalLM refuses them); a temperature that is not positive and finite, and
+    one other than 1.0 with mc_samples > 0 and calibration=False, where no row of width V exists.  ``eval_batch_size`` is accepted
+    for symmetry with the reference's evaluate and unused, like there.  Single process only.  The model is left in eval mode with
+    the caller's noise (seed, step, auto_step)."""
+    betas = None
+    if _float32_beta("evaluate_report", temperature, "temperature") and float(temperature) != 1.0:
+        betas = [_float32_beta("evaluate_report", 1.0 / float(temperature), "1 / temperature")]
+    host, pos, V, S = _report_walk("evaluate_report", model, source, seq_len, mc_samples, seed, calibration, betas)
+    if betas is not None:
+        host = {k: (v[0] if k in ("nll", "conf", "entropy", "dnll") else v) for k, v in host.items()}
     valid = (host["tgt"] >= 0) & (host["tgt"] < V)
     rep = report_from_tokens(host["nll"], host.get("conf"), host.get("entropy"), host.get("rank"), valid, bins,
                              host.get("nll_s"), host.get("h_pred"), host.get("mi"))
     rep.mc_samples = S
+    if betas is not None:
+        rep.temperature = temperature_block(betas[0])
     if keep_tokens:
-        order = np.argsort(np.concatenate(keep["pos"])) if n_tok else np.zeros(0, np.int64)
+        order = np.argsort(np.concatenate(pos)) if len(host["tgt"]) else np.zeros(0, np.int64)
         rep.per_token = {k: v[order] for k, v in host.items()}
     return rep
+
+
+def evaluate_temperatures(model, source, seq_len, betas, mc_samples=0, seed=1111, bins=15):
+    """evaluate_report at the 1..8 inverse temperatures ``betas`` (beta = 1 / T, each rounded to float32) from ONE walk of the
+    text -> (one EvalReport per beta, the mean d nll / d beta per beta).  blm_row_stats_temps reduces each chunk's (rows, V)
+    matrix for every beta in the same single read; windows, chunks, the single host copy and the float64 sums are
+    evaluate_report's, and so are its refusals and what stays untempered under Monte-Carlo.  The report of beta is what
+    evaluate_report(temperature=1 / beta) returns (at beta = 1 too: here that entry goes through the same kernel as the others).
+    The summed NLL is convex in beta, so the second result changes sign at most once: TemperatureSearch rests on that."""
+    try:
+        betas = list(betas)
+    except TypeError:
+        raise ops.BayesLMError("evaluate_temperatures: betas must be 1..8 positive finite numbers, got %r" % (betas,))
+    if not 1 <= len(betas) <= 8:
+        raise ops.BayesLMError("evaluate_temperatures: %d inverse temperatures, one walk takes 1..8" % len(betas))
+    bs = [_float32_beta("evaluate_temperatures", b, "betas[%d]" % j) for j, b in enumerate(betas)]
+    host, _, V, S = _report_walk("evaluate_temperatures", model, source, seq_len, mc_samples, seed, True, bs)
+    valid = (host["tgt"] >= 0) & (host["tgt"] < V)
+    n = int(valid.sum())
+    reps, dloss = [], []
+    for j, b in enumerate(bs):
+        rep = report_from_tokens(host["nll"][j], host["conf"][j], host["entropy"][j], host.get("rank"), valid, bins,
+                                 host.get("nll_s"), host.get("h_pred"), host.get("mi"))
+        rep.mc_samples = S
+        rep.temperature = temperature_block(b)
+        reps.append(rep)
+        dloss.append(float(host["dnll"][j].astype(np.float64)[valid].sum() / n) if n else float("nan"))
+    return reps, dloss
+
+
+class TemperatureSearch:
+    """Host-side search for the inverse temperature that minimises a held-out NLL, from its value and slope on grids of
+    ``points`` betas (one walk of the text each: evaluate_temperatures).  The NLL is convex in beta, so its slope changes sign
+    at most once, from - to +; the search keeps the bracket [a, b] with slope(a) < 0 < slope(b).
+
+        grid()     the next betas (float32 values): geometric over [1/8, 8] (cut to [lo, hi]) the first time, then geometric
+                   over the bracket, ends included -- each pass divides the bracket's log-width by points - 1.  While the
+                   slope has one sign on everything seen, the grid spans from the last end to the bound on that side.
+        update()   takes the betas, their mean NLL and mean slope; a non-finite one raises, naming beta.
+        result()   beta: the root of the secant through the bracket's two slopes; the bound with ``at_bound`` set once the
+                   slope at lo is still > 0 or at hi still < 0; before that the seen beta whose slope is nearest 0.
+        bracket    (a, b): what is known to hold the minimiser within [lo, hi]; nested from one update to the next."""
+
+    def __init__(self, lo=1.0 / 16, hi=16.0, points=8):
+        self.lo, self.hi, self.points = float(np.float32(lo)), float(np.float32(hi)), int(points)  # betas are float32 values
+        if not (0.0 < self.lo < self.hi < math.inf):
+            raise ops.BayesLMError("TemperatureSearch: need 0 < lo < hi < inf, got lo = %r, hi = %r" % (lo, hi))
+        if not 2 <= self.points <= 8:
+            raise ops.BayesLMError("TemperatureSearch: points = %r outside 2..8, what one walk evaluates" % (points,))
+        self.seen = {}  # beta -> (loss, dloss)
+        self.at_bound = False
+
+    def _ends(self):
+        """(a, b): the greatest seen beta with slope < 0 and the least with slope > 0 (None: none yet)"""
+        neg = [b for b, (_, d) in self.seen.items() if d < 0]
+        pos = [b for b, (_, d) in self.seen.items() if d >= 0]
+        return (max(neg) if neg else None), (min(pos) if pos else None)
+
+    @property
+    def bracket(self):
+        a, b = self._ends()
+        return (self.lo if a is None else a), (self.hi if b is None else b)
+
+    @property
+    def done(self):
+        """nothing left to learn: at a bound, or a slope of exactly 0 was seen"""
+        a, b = self._ends()
+        return self.at_bound or (b is not None and self.seen[b][1] == 0)
+
+    def grid(self):
+        a, b = self.bracket if self.seen else (max(self.lo, 0.125), min(self.hi, 8.0))
+        g = np.exp(np.linspace(math.log(a), math.log(b), self.points))
+        g[0], g[-1] = a, b
+        return sorted({min(self.hi, max(self.lo, float(np.float32(v)))) for v in g})
+
+    def update(self, betas, loss, dloss):
+        for b, l, d in zip(betas, loss, dloss):
+            b, l, d = float(b), float(l), float(d)
+            if not (math.isfinite(l) and math.isfinite(d)):
+                raise ops.BayesLMError("TemperatureSearch: loss %r with slope %r at beta = %r is not finite (a target the model "
+                                       "gives probability 0, or a NaN in its output)" % (l, d, b))
+            self.seen[b] = (l, d)
+        a, b = self._ends()
+        lo_seen, hi_seen = min(self.seen), max(self.seen)
+        self.at_bound = (a is None and lo_seen <= self.lo) or (b is None and hi_seen >= self.hi)
+
+    def result(self):
+        if not self.seen:
+            raise ops.BayesLMError("TemperatureSearch.result: nothing evaluated yet")
+        a, b = self._ends()
+        if a is not None and b is not None:
+            da, db = self.seen[a][1], self.seen[b][1]
+            return a - da * (b - a) / (db - da)
+        return b if a is None else a  # one sign throughout: the end on the minimiser's side (the bound once at_bound)
+
+
+@dataclasses.dataclass
+class TemperatureFit:
+    """What fit_temperature returns."""
+    temperature: float   # 1 / beta
+    beta: float          # the fitted inverse temperature, a float32 value: what evaluate_report(temperature=...) hands the kernel
+    at_bound: bool       # the NLL still fell at the search's lo or hi: beta is that bound, not a minimiser
+    passes: int          # search walks run (the walk that fills before / after not counted)
+    curve: list          # [beta, loss, dloss, ece] of every beta evaluated, in the order evaluated
+    before: EvalReport   # the fit text at beta = 1
+    after: EvalReport    # the fit text at beta
+
+
+def fit_temperature(model, source, seq_len, mc_samples=0, seed=1111, bins=15, passes=3, lo=1.0 / 16, hi=16.0, points=8):
+    """Temperature scaling (Guo et al. 2017): the one scalar T = 1 / beta that minimises the NLL of ``model`` on the held-out
+    stream ``source``, at mean weights or under the average of ``mc_samples`` weight samples (where it tempers the AVERAGE:
+    pbar^beta / Z) -> TemperatureFit.  ``passes`` walks of the text evaluate ``points`` betas each (evaluate_temperatures: one
+    read of every chunk for all of them) and narrow TemperatureSearch's bracket -- three passes of eight leave a ratio of
+    64^(1/343) = 1.012 between its ends, and the secant through the two slopes places beta inside it; the search stops early at a
+    bound.  A last walk over [1, beta] fills ``before`` and ``after``.  Refuses what evaluate_report refuses, and passes < 1."""
+    if int(passes) < 1:
+        raise ops.BayesLMError("fit_temperature: passes = %r, at least one search walk is needed" % (passes,))
+    search = TemperatureSearch(lo, hi, points)
+    curve, done = [], 0
+    for _ in range(int(passes)):
+        betas = search.grid()
+        reps, dloss = evaluate_temperatures(model, source, seq_len, betas, mc_samples, seed, bins)
+        search.update(betas, [r.loss for r in reps], dloss)
+        curve += [[b, r.loss, d, r.ece] for b, r, d in zip(betas, reps, dloss)]
+        done += 1
+        if search.done:
+            break
+    beta = float(np.float32(search.result()))
+    (before, after), dloss = evaluate_temperatures(model, source, seq_len, [1.0, beta], mc_samples, seed, bins)
+    curve += [[b, r.loss, d, r.ece] for b, r, d in zip((1.0, beta), (before, after), dloss)]
+    return TemperatureFit(1.0 / beta, beta, search.at_bound, done, curve, before, after)

@@ -2365,6 +2365,68 @@ def row_stats(x, targets=None, V=None):
     return RowStats(nll, conf, entropy, pred, rank)
 
 
+class RowStatsTemps(NamedTuple):
+    """RowStats at J inverse temperatures (include/bayeslm.h, blm_row_stats_temps): the float fields are (J, R), row j the
+    figures of the tempered distribution p ~ exp(betas[j] x)."""
+    nll: Optional[torch.Tensor]   # (J, R) float32; None without targets
+    conf: torch.Tensor            # (J, R) float32
+    entropy: torch.Tensor         # (J, R) float32
+    dnll: Optional[torch.Tensor]  # (J, R) float32 d nll / d beta = E_beta[x] - x[target]; None without targets
+    pred: torch.Tensor            # (R,) int32, the same at every temperature
+    rank: Optional[torch.Tensor]  # (R,) int32, likewise; None without targets
+
+
+def row_temps(betas, what="row_stats_temps"):
+    """The blm_row_temps struct of 1..8 positive finite inverse temperatures, each rounded to float32 once."""
+    try:
+        bs = [float(b) for b in betas]
+    except (TypeError, ValueError):
+        raise BayesLMError("%s: betas must be 1..%d positive finite numbers, got %r" % (what, L.ROW_TEMPS_MAX, betas))
+    if not 1 <= len(bs) <= L.ROW_TEMPS_MAX:
+        raise BayesLMError("%s: %d inverse temperatures, blm_row_stats_temps takes 1..%d per launch" % (what, len(bs), L.ROW_TEMPS_MAX))
+    t = L.RowTemps()
+    t.abi_version, t.count = L.ABI_VERSION, len(bs)
+    for j, b in enumerate(bs):
+        t.beta[j] = b if math.isfinite(b) else 0.0  # ctypes rounds to float32 (an overflow to inf is caught below)
+        if not (math.isfinite(b) and b > 0.0 and 0.0 < t.beta[j] < math.inf):
+            raise BayesLMError("%s: betas[%d] = %r is not a positive finite float32 inverse temperature" % (what, j, b))
+    return t
+
+
+def row_stats_temps(x, betas, targets=None, V=None):
+    """ops.row_stats at the J = len(betas) <= 8 inverse temperatures ``betas`` (beta = 1 / T > 0) from ONE read of x
+    (blm_row_stats_temps): per temperature the NLL of the target, the confidence, the entropy and d nll / d beta of the tempered
+    distribution p ~ exp(beta x); prediction and rank do not depend on beta.  Argument rules of row_stats (row stride honoured).
+    Temperature j's figures are bit-identical whatever else is in the list.  -> RowStatsTemps"""
+    temps = row_temps(betas)
+    J = temps.count
+    if torch.is_tensor(x) and x.dim() == 2 and x.stride(-1) == 1 and x.stride(0) >= x.shape[1] and not x.is_contiguous():
+        dev_tensor(x[:1], "x")  # the device checks of the product path; the view itself is what the kernel reads
+    else:
+        x = _f32(x, "x")
+    if x.dim() != 2 or x.stride(-1) != 1:
+        raise BayesLMError("row_stats_temps: a row-major (R, V) matrix expected")
+    R, V = x.shape[0], int(V if V is not None else x.shape[1])
+    if not 1 <= V <= x.shape[1]:
+        raise BayesLMError("row_stats_temps: V = %d outside [1, %d], the columns of x" % (V, x.shape[1]))
+    dev = x.device
+    conf, entropy = (torch.empty(J, R, device=dev, dtype=torch.float32) for _ in range(2))
+    pred = torch.empty(R, device=dev, dtype=torch.int32)
+    tgt = nll = dnll = rank = None
+    if targets is not None:
+        tgt = dev_tensor(targets.reshape(-1), "targets", torch.int64)
+        if tgt.numel() != R:
+            raise BayesLMError("row_stats_temps: %d targets for %d rows" % (tgt.numel(), R))
+        nll, dnll = (torch.empty(J, R, device=dev, dtype=torch.float32) for _ in range(2))
+        rank = torch.empty(R, device=dev, dtype=torch.int32)
+    if R == 0:
+        return RowStatsTemps(nll, conf, entropy, dnll, pred, rank)
+    L.require_gfx950()
+    calls().blm_row_stats_temps(ptr(x), x.stride(0) if R > 1 else max(x.stride(0), V), ptr(tgt), R, V, C.byref(temps), ptr(nll),
+                                ptr(conf), ptr(entropy), ptr(dnll), ptr(pred), ptr(rank), stream())
+    return RowStatsTemps(nll, conf, entropy, dnll, pred, rank)
+
+
 def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=1.0):
     """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
     with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64

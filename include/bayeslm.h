@@ -549,6 +549,28 @@ int blm_sample_rows(const float* x, int64_t ldx, int R, int V, float temperature
  * fixed order without atomics: the same bits in every run.  No workspace. */
 int blm_row_stats(const float* x, int64_t ldx, const int64_t* tgt, int R, int V, float* nll, float* conf, float* entropy,
                   int32_t* pred, int32_t* rank, void* stream);
+/* blm_row_stats at several temperatures from the same single read of x (temperature scaling: engine.evaluate_temperatures,
+ * engine.fit_temperature).  For an inverse temperature b = 1 / T > 0 the tempered distribution of a row is p_b ~ exp(b x) --
+ * for a row of log pbar that is pbar^b / Z.  With m = max x, d = x - m, s = sum exp(b d) and r = sum exp(b d) d / s = E_b[x] - m:
+ *   nll = b (m - x[tgt]) + log s;  conf = 1 / s;  entropy = log s - b r;  dnll = d nll / d b = (m - x[tgt]) + r.
+ * pred and rank are blm_row_stats' and do not depend on b.  The list travels in this host struct, read before the launch and
+ * handed to the kernel by value: no device memory, no copy. */
+#define BLM_ROW_TEMPS_MAX 8
+typedef struct blm_row_temps {
+  uint32_t abi_version; /* BLM_ABI_VERSION */
+  int32_t count;        /* 1 .. BLM_ROW_TEMPS_MAX */
+  float beta[BLM_ROW_TEMPS_MAX]; /* beta[j] finite and > 0 for j < count; the others are not read */
+} blm_row_temps;
+/* x, ldx, tgt, R, V as for blm_row_stats.  nll / conf / entropy / dnll: (count, R) contiguous, temperature j's figure of row r
+ * at [j * R + r], each may be NULL; pred / rank (R), each may be NULL; nll, dnll and rank need tgt.  Kernel forms exist for 1,
+ * 2, 4 and 8 temperatures, a count in between runs the next larger one with its surplus slots idle and unwritten.  The figures
+ * of beta[j] are bit-identical whatever else the list holds and wherever in the list it stands, and the same in every run.  A
+ * row that holds a NaN, a target outside [0, V) and a target at -inf (nll = dnll = +inf) are answered as blm_row_stats answers
+ * them, in every temperature's slot.  BLM_ERR_INVALID, before any launch: NULL x or temps, count outside
+ * 1..BLM_ROW_TEMPS_MAX, a beta that is not finite or not > 0, R < 0, V <= 0, ldx < V, nll / dnll / rank without tgt, extents too
+ * large; BLM_ERR_ABI: abi_version.  R == 0: BLM_OK, nothing launched.  No workspace. */
+int blm_row_stats_temps(const float* x, int64_t ldx, const int64_t* tgt, int R, int V, const blm_row_temps* temps, float* nll,
+                        float* conf, float* entropy, float* dnll, int32_t* pred, int32_t* rank, void* stream);
 
 /* --------------------------------------------------------------------------
  * Search on the incremental path (csrc/beam.hip): the k best next words, beam selection, top-k / nucleus sampling.
