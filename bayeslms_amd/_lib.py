@@ -153,6 +153,9 @@ SIGNATURES = {
     "blm_ce_interp_fwd": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _i, _i, _vp]),
     "blm_ce_soft_fwd_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
     "blm_ce_soft_topk_fwd_bwd": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
+    "blm_ce_soft_temp_fwd_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
+    "blm_ce_soft_topk_temp_fwd_bwd": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i,
+                                           _vp]),
     "blm_linear_nll_ws_floats": (_i64, [_i, _i]),
     "blm_linear_nll": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "blm_linear_mc_stats_ws_floats": (_i64, [_i, _i, _i]),

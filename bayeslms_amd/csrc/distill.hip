@@ -9,6 +9,10 @@
 //   dz_v = ((1 - lambda) valid (p_v - [v = t]) + lambda (Q p_v - q_v)) grad_scale
 // One workgroup per row, every sum in a fixed order, no atomics: the same bits from every run.
 // blm_ce_soft_topk_fwd_bwd (below): the same loss against a SPARSE teacher row, the K best entries per token.
+// blm_ce_soft_temp_fwd_bwd / blm_ce_soft_topk_temp_fwd_bwd (further below): both with a softmax temperature on the soft term, in
+// kernels of their own; the kernels up to there are what temperature 1 runs and are not touched by them.
+#include <cmath>
+
 #include "blm_device.h"
 #include "blm_host.h"
 
@@ -382,6 +386,392 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_topk_kernel(const float* logits, 
   if (threadIdx.x == 0) topk_finish(row, valid, xt, lse, Q, qz, k, lambda, loss, nll, soft, kl, lse_out);
 }
 
+// ---- distillation temperature: blm_ce_soft_temp_fwd_bwd / blm_ce_soft_topk_temp_fwd_bwd (definitions: include/bayeslm.h) ----
+// The hard term stays at temperature 1, the soft term compares softmax(beta z) with the teacher raised to beta and renormalised
+// over its live entries, so one read of a row has to give both softmax(z) and softmax(beta z).  Three rounds per row:
+//   1. max z and max live l                                          (row_max2: one barrier pair)
+//   2. sum exp(z - m), s_b = sum exp(beta (z - m)), Z = sum e_v, A = sum e_v (z_v - m),  e_v = exp(beta (l_v - ml))
+//                                                                    (row_sum4: one barrier pair)
+//   3. the KL terms and the gradient, every exponent formed from the max-shifted values: log p = (z - m) - log sum,
+//      log p~ = beta (z - m) - log s_b, log q~ = beta (l - ml) - log Z
+// soft = log s_b - beta A / Z, which is lse_b - beta sum q~ z with the beta m of both terms cancelled before it is rounded.
+// The untempered kernels above are not touched: temperature 1 launches them.
+__device__ __forceinline__ float uniform(float v) {  // a value every lane holds alike (a row reduction's result): one SGPR, no VGPR
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ void row_max2(float& a, float& b, float (*red)[16]) {  // two maxima behind one barrier pair
+  a = wave_max(a);
+  b = wave_max(b);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { red[0][w] = a; red[1][w] = b; }
+  __syncthreads();
+  a = red[0][lane & 15];
+  b = red[1][lane & 15];
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    a = fmaxf(a, __shfl_xor(a, o, 64));
+    b = fmaxf(b, __shfl_xor(b, o, 64));
+  }
+  a = uniform(a);
+  b = uniform(b);
+}
+__device__ __forceinline__ void row_sum4(float& a, float& b, float& c, float& d, float (*red)[16]) {  // four sums, one barrier pair
+  a = wave_sum(a);
+  b = wave_sum(b);
+  c = wave_sum(c);
+  d = wave_sum(d);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; red[3][w] = d; }
+  __syncthreads();
+  a = uniform(fold16_sum(red[0][lane & 15]));
+  b = uniform(fold16_sum(red[1][lane & 15]));
+  c = uniform(fold16_sum(red[2][lane & 15]));
+  d = uniform(fold16_sum(red[3][lane & 15]));
+}
+
+struct TempRow {  // a row's constants of round 3, the same in every lane
+  float beta, m, logl, logs, ml, logZ;  // log p = (z - m) - logl,  log p~ = beta (z - m) - logs,  log q~ = beta (l - ml) - logZ
+  float hard, soft;                     // gradient = hard (p - onehot) + soft (p~ - q~)
+  float lse, sft;                       // outputs: the temperature-1 lse and the unscaled soft term
+  bool valid;
+};
+// rounds 1 and 2 leave (m, ml) and the four sums; a row without a live teacher entry (ml = -inf) has soft = kl = 0 and no soft
+// gradient: ml and log Z are set to 0 there so that log q~ = beta (-inf - 0) - 0 = -inf, q~ = 0, without an inf - inf
+__device__ __forceinline__ TempRow temp_row(float beta, float m, float ml, float l, float sb, float Z, float A, float lambda,
+                                            float scale, bool valid, float gscale) {
+  const bool has_q = ml > -INFINITY;
+  TempRow r;
+  r.beta = beta;
+  r.m = m;
+  r.logl = __logf(l);
+  r.logs = __logf(sb);
+  r.ml = has_q ? ml : 0.f;
+  r.logZ = has_q ? __logf(Z) : 0.f;
+  r.hard = valid ? (1.f - lambda) * gscale : 0.f;
+  r.soft = has_q ? lambda * scale * beta * gscale : 0.f;
+  r.lse = m + r.logl;
+  r.sft = has_q ? r.logs - beta * (A / Z) : 0.f;
+  r.valid = valid;
+  return r;
+}
+// one (z, l) pair of round 2: its terms of the four sums
+__device__ __forceinline__ void temp_acc(float z, float l, float beta, float m, float mls, float& sl, float& sb, float& Z, float& A) {
+  const float a = z - m, e = __expf(beta * (l - mls));
+  sl += __expf(a);
+  sb += __expf(beta * a);
+  Z += e;
+  A += e > 0.f ? e * a : 0.f;
+}
+// one element of round 3: its KL term (returned) and its gradient (g), the one-hot term apart
+__device__ __forceinline__ float temp_elem(float z, float l, const TempRow& r, float& g) {
+  const float a = z - r.m, lb = r.beta * a - r.logs, lt = r.beta * (l - r.ml) - r.logZ;
+  const float qt = __expf(lt);
+  g = r.hard * __expf(a - r.logl) + r.soft * (__expf(lb) - qt);
+  return qt > 0.f ? qt * (lt - lb) : 0.f;
+}
+// ... of a column the teacher row does not hold (top-k: every column of the dense sweep)
+__device__ __forceinline__ float temp_grad(float z, const TempRow& r) {
+  const float a = z - r.m;
+  return r.hard * __expf(a - r.logl) + r.soft * __expf(r.beta * a - r.logs);
+}
+__device__ __forceinline__ void temp_finish(long row, const TempRow& r, float xt, float k, float lambda, float scale,
+                                            float* __restrict__ loss, float* __restrict__ nll, float* __restrict__ soft,
+                                            float* __restrict__ kl, float* __restrict__ lse_out) {
+  const float n = r.valid ? r.lse - xt : 0.f;
+  loss[row] = (1.f - lambda) * n + lambda * scale * r.sft;
+  if (nll) nll[row] = n;
+  if (soft) soft[row] = r.sft;
+  if (kl) kl[row] = k;
+  if (lse_out) lse_out[row] = r.lse;
+}
+
+// ce_soft_row_kernel with a temperature: both rows in registers, each read from memory once; same requirements.
+template <int NV>
+__global__ __launch_bounds__(1024) void ce_soft_temp_row_kernel(const float* logits, long ld, const float* __restrict__ logq, long ldq,
+                                                                const int64_t* __restrict__ tgt, float lambda, float beta, float scale,
+                                                                float* __restrict__ loss, float* __restrict__ nll,
+                                                                float* __restrict__ soft, float* __restrict__ kl,
+                                                                float* __restrict__ lse_out, float* dlogits, float gscale, int V) {
+  __shared__ float red[4][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  const float* y = logq + row * ldq;
+  const unsigned t0 = threadIdx.x * 4u, Vu = (unsigned)V;
+  float4 v[NV], u[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {  // whole quads only; a quad outside the row reads quad 0 and is skipped wherever it is used
+    const unsigned j = t0 + 4096u * i;
+    const unsigned js = j + 3 < Vu ? j : 0u;
+    v[i] = *reinterpret_cast<const float4*>(x + js);
+    u[i] = *reinterpret_cast<const float4*>(y + js);
+  }
+  const unsigned je = (Vu & ~3u) + threadIdx.x;  // this thread's column behind the whole quads, if je < V
+  const bool extra = je < Vu;
+  const float ze = extra ? x[je] : -INFINITY, le = extra ? y[je] : -INFINITY;
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // read before any in-place gradient write (the reductions below have barriers)
+  const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;
+  float m = ze, ml = le;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;
+    m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
+    ml = fmaxf(ml, fmaxf(fmaxf(u[i].x, u[i].y), fmaxf(u[i].z, u[i].w)));
+  }
+  row_max2(m, ml, red);
+  const float mls = ml > -INFINITY ? ml : 0.f;
+  float sl = 0.f, sb = 0.f, Z = 0.f, A = 0.f;
+  temp_acc(ze, le, beta, m, mls, sl, sb, Z, A);  // ze = le = -inf without an extra column: four zeros
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;
+    temp_acc(v[i].x, u[i].x, beta, m, mls, sl, sb, Z, A);
+    temp_acc(v[i].y, u[i].y, beta, m, mls, sl, sb, Z, A);
+    temp_acc(v[i].z, u[i].z, beta, m, mls, sl, sb, Z, A);
+    temp_acc(v[i].w, u[i].w, beta, m, mls, sl, sb, Z, A);
+  }
+  row_sum4(sl, sb, Z, A, red);
+  const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
+  float* d = dlogits ? dlogits + row * ld : nullptr;
+  float ge;
+  float k = temp_elem(ze, le, r, ge);
+  if (d && extra) d[je] = tu == je ? ge - r.hard : ge;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const unsigned j = t0 + 4096u * i;
+    if (!(j + 3 < Vu)) continue;
+    float4 g;
+    k += (temp_elem(v[i].x, u[i].x, r, g.x) + temp_elem(v[i].y, u[i].y, r, g.y)) +
+         (temp_elem(v[i].z, u[i].z, r, g.z) + temp_elem(v[i].w, u[i].w, r, g.w));
+    if (d) {
+      g.x -= tu == j ? r.hard : 0.f;
+      g.y -= tu == j + 1 ? r.hard : 0.f;
+      g.z -= tu == j + 2 ? r.hard : 0.f;
+      g.w -= tu == j + 3 ? r.hard : 0.f;
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+  }
+  k = row_sum(k, red[0]);
+  if (threadIdx.x == 0) temp_finish(row, r, xt, k, lambda, scale, loss, nll, soft, kl, lse_out);
+}
+
+// Any V, any stride, any alignment: the three rounds as three sweeps over both rows (the second and third from L2 / the
+// Infinity Cache).  Every element is read and written by the same thread, and the first store lies behind the barriers of
+// round 2, so the in-place form needs no further ordering.
+__global__ __launch_bounds__(SOFT_TPB) void ce_soft_temp_kernel(const float* logits, long ld, const float* __restrict__ logq, long ldq,
+                                                                const int64_t* __restrict__ tgt, float lambda, float beta, float scale,
+                                                                float* __restrict__ loss, float* __restrict__ nll,
+                                                                float* __restrict__ soft, float* __restrict__ kl,
+                                                                float* __restrict__ lse_out, float* dlogits, float gscale, int V,
+                                                                int vec) {
+  __shared__ float red[4][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  const float* y = logq + row * ldq;
+  const int V4 = vec ? (V & ~3) : 0;
+  float m = -INFINITY, ml = -INFINITY;
+  for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + j), u = *reinterpret_cast<const float4*>(y + j);
+    m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+    ml = fmaxf(ml, fmaxf(fmaxf(u.x, u.y), fmaxf(u.z, u.w)));
+  }
+  for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) {
+    m = fmaxf(m, x[j]);
+    ml = fmaxf(ml, y[j]);
+  }
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // read before any in-place gradient write
+  row_max2(m, ml, red);
+  const float mls = ml > -INFINITY ? ml : 0.f;
+  float sl = 0.f, sb = 0.f, Z = 0.f, A = 0.f;
+  for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + j), u = *reinterpret_cast<const float4*>(y + j);
+    temp_acc(v.x, u.x, beta, m, mls, sl, sb, Z, A);
+    temp_acc(v.y, u.y, beta, m, mls, sl, sb, Z, A);
+    temp_acc(v.z, u.z, beta, m, mls, sl, sb, Z, A);
+    temp_acc(v.w, u.w, beta, m, mls, sl, sb, Z, A);
+  }
+  for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) temp_acc(x[j], y[j], beta, m, mls, sl, sb, Z, A);
+  row_sum4(sl, sb, Z, A, red);
+  const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
+  float* d = dlogits ? dlogits + row * ld : nullptr;
+  float k = 0.f;
+  for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + j), u = *reinterpret_cast<const float4*>(y + j);
+    float4 g;
+    k += (temp_elem(v.x, u.x, r, g.x) + temp_elem(v.y, u.y, r, g.y)) + (temp_elem(v.z, u.z, r, g.z) + temp_elem(v.w, u.w, r, g.w));
+    if (d) {
+      if (valid && t >= j && t < j + 4) {
+        if (t == j) g.x -= r.hard; else if (t == j + 1) g.y -= r.hard; else if (t == j + 2) g.z -= r.hard; else g.w -= r.hard;
+      }
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+  }
+  for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) {
+    float g;
+    k += temp_elem(x[j], y[j], r, g);
+    if (d) d[j] = (valid && j == t) ? g - r.hard : g;
+  }
+  k = row_sum(k, red[0]);
+  if (threadIdx.x == 0) temp_finish(row, r, xt, k, lambda, scale, loss, nll, soft, kl, lse_out);
+}
+
+// top-k with a temperature.  Thread j < K owns entry j as in the untempered kernels; an entry is LIVE when its id lies in
+// [0, V) and its logq is above -inf.  An entry with a good id and logq = -inf takes no part in the sums (l = -inf gives e = 0)
+// and still overwrites its column -- with the value the dense sweep wrote there.
+struct TempEntry {
+  unsigned id;  // 0xFFFFFFFF: an empty slot
+  float l, z;   // l = -inf, z = 0 in an empty slot
+};
+__device__ __forceinline__ TempEntry temp_entry(const int* __restrict__ ids, const float* __restrict__ logq, const float* x, int K, int V) {
+  TempEntry e = {0xFFFFFFFFu, -INFINITY, 0.f};
+  if ((int)threadIdx.x < K) {
+    const int id = ids[threadIdx.x];
+    if (id >= 0 && id < V) {
+      e.id = (unsigned)id;
+      e.l = logq[threadIdx.x];
+      e.z = x[id];
+    }
+  }
+  return e;
+}
+__device__ __forceinline__ void temp_fix(const TempEntry& e, const TempRow& r, unsigned tu, float* d) {
+  if (e.id == 0xFFFFFFFFu) return;
+  float g;
+  temp_elem(e.z, e.l, r, g);
+  d[e.id] = g - (tu == e.id ? r.hard : 0.f);
+}
+
+template <int NV>
+__global__ __launch_bounds__(1024) void ce_topk_temp_row_kernel(const float* logits, long ld, const int* __restrict__ ids,
+                                                                const float* __restrict__ logq, long ldk, int K,
+                                                                const int64_t* __restrict__ tgt, float lambda, float beta, float scale,
+                                                                float* __restrict__ loss, float* __restrict__ nll,
+                                                                float* __restrict__ soft, float* __restrict__ kl,
+                                                                float* __restrict__ lse_out, float* dlogits, float gscale, int V) {
+  __shared__ float red[4][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  const unsigned t0 = threadIdx.x * 4u, Vu = (unsigned)V;
+  float4 v[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {  // whole quads only; a quad outside the row reads quad 0 and is skipped wherever it is used
+    const unsigned j = t0 + 4096u * i;
+    v[i] = *reinterpret_cast<const float4*>(x + (j + 3 < Vu ? j : 0u));
+  }
+  const unsigned je = (Vu & ~3u) + threadIdx.x;  // this thread's column behind the whole quads, if je < V
+  const bool extra = je < Vu;
+  const float ze = extra ? x[je] : -INFINITY;
+  const TempEntry e = temp_entry(ids + row * ldk, logq + row * ldk, x, K, V);
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (the reductions below have barriers)
+  const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;
+  float m = ze, ml = e.l;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;
+    m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
+  }
+  row_max2(m, ml, red);
+  const float mls = ml > -INFINITY ? ml : 0.f;
+  float sl = __expf(ze - m), sb = __expf(beta * (ze - m));
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!(t0 + 4096u * i + 3 < Vu)) continue;
+    sl += __expf(v[i].x - m) + __expf(v[i].y - m) + __expf(v[i].z - m) + __expf(v[i].w - m);
+    sb += __expf(beta * (v[i].x - m)) + __expf(beta * (v[i].y - m)) + __expf(beta * (v[i].z - m)) + __expf(beta * (v[i].w - m));
+  }
+  float Z = __expf(beta * (e.l - mls)), A = Z > 0.f ? Z * (e.z - m) : 0.f;
+  row_sum4(sl, sb, Z, A, red);
+  const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
+  float gu;
+  const float k = row_sum(temp_elem(e.z, e.l, r, gu), red[0]);
+  if (dlogits) {
+    float* d = dlogits + row * ld;
+    if (extra) d[je] = temp_grad(ze, r) - (tu == je ? r.hard : 0.f);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const unsigned j = t0 + 4096u * i;
+      if (!(j + 3 < Vu)) continue;
+      float4 g;
+      g.x = temp_grad(v[i].x, r) - (tu == j ? r.hard : 0.f);
+      g.y = temp_grad(v[i].y, r) - (tu == j + 1 ? r.hard : 0.f);
+      g.z = temp_grad(v[i].z, r) - (tu == j + 2 ? r.hard : 0.f);
+      g.w = temp_grad(v[i].w, r) - (tu == j + 3 ? r.hard : 0.f);
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+    __syncthreads();  // every dense store of the row is behind this barrier; the K columns of the teacher are written after it
+    temp_fix(e, r, tu, d);
+  }
+  if (threadIdx.x == 0) temp_finish(row, r, xt, k, lambda, scale, loss, nll, soft, kl, lse_out);
+}
+
+// Any V, any stride, any alignment: ce_topk_kernel's two sweeps, the online pass carrying both sum exp(z - m) and s_b.
+__global__ __launch_bounds__(SOFT_TPB) void ce_topk_temp_kernel(const float* logits, long ld, const int* __restrict__ ids,
+                                                                const float* __restrict__ logq, long ldk, int K,
+                                                                const int64_t* __restrict__ tgt, float lambda, float beta, float scale,
+                                                                float* __restrict__ loss, float* __restrict__ nll,
+                                                                float* __restrict__ soft, float* __restrict__ kl,
+                                                                float* __restrict__ lse_out, float* dlogits, float gscale, int V,
+                                                                int vec) {
+  __shared__ float red[4][16];
+  const long row = blockIdx.x;
+  const float* x = logits + row * ld;
+  float mt = -INFINITY, sl = 0.f, sb = 0.f;
+  const int V4 = vec ? (V & ~3) : 0;
+  for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + j);
+    const float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+    if (mx > mt) { sl *= __expf(mt - mx); sb *= __expf(beta * (mt - mx)); mt = mx; }
+    if (mt > -INFINITY) {
+      sl += __expf(v.x - mt) + __expf(v.y - mt) + __expf(v.z - mt) + __expf(v.w - mt);
+      sb += __expf(beta * (v.x - mt)) + __expf(beta * (v.y - mt)) + __expf(beta * (v.z - mt)) + __expf(beta * (v.w - mt));
+    }
+  }
+  for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) {
+    const float v = x[j];
+    if (v > mt) { sl *= __expf(mt - v); sb *= __expf(beta * (mt - v)); mt = v; }
+    if (mt > -INFINITY) { sl += __expf(v - mt); sb += __expf(beta * (v - mt)); }
+  }
+  const TempEntry e = temp_entry(ids + row * ldk, logq + row * ldk, x, K, V);
+  const long t = tgt[row];
+  const bool valid = t >= 0 && t < V;
+  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (row_max2 has barriers)
+  const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;
+  float m = mt, ml = e.l;
+  row_max2(m, ml, red);
+  const float mls = ml > -INFINITY ? ml : 0.f;
+  sl = mt == -INFINITY ? 0.f : sl * __expf(mt - m);
+  sb = mt == -INFINITY ? 0.f : sb * __expf(beta * (mt - m));
+  float Z = __expf(beta * (e.l - mls)), A = Z > 0.f ? Z * (e.z - m) : 0.f;
+  row_sum4(sl, sb, Z, A, red);
+  const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
+  float gu;
+  const float k = row_sum(temp_elem(e.z, e.l, r, gu), red[0]);
+  if (dlogits) {
+    float* d = dlogits + row * ld;
+    for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {  // each element read and written by the same thread
+      const float4 v = *reinterpret_cast<const float4*>(x + j);
+      const unsigned ju = (unsigned)j;
+      float4 g;
+      g.x = temp_grad(v.x, r) - (tu == ju ? r.hard : 0.f);
+      g.y = temp_grad(v.y, r) - (tu == ju + 1 ? r.hard : 0.f);
+      g.z = temp_grad(v.z, r) - (tu == ju + 2 ? r.hard : 0.f);
+      g.w = temp_grad(v.w, r) - (tu == ju + 3 ? r.hard : 0.f);
+      *reinterpret_cast<float4*>(d + j) = g;
+    }
+    for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) d[j] = temp_grad(x[j], r) - (tu == (unsigned)j ? r.hard : 0.f);
+    __syncthreads();  // as in ce_topk_temp_row_kernel
+    temp_fix(e, r, tu, d);
+  }
+  if (threadIdx.x == 0) temp_finish(row, r, xt, k, lambda, scale, loss, nll, soft, kl, lse_out);
+}
+
 // deterministic single-block sum: out += sum(x[0..n))  (the fixed-order loss_sum of blm_ce_fwd_bwd)
 __global__ __launch_bounds__(1024) void soft_sum_kernel(const float* __restrict__ x, long n, float* out) {
   __shared__ float red[16];
@@ -396,23 +786,39 @@ __global__ __launch_bounds__(1024) void soft_sum_kernel(const float* __restrict_
 using namespace blm;
 #define ST static_cast<hipStream_t>(stream)
 
-extern "C" int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
-                                   float* loss, float* nll, float* soft, float* kl, float* lse, float* loss_sum, float* dlogits,
-                                   float grad_scale, int M, int V, void* stream) {
-  if (!logits || !logq || !tgt || !loss) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: logits, logq, tgt and loss are required");
-  if (M < 0 || V <= 0) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: M = %d, V = %d: M >= 0 and V > 0 expected", M, V);
+// The argument checks of the dense entry points, under the name `fn` of the one that was called -> BLM_OK to go on.
+static int soft_args(const char* fn, const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                     const float* loss, const float* dlogits, int M, int V) {
+  if (!logits || !logq || !tgt || !loss) return blm_fail(BLM_ERR_INVALID, "%s: logits, logq, tgt and loss are required", fn);
+  if (M < 0 || V <= 0) return blm_fail(BLM_ERR_INVALID, "%s: M = %d, V = %d: M >= 0 and V > 0 expected", fn, M, V);
   if (ld < V || ldq < V || !extents_ok({M, ld}) || !extents_ok({M, ldq}))
-    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: row strides ld = %lld, ldq = %lld must be >= V = %d (and M x stride an addressable extent)",
+    return blm_fail(BLM_ERR_INVALID, "%s: row strides ld = %lld, ldq = %lld must be >= V = %d (and M x stride an addressable extent)", fn,
                     (long long)ld, (long long)ldq, V);
-  if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: lambda = %g outside [0, 1]", (double)lambda);
+  if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "%s: lambda = %g outside [0, 1]", fn, (double)lambda);
   if (M == 0) return BLM_OK;
   const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), q0 = reinterpret_cast<uintptr_t>(logq), d0 = reinterpret_cast<uintptr_t>(dlogits);
   if (dlogits) {  // the gradient may be written over the logits it is the gradient of, element for element, and over nothing else read here
     const uintptr_t zn = ((uintptr_t)(M - 1) * (uintptr_t)ld + (uintptr_t)V) * 4, qn = ((uintptr_t)(M - 1) * (uintptr_t)ldq + (uintptr_t)V) * 4;
-    if (d0 < q0 + qn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: dlogits overlaps logq");
+    if (d0 < q0 + qn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logq", fn);
     if (d0 != z0 && d0 < z0 + zn && z0 < d0 + zn)
-      return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_fwd_bwd: dlogits overlaps logits without being logits itself (in place means dlogits == logits)");
+      return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logits without being logits itself (in place means dlogits == logits)", fn);
   }
+  return BLM_OK;
+}
+// ... and what the tempered entry points refuse beside: beta = 1 / T and the factor on the soft term
+static int temp_args(const char* fn, float beta, float soft_scale) {
+  if (!(beta > 0.f) || !std::isfinite(beta)) return blm_fail(BLM_ERR_INVALID, "%s: beta = %g: a finite inverse temperature > 0 expected", fn, (double)beta);
+  if (!(soft_scale >= 0.f) || !std::isfinite(soft_scale))
+    return blm_fail(BLM_ERR_INVALID, "%s: soft_scale = %g: a finite factor >= 0 expected", fn, (double)soft_scale);
+  return BLM_OK;
+}
+
+extern "C" int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                                   float* loss, float* nll, float* soft, float* kl, float* lse, float* loss_sum, float* dlogits,
+                                   float grad_scale, int M, int V, void* stream) {
+  if (const int bad = soft_args("blm_ce_soft_fwd_bwd", logits, ld, logq, ldq, tgt, lambda, loss, dlogits, M, V)) return bad;
+  if (M == 0) return BLM_OK;
+  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), q0 = reinterpret_cast<uintptr_t>(logq), d0 = reinterpret_cast<uintptr_t>(dlogits);
   const bool vec = ((ld & 3) == 0) && ((ldq & 3) == 0) && (((z0 | q0 | d0) & 15) == 0);
   if (vec && V >= 4 && V <= 4096 * 3)
     hipLaunchKernelGGL(ce_soft_row_kernel<3>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
@@ -431,32 +837,62 @@ extern "C" int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float*
   return BLM_OK;
 }
 
-extern "C" int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
-                                        const int64_t* tgt, float lambda, float* loss, float* nll, float* soft, float* kl, float* lse,
+extern "C" int blm_ce_soft_temp_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                                        float beta, float soft_scale, float* loss, float* nll, float* soft, float* kl, float* lse,
                                         float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream) {
+  if (const int bad = soft_args("blm_ce_soft_temp_fwd_bwd", logits, ld, logq, ldq, tgt, lambda, loss, dlogits, M, V)) return bad;
+  if (const int bad = temp_args("blm_ce_soft_temp_fwd_bwd", beta, soft_scale)) return bad;
+  if (M == 0) return BLM_OK;
+  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), q0 = reinterpret_cast<uintptr_t>(logq), d0 = reinterpret_cast<uintptr_t>(dlogits);
+  const bool vec = ((ld & 3) == 0) && ((ldq & 3) == 0) && (((z0 | q0 | d0) & 15) == 0);  // the forms of blm_ce_soft_fwd_bwd, by its conditions
+  if (vec && V >= 4 && V <= 4096 * 3)
+    hipLaunchKernelGGL(ce_soft_temp_row_kernel<3>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, beta,
+                       soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
+  else if (vec && V <= 4096 * 9)
+    hipLaunchKernelGGL(ce_soft_temp_row_kernel<9>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, beta,
+                       soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
+  else
+    hipLaunchKernelGGL(ce_soft_temp_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, beta, soft_scale,
+                       loss, nll, soft, kl, lse, dlogits, grad_scale, V, vec ? 1 : 0);
+  BLM_HIP(hipGetLastError());
+  if (loss_sum) {
+    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
+    BLM_HIP(hipGetLastError());
+  }
+  return BLM_OK;
+}
+
+// The argument checks of the top-k entry points, under the name `fn` of the one that was called -> BLM_OK to go on.
+static int topk_args(const char* fn, const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
+                     const int64_t* tgt, float lambda, const float* loss, const float* dlogits, int M, int V) {
   const char* missing = !logits ? "logits" : !ids ? "ids" : !logq ? "logq" : !tgt ? "tgt" : !loss ? "loss" : nullptr;
-  if (missing) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: %s is NULL (logits, ids, logq, tgt and loss are required)", missing);
-  if (M < 0 || V <= 0) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: M = %d, V = %d: M >= 0 and V > 0 expected", M, V);
-  if (K < 1 || K > BLM_TOPK_MAX)
-    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: K = %d outside [1, BLM_TOPK_MAX = %d]", K, BLM_TOPK_MAX);
+  if (missing) return blm_fail(BLM_ERR_INVALID, "%s: %s is NULL (logits, ids, logq, tgt and loss are required)", fn, missing);
+  if (M < 0 || V <= 0) return blm_fail(BLM_ERR_INVALID, "%s: M = %d, V = %d: M >= 0 and V > 0 expected", fn, M, V);
+  if (K < 1 || K > BLM_TOPK_MAX) return blm_fail(BLM_ERR_INVALID, "%s: K = %d outside [1, BLM_TOPK_MAX = %d]", fn, K, BLM_TOPK_MAX);
   if (ld < V || !extents_ok({M, ld}))
-    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: row stride ld = %lld must be >= V = %d (and M x ld an addressable extent)",
-                    (long long)ld, V);
+    return blm_fail(BLM_ERR_INVALID, "%s: row stride ld = %lld must be >= V = %d (and M x ld an addressable extent)", fn, (long long)ld, V);
   if (ldk < K || !extents_ok({M, ldk}))
-    return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: row stride ldk = %lld must be >= K = %d (and M x ldk an addressable extent)",
-                    (long long)ldk, K);
-  if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: lambda = %g outside [0, 1]", (double)lambda);
+    return blm_fail(BLM_ERR_INVALID, "%s: row stride ldk = %lld must be >= K = %d (and M x ldk an addressable extent)", fn, (long long)ldk, K);
+  if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "%s: lambda = %g outside [0, 1]", fn, (double)lambda);
   if (M == 0) return BLM_OK;
   const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), d0 = reinterpret_cast<uintptr_t>(dlogits);
   if (dlogits) {  // the gradient may be written over the logits it is the gradient of, element for element, and over nothing else read here
     const uintptr_t zn = ((uintptr_t)(M - 1) * (uintptr_t)ld + (uintptr_t)V) * 4, kn = ((uintptr_t)(M - 1) * (uintptr_t)ldk + (uintptr_t)K) * 4;
     const uintptr_t i0 = reinterpret_cast<uintptr_t>(ids), q0 = reinterpret_cast<uintptr_t>(logq);
-    if (d0 < i0 + kn && i0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: dlogits overlaps ids");
-    if (d0 < q0 + kn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "blm_ce_soft_topk_fwd_bwd: dlogits overlaps logq");
+    if (d0 < i0 + kn && i0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps ids", fn);
+    if (d0 < q0 + kn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logq", fn);
     if (d0 != z0 && d0 < z0 + zn && z0 < d0 + zn)
-      return blm_fail(BLM_ERR_INVALID,
-                      "blm_ce_soft_topk_fwd_bwd: dlogits overlaps logits without being logits itself (in place means dlogits == logits)");
+      return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logits without being logits itself (in place means dlogits == logits)", fn);
   }
+  return BLM_OK;
+}
+
+extern "C" int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
+                                        const int64_t* tgt, float lambda, float* loss, float* nll, float* soft, float* kl, float* lse,
+                                        float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream) {
+  if (const int bad = topk_args("blm_ce_soft_topk_fwd_bwd", logits, ld, ids, logq, ldk, K, tgt, lambda, loss, dlogits, M, V)) return bad;
+  if (M == 0) return BLM_OK;
+  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), d0 = reinterpret_cast<uintptr_t>(dlogits);
   const bool vec = ((ld & 3) == 0) && (((z0 | d0) & 15) == 0);
 #define TOPK_ROW(NV)                                                                                                                  \
   hipLaunchKernelGGL(ce_topk_row_kernel<NV>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, loss, \
@@ -468,6 +904,33 @@ extern "C" int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const i
     hipLaunchKernelGGL(ce_topk_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, loss, nll,
                        soft, kl, lse, dlogits, grad_scale, V, vec ? 1 : 0);
 #undef TOPK_ROW
+  BLM_HIP(hipGetLastError());
+  if (loss_sum) {
+    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
+    BLM_HIP(hipGetLastError());
+  }
+  return BLM_OK;
+}
+
+extern "C" int blm_ce_soft_topk_temp_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
+                                             const int64_t* tgt, float lambda, float beta, float soft_scale, float* loss, float* nll,
+                                             float* soft, float* kl, float* lse, float* loss_sum, float* dlogits, float grad_scale, int M,
+                                             int V, void* stream) {
+  if (const int bad = topk_args("blm_ce_soft_topk_temp_fwd_bwd", logits, ld, ids, logq, ldk, K, tgt, lambda, loss, dlogits, M, V)) return bad;
+  if (const int bad = temp_args("blm_ce_soft_topk_temp_fwd_bwd", beta, soft_scale)) return bad;
+  if (M == 0) return BLM_OK;
+  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), d0 = reinterpret_cast<uintptr_t>(dlogits);
+  const bool vec = ((ld & 3) == 0) && (((z0 | d0) & 15) == 0);  // the forms of blm_ce_soft_topk_fwd_bwd, by its conditions
+#define TOPK_TEMP_ROW(NV)                                                                                                                  \
+  hipLaunchKernelGGL(ce_topk_temp_row_kernel<NV>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, beta, \
+                     soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V)
+  if (vec && V >= 4 && V <= 4096 * 3) TOPK_TEMP_ROW(3);
+  else if (vec && V >= 4 && V <= 4096 * 9) TOPK_TEMP_ROW(9);
+  else if (vec && V >= 4 && V <= 4096 * 16) TOPK_TEMP_ROW(16);
+  else
+    hipLaunchKernelGGL(ce_topk_temp_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, beta,
+                       soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V, vec ? 1 : 0);
+#undef TOPK_TEMP_ROW
   BLM_HIP(hipGetLastError());
   if (loss_sum) {
     hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);

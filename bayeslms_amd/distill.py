@@ -13,6 +13,10 @@ in the same order in every epoch and the teacher is frozen, so its rows are comp
 without ``renorm`` the soft term of a row is weighted by the mass Q < 1 its k entries hold and the tail of the teacher is
 dropped; with ``renorm`` the target is the renormalised head (Q = 1).
 
+Neither the teacher nor the cache knows a softmax temperature: the losses take one (``temperature=`` of the two ops, a third
+entry of ``soft``), raise the rows handed out here to 1 / T and renormalise them, and a constant on a row cancels there -- so
+one cache file serves every temperature.
+
 A student is judged as every model is, by hard-label loss: ``python -m bayeslms_amd.evaluate`` on the student at mean weights,
 on the teacher at mean weights and on the teacher with ``--mc-samples S`` gives perplexity and calibration error of all three.
 """

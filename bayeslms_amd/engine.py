@@ -11,6 +11,7 @@ three flat buffers (train.py:419-420,466 semantics, averaged over ranks).
 import contextlib
 import dataclasses
 import datetime
+import gc
 import math
 import os
 import sys
@@ -105,13 +106,19 @@ def allreduce_busbw(nbytes, reps=5, device=None, group=None):
     dist.all_reduce(x, group=group)
     if cuda:
         torch.cuda.synchronize()
-    dist.barrier(group)
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        dist.all_reduce(x, group=group)
-    if cuda:
-        torch.cuda.synchronize()
-    el = (time.perf_counter() - t0) / reps
+    gc_was_on = gc.isenabled()
+    gc.disable()  # a full collection of the interpreter's heap takes tens of ms: it must not land between the two clock reads
+    try:
+        dist.barrier(group)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            dist.all_reduce(x, group=group)
+        if cuda:
+            torch.cuda.synchronize()
+        el = (time.perf_counter() - t0) / reps
+    finally:
+        if gc_was_on:
+            gc.enable()
     t = torch.tensor([el], dtype=torch.float64, device=device if cuda else "cpu")
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     el = float(t.item())
@@ -613,7 +620,9 @@ class Trainer:
         ops.cross_entropy_soft against the teacher's (T * B, V) log-probabilities takes the place of the hard-label cross entropy
         (weight 0 is that loss), everything else is the same step; the step's mean hard NLL, soft loss and KL(teacher || student)
         stay on the device as ``self.last_soft``.  ``soft`` = (ops.SparseTargets, weight): the same against the teacher's K best
-        entries per token (ops.cross_entropy_soft_topk).  Single process only."""
+        entries per token (ops.cross_entropy_soft_topk).  ``soft`` = (targets, weight, temperature): the soft term at that softmax
+        temperature T, times T ** 2 (the ops' ``temperature`` keyword); ``last_soft`` then holds the soft loss and the KL at
+        temperature, without that factor.  Single process only."""
         if soft is not None and self.world > 1:
             raise ops.BayesLMError("Trainer.step: soft targets with world = %d: data-parallel distillation is not built (the teacher's "
                                    "rows would have to follow each rank's batch columns); train the student in one process" % self.world)
@@ -637,7 +646,7 @@ class Trainer:
             mle, _ = ops.cross_entropy(out.view(-1, V), targets, unit_grad=True)
         else:
             soft_loss = ops.cross_entropy_soft_topk if isinstance(soft[0], ops.SparseTargets) else ops.cross_entropy_soft
-            mle, parts = soft_loss(out.view(-1, V), targets, soft[0], soft[1], unit_grad=True)
+            mle, parts = soft_loss(out.view(-1, V), targets, soft[0], soft[1], unit_grad=True, temperature=soft[2] if len(soft) > 2 else 1.0)
             self.last_soft = ops.SoftStats(parts.nll.mean(), parts.soft.mean(), parts.kl.mean())  # no host synchronisation
         kl = None
         if kl_fn is not None:

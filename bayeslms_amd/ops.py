@@ -1542,7 +1542,7 @@ class _CrossEntropySoft(torch.autograd.Function):
     upstream scalar."""
 
     @staticmethod
-    def forward(ctx, logits, targets, teacher_logp, weight, unit_grad):
+    def forward(ctx, logits, targets, teacher_logp, weight, unit_grad, temper=None):
         V = logits.shape[-1]
         whole = logits
         logits, ld = _rows2d(logits, V, "logits")  # rows padded to 4 floats (odd vocabulary, ops._Linear) are taken as they are
@@ -1574,8 +1574,12 @@ class _CrossEntropySoft(torch.autograd.Function):
             else:
                 grad = torch.empty(M, ld, device=dev, dtype=torch.float32)[:, :V]
         L.require_gfx950()
-        calls().blm_ce_soft_fwd_bwd(ptr(logits), ld, ptr(logq), ldq, ptr(targets), float(weight), ptr(rows), ptr(nll), ptr(soft), ptr(kl),
-                                    None, ptr(loss), ptr(grad), 1.0 / M, M, V, stream())
+        if temper is None:
+            calls().blm_ce_soft_fwd_bwd(ptr(logits), ld, ptr(logq), ldq, ptr(targets), float(weight), ptr(rows), ptr(nll), ptr(soft), ptr(kl),
+                                        None, ptr(loss), ptr(grad), 1.0 / M, M, V, stream())
+        else:  # (beta, soft_scale): the soft term at a temperature
+            calls().blm_ce_soft_temp_fwd_bwd(ptr(logits), ld, ptr(logq), ldq, ptr(targets), float(weight), temper[0], temper[1], ptr(rows),
+                                             ptr(nll), ptr(soft), ptr(kl), None, ptr(loss), ptr(grad), 1.0 / M, M, V, stream())
         if fuse:  # the buffer now holds the gradient: any other autograd consumer of the logits must fail, not read it
             torch.autograd.graph.increment_version(whole)
         ctx.meta = (whole if fuse else grad.view(whole.shape) if grad is not None else None, fuse)
@@ -1587,18 +1591,38 @@ class _CrossEntropySoft(torch.autograd.Function):
     def backward(ctx, g, _g_nll, _g_soft, _g_kl):
         grad, fuse = ctx.meta
         if g is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         if fuse:
-            return grad, None, None, None, None
+            return grad, None, None, None, None, None
         if getattr(ctx, "spent", False):  # the buffer was scaled by the first backward's upstream gradient
             raise BayesLMError("cross_entropy_soft: backward ran already and scaled the gradient buffer by its upstream gradient; a "
                                "second backward over a retained graph needs a second forward")
         ctx.spent = True
         grad.mul_(_f32(g.reshape(()), "g"))
-        return grad, None, None, None, None
+        return grad, None, None, None, None, None
 
 
-def cross_entropy_soft(logits, targets, teacher_logp, weight, unit_grad=False):
+def _temper(name, temperature, soft_scale):
+    """The ``temperature`` / ``soft_scale`` keywords of the distillation losses -> None (temperature 1 and factor 1: the untempered
+    entry point, as before the keywords existed) or (beta, c) = (float32(1 / T), soft_scale or T * T) for the tempered one."""
+    T = temperature
+    if isinstance(T, bool) or not isinstance(T, (int, float)) or not math.isfinite(T) or not T > 0:
+        raise BayesLMError("%s: temperature must be a finite float > 0, got %r" % (name, T))
+    beta = float(torch.tensor(1.0 / float(T), dtype=torch.float32))
+    if not (math.isfinite(beta) and beta > 0.0):
+        raise BayesLMError("%s: temperature %r: 1 / temperature = %r is no finite float32 > 0" % (name, T, beta))
+    c = soft_scale
+    if c is not None and (isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0):
+        raise BayesLMError("%s: soft_scale must be None (temperature ** 2) or a finite float >= 0, got %r" % (name, c))
+    if float(T) == 1.0 and (c is None or float(c) == 1.0):
+        return None
+    c = float(T) * float(T) if c is None else float(c)
+    if not math.isfinite(float(torch.tensor(c, dtype=torch.float32))):
+        raise BayesLMError("%s: soft_scale = %r (temperature %r) is no finite float32" % (name, c, T))
+    return beta, c
+
+
+def cross_entropy_soft(logits, targets, teacher_logp, weight, unit_grad=False, temperature=1.0, soft_scale=None):
     """Distillation loss -> (mean over the M rows of (1 - weight) nll + weight soft, SoftStats(nll, soft, kl)): ``soft`` is the
     cross entropy of softmax(logits) under the teacher's distribution exp(teacher_logp), ``nll`` the hard-label one against
     ``targets``, ``kl`` = KL(teacher || student) per row; definitions in include/bayeslm.h, blm_ce_soft_fwd_bwd -- one pass
@@ -1606,7 +1630,11 @@ def cross_entropy_soft(logits, targets, teacher_logp, weight, unit_grad=False):
     padded rows of ops.linear_mc_logprobs are read in place; -inf entries are zeros of the teacher).  ``weight``: a float in
     [0, 1]; 0 is ops.cross_entropy's loss.  As there, in grad mode with ``unit_grad=True`` (the trainers' contract: the loss
     enters the objective with coefficient exactly 1) the logits buffer is CONSUMED: it is overwritten with the gradient and
-    its version counter is bumped; with ``unit_grad=False`` the logits stay and the gradient has its own buffer."""
+    its version counter is bumped; with ``unit_grad=False`` the logits stay and the gradient has its own buffer.
+    ``temperature`` T (a finite float > 0) puts the soft term at a softmax temperature (include/bayeslm.h,
+    blm_ce_soft_temp_fwd_bwd): softmax(logits / T) against the teacher raised to 1 / T and renormalised, times ``soft_scale``
+    (None: T ** 2, Hinton's scaling); the hard term stays at temperature 1, and ``soft`` / ``kl`` of the result are the quantities
+    at temperature, without that factor.  T = 1 with ``soft_scale`` None or 1 is the untempered call, bit for bit."""
     if type(logits) is not torch.Tensor:
         logits = logits.as_subclass(torch.Tensor)  # model outputs are `Logits` in grad mode (below); the op wants the plain tensor
     if not torch.is_tensor(teacher_logp):
@@ -1616,7 +1644,8 @@ def cross_entropy_soft(logits, targets, teacher_logp, weight, unit_grad=False):
                            "no gradient is formed for it)")
     if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0:
         raise BayesLMError("cross_entropy_soft: weight must be a float in [0, 1], got %r" % (weight,))
-    loss, nll, soft, kl = _CrossEntropySoft.apply(logits, targets, teacher_logp, float(weight), unit_grad)
+    temper = _temper("cross_entropy_soft", temperature, soft_scale)
+    loss, nll, soft, kl = _CrossEntropySoft.apply(logits, targets, teacher_logp, float(weight), unit_grad, temper)
     return loss, SoftStats(nll, soft, kl)
 
 
@@ -1634,7 +1663,7 @@ class _CrossEntropySoftTopk(torch.autograd.Function):
     """_CrossEntropySoft with the teacher's dense rows replaced by SparseTargets: the same buffers, the same two gradient forms."""
 
     @staticmethod
-    def forward(ctx, logits, targets, ids, logq, weight, unit_grad):
+    def forward(ctx, logits, targets, ids, logq, weight, unit_grad, temper=None):
         V = logits.shape[-1]
         whole = logits
         logits, ld = _rows2d(logits, V, "logits")  # rows padded to 4 floats (odd vocabulary, ops._Linear) are taken as they are
@@ -1669,8 +1698,13 @@ class _CrossEntropySoftTopk(torch.autograd.Function):
             else:
                 grad = torch.empty(M, ld, device=dev, dtype=torch.float32)[:, :V]
         L.require_gfx950()
-        calls().blm_ce_soft_topk_fwd_bwd(ptr(logits), ld, ptr(ids), ptr(logq), K, K, ptr(targets), float(weight), ptr(rows), ptr(nll),
-                                         ptr(soft), ptr(kl), None, ptr(loss), ptr(grad), 1.0 / M, M, V, stream())
+        if temper is None:
+            calls().blm_ce_soft_topk_fwd_bwd(ptr(logits), ld, ptr(ids), ptr(logq), K, K, ptr(targets), float(weight), ptr(rows), ptr(nll),
+                                             ptr(soft), ptr(kl), None, ptr(loss), ptr(grad), 1.0 / M, M, V, stream())
+        else:  # (beta, soft_scale): the soft term at a temperature
+            calls().blm_ce_soft_topk_temp_fwd_bwd(ptr(logits), ld, ptr(ids), ptr(logq), K, K, ptr(targets), float(weight), temper[0],
+                                                  temper[1], ptr(rows), ptr(nll), ptr(soft), ptr(kl), None, ptr(loss), ptr(grad), 1.0 / M,
+                                                  M, V, stream())
         if fuse:  # the buffer now holds the gradient: any other autograd consumer of the logits must fail, not read it
             torch.autograd.graph.increment_version(whole)
         ctx.meta = (whole if fuse else grad.view(whole.shape) if grad is not None else None, fuse)
@@ -1682,24 +1716,26 @@ class _CrossEntropySoftTopk(torch.autograd.Function):
     def backward(ctx, g, _g_nll, _g_soft, _g_kl):
         grad, fuse = ctx.meta
         if g is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         if fuse:
-            return grad, None, None, None, None, None
+            return grad, None, None, None, None, None, None
         if getattr(ctx, "spent", False):  # the buffer was scaled by the first backward's upstream gradient
             raise BayesLMError("cross_entropy_soft_topk: backward ran already and scaled the gradient buffer by its upstream gradient; "
                                "a second backward over a retained graph needs a second forward")
         ctx.spent = True
         grad.mul_(_f32(g.reshape(()), "g"))
-        return grad, None, None, None, None, None
+        return grad, None, None, None, None, None, None
 
 
-def cross_entropy_soft_topk(logits, targets, sparse, weight, unit_grad=False):
+def cross_entropy_soft_topk(logits, targets, sparse, weight, unit_grad=False, temperature=1.0, soft_scale=None):
     """ops.cross_entropy_soft against the K best entries of the teacher per token instead of its dense rows -> (loss,
     SoftStats(nll, soft, kl)); definitions in include/bayeslm.h, blm_ce_soft_topk_fwd_bwd.  ``sparse``: SparseTargets(ids (M, K)
     int32, logq (M, K) float32) on the GPU, no gradient, 1 <= K <= BLM_TOPK_MAX, the live ids of a row distinct (ops.topk_rows'
     are); an id outside [0, V) is an empty slot.  The teacher's mass Q = sum_j exp(logq_j) of a row is carried as it is: with
     Q < 1 (top-k of a normalised teacher) the soft term weighs Q, and the tail of the teacher is dropped.  ``weight``,
-    ``unit_grad`` and what happens to the logits buffer: as ops.cross_entropy_soft."""
+    ``unit_grad`` and what happens to the logits buffer: as ops.cross_entropy_soft.  ``temperature``, ``soft_scale``: as there
+    (blm_ce_soft_topk_temp_fwd_bwd); the tempered target is the K entries raised to 1 / T and renormalised over the live ones, so
+    a constant on a row's logq -- renormalised targets or not -- changes nothing, and Q is not carried."""
     if type(logits) is not torch.Tensor:
         logits = logits.as_subclass(torch.Tensor)  # model outputs are `Logits` in grad mode (below); the op wants the plain tensor
     if not (isinstance(sparse, tuple) and len(sparse) == 2 and torch.is_tensor(sparse[0]) and torch.is_tensor(sparse[1])):
@@ -1712,7 +1748,8 @@ def cross_entropy_soft_topk(logits, targets, sparse, weight, unit_grad=False):
                            "no gradient is formed for it)")
     if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0:
         raise BayesLMError("cross_entropy_soft_topk: weight must be a float in [0, 1], got %r" % (weight,))
-    loss, nll, soft, kl = _CrossEntropySoftTopk.apply(logits, targets, ids, logq, float(weight), unit_grad)
+    temper = _temper("cross_entropy_soft_topk", temperature, soft_scale)
+    loss, nll, soft, kl = _CrossEntropySoftTopk.apply(logits, targets, ids, logq, float(weight), unit_grad, temper)
     return loss, SoftStats(nll, soft, kl)
 
 

@@ -122,12 +122,18 @@ def build_parser():
                         'The first epoch computes and stores them, every later epoch -- and every later run against the same '
                         'teacher, corpus, K and batch shape -- loads them and runs no teacher; a file written for anything else is '
                         'refused')
+    p.add_argument('--distill-temperature', type=float, default=1.0, metavar='T',
+                   help='new, optional (with --distill-from): the softmax temperature of the soft term, T in [1/16, 16] (Hinton et al. '
+                        '2015): the student\'s softmax(logits / T) is trained against the teacher raised to 1 / T and renormalised, '
+                        'times T^2; the hard-label term stays at temperature 1.  With --distill-top-k the K entries are renormalised '
+                        '(T other than 1 needs --distill-top-k-renorm 1), and one --distill-cache file serves every temperature')
     return p
 
 
 # the flags build_model reads: what --distill-teacher-args may set for the teacher
 TEACHER_FLAGS = ("model", "emsize", "nhid", "nlayers", "nhead", "uncertainty", "T_bayes_pos", "L_bayes_pos", "L_gauss_pos", "L_v_pos",
                  "T_gauss_pos", "T_v_pos", "dropout", "tied")
+DISTILL_T_LO, DISTILL_T_HI = 1.0 / 16, 16.0  # --distill-temperature: the default bounds of engine.TemperatureSearch
 
 
 def check_distill_args(args, world):
@@ -136,7 +142,7 @@ def check_distill_args(args, world):
         for flag, given in (("--distill-weight", args.distill_weight is not None), ("--distill-mc-samples", args.distill_mc_samples != 0),
                             ("--distill-teacher-args", args.distill_teacher_args is not None),
                             ("--distill-top-k", args.distill_top_k != 0), ("--distill-top-k-renorm", args.distill_top_k_renorm != 0),
-                            ("--distill-cache", bool(args.distill_cache))):
+                            ("--distill-cache", bool(args.distill_cache)), ("--distill-temperature", args.distill_temperature != 1.0)):
             if given:
                 raise SystemExit("%s needs --distill-from" % flag)
         return None
@@ -154,6 +160,14 @@ def check_distill_args(args, world):
     elif not 1 <= args.distill_top_k <= TOPK_MAX:
         raise SystemExit("--distill-top-k must lie in 1..%d, the most entries per token the sparse loss takes (got %d)"
                          % (TOPK_MAX, args.distill_top_k))
+    T = args.distill_temperature
+    if not math.isfinite(T):
+        raise SystemExit("--distill-temperature must be a finite number (got %r)" % T)
+    if not DISTILL_T_LO <= T <= DISTILL_T_HI:
+        raise SystemExit("--distill-temperature must lie in [1/16, 16], the range the evaluation's temperature search covers (got %r)" % T)
+    if T != 1.0 and args.distill_top_k and not args.distill_top_k_renorm:
+        raise SystemExit("--distill-temperature %r with --distill-top-k needs --distill-top-k-renorm 1: the tempered target is the K "
+                         "entries renormalised, and only then does T -> 1 meet the run without the flag" % T)
     if world > 1:
         raise SystemExit("--distill-from runs in a single process: data-parallel distillation is not built (world size %d)" % world)
     if (args.noise_source or os.environ.get("BLM_NOISE_SOURCE", "philox")) == "torch":
@@ -431,8 +445,12 @@ def main(argv=None, history=None):
                 cache = distill.TeacherCache(args.distill_cache, fields)
             except distill.CacheMismatch as e:
                 raise SystemExit("--distill-cache: %s" % e)
-        say("distilling from %s (%s), weight %g, %s" % (args.distill_from, type(teacher_model).__name__, args.distill_weight,
-                                                       "%d Monte-Carlo samples" % teacher.S if teacher.S else "mean weights"))
+        say("distilling from %s (%s), weight %g, %s%s" % (
+            args.distill_from, type(teacher_model).__name__, args.distill_weight,
+            "%d Monte-Carlo samples" % teacher.S if teacher.S else "mean weights",
+            "" if args.distill_temperature == 1.0 else
+            ", temperature %g (soft term times %g; soft and kd_kl below are at temperature)" % (args.distill_temperature,
+                                                                                               args.distill_temperature ** 2)))
         if topk:
             say("top-%d teacher targets%s: %s" % (
                 topk, " (renormalised)" if args.distill_top_k_renorm else "",
@@ -469,7 +487,7 @@ def main(argv=None, history=None):
                         cache.store(i * train_data.size(1), logq)
                 else:
                     logq, _ = teacher.logprobs(data)
-                loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn, soft=(logq, args.distill_weight))
+                loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn, soft=(logq, args.distill_weight, args.distill_temperature))
                 total_soft, total_kd = total_soft + trainer.last_soft.soft, total_kd + trainer.last_soft.kl
             total_loss = total_loss + loss  # stays on the device: one host sync per log interval (train.py:422 syncs per step)
             if batch % args.log_interval == 0 and batch > 0:

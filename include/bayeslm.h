@@ -717,6 +717,46 @@ int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int6
 int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
                              const int64_t* tgt, float lambda, float* loss, float* nll, float* soft, float* kl, float* lse,
                              float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream);
+/* The distillation loss with a softmax TEMPERATURE T on its soft term (Hinton et al. 2015): the hard-label term stays at
+ * temperature 1, the soft term compares softmax(z / T) with the teacher -- or the model average -- raised to 1 / T and
+ * renormalised.  Arguments as blm_ce_soft_fwd_bwd, with beta and soft_scale behind lambda.
+ * beta = 1/T > 0.  c = soft_scale >= 0.  z is a row of student logits.  t is the hard target.  valid = 0 <= t < V.
+ * Dense teacher row l (log-probabilities, defined up to a constant; -inf means a zero of the teacher):
+ *   live_v = l_v > -inf.   has_q = any live.   ml = max over live l_v.
+ *   e_v = exp(beta (l_v - ml)), and 0 where not live.   Z = sum e_v.
+ *   q~_v = e_v / Z.  This is the teacher (or model average) raised to beta and renormalised over its live entries: pbar^beta / Z.
+ *   m = max z.
+ *   lse = m + log sum exp(z_v - m).   p_v = exp((z_v - m) - log sum exp(z - m)).
+ *   s_beta = sum exp(beta (z_v - m)).   lse_beta = beta m + log s_beta.   p~_v = exp(beta (z_v - m) - log s_beta).
+ *   Both p and p~ are formed from the max-shifted logits, never as exp(beta z - lse_beta).
+ *   nll[m]  = valid ? lse - z_t : 0.
+ *   soft[m] = has_q ? lse_beta - beta sum_live q~_v z_v : 0.  This is the cross entropy of p~ under q~, unscaled.
+ *   kl[m]   = sum_live q~_v ((beta (l_v - ml) - log Z) - (beta (z_v - m) - log s_beta)).  It is summed term by term and is >= 0
+ *             up to rounding.
+ *   loss[m] = (1 - lambda) nll + lambda c soft.
+ *   dlogits[m,v] = ((1 - lambda) valid (p_v - [v = t]) + lambda c beta has_q (p~_v - q~_v)) grad_scale.  This is the gradient of
+ *             grad_scale * sum_m loss[m].
+ *   lse output: the temperature-1 lse, as blm_ce_soft_fwd_bwd's.
+ * The tempered target is always normalised (sum q~ = 1).  The untempered kernels carry Q = sum q as it is.  So at beta = 1, c = 1
+ * the two agree for a teacher row with Q = 1 and differ by the factor Q otherwise.  c = T^2 is Hinton's scaling: the soft
+ * gradient is then lambda T (p~ - q~), and its size does not fall as 1/T when T grows.
+ * BLM_ERR_INVALID, before any launch: everything blm_ce_soft_fwd_bwd refuses; a beta that is not finite or not > 0; a soft_scale
+ * that is negative or not finite.  The kernel forms, their conditions, the in-place gradient, loss_sum and the fixed order of
+ * every sum (no floating-point atomics: the same bits from every run) are blm_ce_soft_fwd_bwd's; the two-sweep form makes a
+ * third sweep here (maxima, sums, gradient). */
+int blm_ce_soft_temp_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                             float beta, float soft_scale, float* loss, float* nll, float* soft, float* kl, float* lse,
+                             float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream);
+/* ... against TOP-K teacher targets: arguments as blm_ce_soft_topk_fwd_bwd, with beta and soft_scale behind lambda.  Sparse
+ * (top-k) teacher row: the same definitions hold with "live" meaning 0 <= ids_j < V and logq_j > -inf, and z_v read at ids_j; a
+ * column that no live entry names has q~ = 0.  A constant added to a row's logq cancels in q~.  So targets stored renormalised
+ * or not give the same tempered loss, and one file of cached top-k targets serves every temperature.  On a dense teacher
+ * that is -inf outside the live ids this is blm_ce_soft_temp_fwd_bwd.  Refuses what blm_ce_soft_topk_fwd_bwd refuses, and beta /
+ * soft_scale as above; duplicate live ids as there. */
+int blm_ce_soft_topk_temp_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
+                                  const int64_t* tgt, float lambda, float beta, float soft_scale, float* loss, float* nll,
+                                  float* soft, float* kl, float* lse, float* loss_sum, float* dlogits, float grad_scale, int M,
+                                  int V, void* stream);
 
 
 /* dcoef[i,n] += sum_m g[m,n] * act_i(z[m,n]), i = tanh, sigmoid, relu, gelu: gradient of the GPNN

@@ -17,7 +17,13 @@ B. the step with the targets extracted ON THE FLY (teacher pass + top-k + studen
    complete CACHE on disk (distill.TeacherCache.load + student step, no teacher): the second is what every epoch after the
    first, and every later run against the same teacher, pays.
 
-usage: distill_probe.py [--top-k K] [kernel|step ...]   (default: both)"""
+--temperature T adds the tempered kernels (include/bayeslm.h, blm_ce_soft_temp_fwd_bwd) beside the untempered ones:
+A. blm_ce_soft_temp_fwd_bwd at beta = 1 / T, soft_scale = T^2 -- and with --top-k blm_ce_soft_topk_temp_fwd_bwd -- as further legs on
+   the same buffers, in the same rotation, in the same run; each is reported as a ratio to its untempered kernel, whose
+   source the temperature did not touch.
+B. the step against the mean-weight teacher's dense rows at temperature T and, with --top-k, from the complete cache at T.
+
+usage: distill_probe.py [--top-k K] [--temperature T] [kernel|step ...]   (default: both)"""
 import os
 import statistics
 import sys
@@ -38,7 +44,7 @@ def say(*a):
     print(*a, flush=True)
 
 
-def kernel_legs(V, top_k=0):
+def kernel_legs(V, top_k=0, temperature=1.0):
     from bayeslms_amd import _lib as L
     L.require_gfx950()
     R, NB, N = 8192, 3, 30
@@ -65,6 +71,16 @@ def kernel_legs(V, top_k=0):
             zs[k].data_ptr(), ld, ks[k][0].data_ptr(), ks[k][1].data_ptr(), top_k, top_k, tgt.data_ptr(), 0.5, f[0].data_ptr(),
             f[1].data_ptr(), f[2].data_ptr(), f[3].data_ptr(), None, total.data_ptr(), zs[k].data_ptr(), 1.0 / R, R, V, st)),
                  ("ops.topk_rows k = %d" % top_k, 1, lambda k: ops.topk_rows(qs[k][:, :V], top_k)))
+    if temperature != 1.0:
+        beta, scale = 1.0 / temperature, temperature * temperature
+        legs += (("blm_ce_soft_temp_fwd_bwd", 3, lambda k: c.blm_ce_soft_temp_fwd_bwd(
+            zs[k].data_ptr(), ld, qs[k].data_ptr(), ld, tgt.data_ptr(), 0.5, beta, scale, f[0].data_ptr(), f[1].data_ptr(), f[2].data_ptr(),
+            f[3].data_ptr(), None, total.data_ptr(), zs[k].data_ptr(), 1.0 / R, R, V, st)),)
+        if top_k:
+            legs += (("blm_ce_soft_topk_temp_fwd_bwd", 2, lambda k: c.blm_ce_soft_topk_temp_fwd_bwd(
+                zs[k].data_ptr(), ld, ks[k][0].data_ptr(), ks[k][1].data_ptr(), top_k, top_k, tgt.data_ptr(), 0.5, beta, scale,
+                f[0].data_ptr(), f[1].data_ptr(), f[2].data_ptr(), f[3].data_ptr(), None, total.data_ptr(), zs[k].data_ptr(), 1.0 / R, R,
+                V, st)),)
     us = {}
     for name, passes, fn in legs:
         for k in range(NB):
@@ -80,16 +96,22 @@ def kernel_legs(V, top_k=0):
             times.append(1e3 * e0.elapsed_time(e1) / N)
         us[name] = statistics.median(times)
         nbytes = passes * R * V * 4 + (2 * top_k * R * 4 if "soft_topk" in name else 0)
-        say("%-24s V %5d %8.1f us  %5.2f TB/s of the %d MB it must move" % (name, V, us[name], nbytes / us[name] / 1e6, nbytes // 10 ** 6))
+        say("%-29s V %5d %8.1f us  %5.2f TB/s of the %d MB it must move" % (name, V, us[name], nbytes / us[name] / 1e6, nbytes // 10 ** 6))
     say("soft / hard at V %d: %.2f x  (3 matrices against 2: 1.5 by bytes)" % (V, us["blm_ce_soft_fwd_bwd"] / us["blm_ce_fwd_bwd"]))
     if top_k:
         t = us["blm_ce_soft_topk_fwd_bwd"]
         say("top-%d / hard at V %d: %.2f x  (%.3f by bytes);  top-%d / dense soft: %.2f x%s" % (
             top_k, V, t / us["blm_ce_fwd_bwd"], (2 * V + 2 * top_k) / (2.0 * V), top_k, t / us["blm_ce_soft_fwd_bwd"],
             "" if t <= us["blm_ce_soft_fwd_bwd"] else "  SLOWER THAN THE DENSE KERNEL: the gather or the correction step is wrong, no result"))
+    if temperature != 1.0:
+        say("tempered / untempered dense soft at V %d, T = %g: %.2f x  (the same 3 matrices; 6 exponentials per element against 4)"
+            % (V, temperature, us["blm_ce_soft_temp_fwd_bwd"] / us["blm_ce_soft_fwd_bwd"]))
+        if top_k:
+            say("tempered / untempered top-%d at V %d, T = %g: %.2f x  (the same 2 matrices; 4 exponentials per element against 2)"
+                % (top_k, V, temperature, us["blm_ce_soft_topk_temp_fwd_bwd"] / us["blm_ce_soft_topk_fwd_bwd"]))
 
 
-def step_legs(top_k=0):
+def step_legs(top_k=0, temperature=1.0):
     T, B, V = 128, 64, bench.V
 
     def build():
@@ -118,7 +140,10 @@ def step_legs(top_k=0):
     legs = [(None, "plain"), (0, "dense"), (2, "dense"), (8, "dense")]
     if top_k:
         legs += [(0, "topk"), (8, "topk"), (0, "cache")]
-    for S, how in legs:
+    legs = [leg + (1.0,) for leg in legs]
+    if temperature != 1.0:
+        legs += [(0, "dense", temperature)] + ([(0, "cache", temperature)] if top_k else [])
+    for S, how, temp in legs:
         torch.manual_seed(7)
         student = build()
         tr = engine.Trainer(student, lr=0.1, clip=1.0, kl_scale=T / float(src.size(0)), seed=1111)
@@ -131,24 +156,29 @@ def step_legs(top_k=0):
             if teacher is None:
                 tr.step(data, tgt, None, kl_fn)
             elif how == "cache":
-                tr.step(data, tgt, None, kl_fn, soft=(cache.load(k * T * B, T * B, dev), 0.5))
+                tr.step(data, tgt, None, kl_fn, soft=(cache.load(k * T * B, T * B, dev), 0.5, temp))
             elif how == "topk":
-                tr.step(data, tgt, None, kl_fn, soft=(teacher.topk(data, top_k)[0], 0.5))
+                tr.step(data, tgt, None, kl_fn, soft=(teacher.topk(data, top_k)[0], 0.5, temp))
             else:
                 logq, _ = teacher.logprobs(data)
-                tr.step(data, tgt, None, kl_fn, soft=(logq, 0.5))
+                tr.step(data, tgt, None, kl_fn, soft=(logq, 0.5, temp))
             torch.cuda.synchronize()
             times.append(1e3 * (time.perf_counter() - t0))
         ms = statistics.median(times[3:])
         base = base or ms
         name = ("plain" if S is None else "top-%d from the cache, no teacher" % top_k if how == "cache" else
                 "teacher S = %d%s" % (S, ", top-%d on the fly" % top_k if how == "topk" else ""))
-        say("%-36s %8.2f ms per step  %5.2f x plain" % (name, ms, ms / base))
+        name += "" if temp == 1.0 else ", T = %g" % temp
+        say("%-43s %8.2f ms per step  %5.2f x plain" % (name, ms, ms / base))
         del student, tr, teacher
 
 
 if __name__ == "__main__":
-    argv, top_k = sys.argv[1:], 0
+    argv, top_k, temperature = sys.argv[1:], 0, 1.0
+    if "--temperature" in argv:
+        i = argv.index("--temperature")
+        temperature = float(argv[i + 1])
+        del argv[i:i + 2]
     if "--top-k" in argv:
         i = argv.index("--top-k")
         top_k = int(argv[i + 1])
@@ -156,7 +186,7 @@ if __name__ == "__main__":
     for w in (argv or ["kernel", "step"]):
         if w == "kernel":
             with torch.no_grad():
-                kernel_legs(33000, top_k)
-                kernel_legs(33278, top_k)
+                kernel_legs(33000, top_k, temperature)
+                kernel_legs(33278, top_k, temperature)
         else:
-            step_legs(top_k)
+            step_legs(top_k, temperature)
