@@ -149,6 +149,7 @@ SIGNATURES = {
     "blm_beam_select_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _i, C.POINTER(BeamPoolArgs),
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_sample_rows_filtered": (_i, [_vp, _i64, _i, _i, _f, _i, _f, _rngp, _vp, _vp]),
+    "blm_spec_accept": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _rngp, _vp, _vp, _vp, _vp, _vp]),
     "blm_ce_fwd_bwd": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
     "blm_ce_interp_fwd": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _i, _i, _vp]),
     "blm_ce_soft_fwd_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp]),

@@ -26,8 +26,17 @@ beside the beam (IncrementalLM.beam_search_pool): a hypothesis that ends leaves 
 every word, the pool is ranked by score / length ** ``--length-penalty`` (>= 0) INSIDE the loop, and the search stops once
 nothing alive can enter it.  ``--nbest`` may then go up to P (fewer lines are written when fewer hypotheses were found),
 ``--min-words M`` refuses a hypothesis of fewer than M words (the closing ``<s>`` counted), and ``--write-scores`` writes
-"rank score normalised-score length" with a trailing "unfinished" on a hypothesis that was still alive after ``--words`` words."""
+"rank score normalised-score length" with a trailing "unfinished" on a hypothesis that was still alive after ``--words`` words.
+
+``--speculate G`` samples speculatively (bayeslms_amd/speculative.py): a cheap draft proposes G words per stream, the model scores
+all G + 1 positions in one chunk and an accept / reject rule keeps a prefix and draws one more word; the words written are
+distributed exactly as without the flag (not the same words: the noise is keyed differently).  The draft is the model itself at
+its mean weights, which needs ``--mc-samples S`` >= 2 to be any cheaper than the target, or another checkpoint:
+``--draft-model-path student.pt``, shaped by ``--draft-args "--model Transformer ..."`` (this command line's own flags; only the
+model-shaping ones are read, the default is the target's own).  The run ends with one line on stderr: rounds, words per target
+chunk, acceptance rate.  Not built with it: ``--beam``, ``--top-k`` / ``--top-p`` and ``--write-uncertainty``."""
 import argparse
+import shlex
 import sys
 
 import torch
@@ -83,7 +92,62 @@ def build_parser():
                         'the three space-separated fields "word h_pred mi" (3 x --words fields per line, single spaces, no '
                         'header): the word as written to --outf, then %%.6g of the predictive entropy of the model average and of '
                         'the mutual information between the word and the weights (nats; the distribution the word was drawn from)')
+    p.add_argument('--speculate', type=int, default=0, metavar='G',
+                   help='G in 1..16: speculative sampling, G drafted words per round and stream (0: off)')
+    p.add_argument('--draft-model-path', type=str, default='', metavar='PATH',
+                   help='with --speculate: the checkpoint that drafts (default: the model itself at mean weights, which needs '
+                        '--mc-samples >= 2)')
+    p.add_argument('--draft-args', type=str, default=None, metavar='"..."',
+                   help='with --draft-model-path: the flags that shape the DRAFT, as one string of this command line\'s own flags '
+                        '(a checkpoint holds weights, not an architecture).  Only the model-shaping ones are read: %s.  Default: '
+                        'the target\'s own' % ", ".join("--" + f for f in DRAFT_FLAGS))
     return p
+
+
+# the flags build_models reads: what --draft-args may set for the draft
+DRAFT_FLAGS = ("model", "emsize", "nhid", "nlayers", "nhead", "uncertainty", "T_bayes_pos", "L_bayes_pos", "L_gauss_pos", "T_gauss_pos",
+               "L_v_pos", "T_v_pos")
+
+
+def check_speculate_args(args):
+    """The --speculate / --draft-* flags, refused before any file or device is looked at -> the draft's model-shaping flags (a
+    namespace; None when the model drafts for itself or nothing is speculated)."""
+    if not args.speculate:
+        for flag, given in (("--draft-model-path", bool(args.draft_model_path)), ("--draft-args", args.draft_args is not None)):
+            if given:
+                raise SystemExit("%s needs --speculate" % flag)
+        return None
+    given = [f for f, v in (("--beam", args.beam), ("--top-k", args.top_k is not None), ("--top-p", args.top_p is not None),
+                            ("--write-uncertainty", args.write_uncertainty)) if v]
+    if given:
+        raise SystemExit("--speculate is not built with %s (filtering would need the filtered target in the accept rule)" % ", ".join(given))
+    if not 1 <= args.speculate <= 16:
+        raise SystemExit("--speculate G: G in 1..16 expected (got %d)" % args.speculate)
+    if not args.draft_model_path:
+        if args.draft_args is not None:
+            raise SystemExit("--draft-args needs --draft-model-path")
+        if args.mc_samples < 2:
+            raise SystemExit("--speculate without --draft-model-path drafts at the model's own mean weights, which needs --mc-samples "
+                             ">= 2 (got --mc-samples %d)" % args.mc_samples)
+        return None
+    shape = argparse.Namespace(**{f: getattr(args, f) for f in DRAFT_FLAGS})
+    if args.draft_args is not None:
+        theirs = build_parser().parse_args(["--model-path", "-", "--vocabulary", "-"] + shlex.split(args.draft_args))
+        shape = argparse.Namespace(**{f: getattr(theirs, f) for f in DRAFT_FLAGS})
+    shape.interpolation_flag = 0
+    return shape
+
+
+def speculative_generate(model, vocab, words, gamma, streams=1, temperature=1.0, seed=1111, prompt="", mc_samples=0, mc_seed=1111,
+                         draft_model=None):
+    """generate() by speculative sampling -> (list of `streams` lists of generated word ids, SpecStats); ``draft_model`` None:
+    the model's own mean weights draft (mc_samples >= 2)."""
+    from .speculative import SpeculativeLM
+    ctx = _context(vocab, prompt)
+    max_len = len(ctx) + max(words, 1) + gamma
+    target = IncrementalLM(model, max_streams=streams, max_len=max_len, mc_samples=mc_samples, seed=mc_seed)
+    draft = None if draft_model is None else IncrementalLM(draft_model, max_streams=streams, max_len=max_len)
+    return SpeculativeLM(target, draft, gamma).generate(ctx, words, streams, temperature, seed)
 
 
 def _context(vocab, prompt):
@@ -148,6 +212,7 @@ def write_uncertainty(rows, h_pred, mi, path):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    draft_shape = check_speculate_args(args)  # before the input paths, the model or a device are looked at
     if args.beam:  # before the input paths, the model or a device are looked at
         given = [f for f, v in (("--temperature", args.temperature), ("--top-k", args.top_k), ("--top-p", args.top_p)) if v is not None]
         if given:
@@ -207,6 +272,17 @@ def main(argv=None):
         if args.write_scores:
             with open(args.write_scores, 'w', encoding='utf-8') as f:
                 f.write("".join("%d %.6f %d\n" % (r + 1, h.score, h.length) for r, h in enumerate(hyps)))
+    elif args.speculate:
+        draft_model = None
+        if args.draft_model_path:
+            draft_model, _ = S.build_models(draft_shape, len(vocab))
+            S.load_partial(draft_model, args.draft_model_path)
+            draft_model = draft_model.to(torch.device("cuda", torch.cuda.current_device())).eval()
+        ids, stats = speculative_generate(model, vocab, args.words, args.speculate, args.streams, args.temperature, args.seed,
+                                          args.prompt, args.mc_samples, args.mc_seed, draft_model)
+        sys.stderr.write("speculative sampling: %d rounds, %d target chunks, %.3f words per target chunk and stream, acceptance rate "
+                         "%.4f (%d of %d drafted words)\n" % (stats.rounds, stats.target_chunks, stats.words_per_chunk(args.speculate),
+                                                              stats.acceptance_rate, stats.accepted, stats.drafted))
     else:
         ids = generate(model, vocab, args.words, args.streams, args.temperature, args.seed, args.prompt, args.mc_samples,
                        args.mc_seed, bool(args.write_uncertainty), args.top_k, args.top_p)

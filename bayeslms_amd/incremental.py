@@ -10,6 +10,8 @@ the histories through the model again.
     nll = lm.step(st, ids, targets=t)         # NLL of the given next words, no logits stored
     st = lm.reorder(st, idx)                  # beam prune / fork: new stream j continues old stream idx[j]; `st` is consumed
     st.lengths                                # host mirror of the per-stream lengths
+    lm.truncate(st, lengths)                  # take tokens back out: stream j keeps its first lengths[j] (Transformer only; what
+                                              # speculative sampling, bayeslms_amd/speculative.py, does with rejected drafts)
     vals, ids = lm.step_topk(st, ids, k=8)    # the 8 best next words of each stream, best first (blm_topk_rows)
     st = lm.reorder_device(st, idx)           # the same gather with a DEVICE index and no copy to the host (equal lengths promised)
     nbest = lm.beam_search([[bos, w1, w2]], beam=8, max_words=30, eos=bos)   # -> [[BeamHypothesis(tokens, score, length), ...]]
@@ -233,6 +235,23 @@ class IncrementalLM:
         else:
             buf.zero_()  # init_hidden
         return IncrementalState(self, n, buf)
+
+    def truncate(self, st, lengths):
+        """Take tokens back out of ``st``: stream j keeps its first lengths[j] tokens (host-known, 0 <= lengths[j] <=
+        st.lengths[j]).  Transformer: the device `past` of every sample slot (with mc_samples all S slices) and the host mirror
+        are set back and nothing else moves -- the key/value rows beyond a length are overwritten by the next append.  LSTM:
+        refused, because (h, c) of an earlier position no longer exists (bayeslms_amd/speculative.py keeps a copy instead)."""
+        buf = st._live(self)
+        if self.kind != "transformer":
+            raise BayesLMError("IncrementalLM.truncate: an LSTM state cannot be taken back, (h, c) of an earlier position no "
+                               "longer exists (copy the state before the step instead)")
+        a = _host_ints(lengths, st.n, "lengths")
+        if any(int(v) < 0 or int(v) > have for v, have in zip(a, st.lengths)):
+            raise BayesLMError("IncrementalLM.truncate: lengths must lie in [0, st.lengths] = %s, got %s" % (st.lengths, a.tolist()))
+        S = max(self.mc_samples, 1)
+        with torch.no_grad():
+            buf.past[:S * st.n].copy_(_upload(np.tile(a, S), self.device, torch.int32))  # sample-major: slot s * n + j
+        st.lengths = [int(v) for v in a]
 
     def reorder(self, st, idx):
         """Beam prune / fork: new stream j continues stream idx[j] of ``st`` (idx (m,) int64: host, or one copy to the host;

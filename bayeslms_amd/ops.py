@@ -2487,6 +2487,67 @@ def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=
     return out
 
 
+class SpecAccept(NamedTuple):
+    """What one verification of G drafted words per stream decides (include/bayeslm.h, blm_spec_accept)."""
+    n_acc: torch.Tensor   # (N,) int32: the drafted words kept, the smallest t with accept[t, n] = 0 (G: all of them)
+    token: torch.Tensor   # (N,) int64: the word emitted behind them, cand[n_acc[n], n]
+    accept: torch.Tensor  # (G, N) uint8: every position's own flag, whether or not an earlier one rejected
+    cand: torch.Tensor    # (G + 1, N) int64: every position's own candidate; -1 in a row that holds a NaN
+
+
+def _spec_rows(t, name, V):
+    """(T, N, V) float32 rows for blm_spec_accept -> (tensor, row stride): a view whose rows lie at one stride >= V (padded
+    vocabulary rows, a column slice) is read in place, anything else through its contiguous copy."""
+    if t.dim() != 3 or t.shape[2] != V:
+        raise BayesLMError("spec_accept: %s must be (T, N, V = %d), got %s" % (name, V, tuple(t.shape)))
+    T, N = t.shape[0], t.shape[1]
+    ld = t.stride(1) if N > 1 else (t.stride(0) if T > 1 else V)
+    if t.dtype == torch.float32 and t.stride(2) == 1 and ld >= V and (T == 1 or t.stride(0) == N * ld) and not t.is_contiguous():
+        dev_tensor(t[:1, :1], name)  # the device checks of the product path; the view itself is what the kernel reads
+        return t, ld
+    return _f32(t, name), V
+
+
+def spec_accept(logp, logq, draft, temperature=1.0, seed=0, stream_id=0, step=0):
+    """The accept / reject / residual-draw step of speculative sampling (blm_spec_accept; definitions: include/bayeslm.h): the
+    target's rows ``logp`` (G + 1, N, V) and the draft's rows ``logq`` (G, N, V) -- logits or log-probabilities, the kernel
+    normalises -- against the drafted ids ``draft`` (G, N) int64.  temperature 0 is greedy and takes logq = None.  The Philox
+    noise is keyed by (seed, stream_id, step), which MUST differ from the (stream_id, step) under which the drafted ids were drawn:
+    otherwise the residual draw reuses the draft's noise and the emitted words are no longer distributed as the target.
+    -> SpecAccept(n_acc, token, accept, cand)"""
+    tau = float(temperature)
+    t32 = C.c_float(tau).value if math.isfinite(tau) else tau  # what the entry point receives
+    if not (tau >= 0.0 and math.isfinite(t32)):
+        raise BayesLMError("spec_accept: temperature = %r: a finite value >= 0 expected" % (temperature,))
+    if tau > 0.0 and (t32 == 0.0 or not math.isfinite(C.c_float(1.0 / t32).value)):
+        raise BayesLMError("spec_accept: 1 / temperature (%r) is no finite float32" % (temperature,))
+    tau = t32
+    if not torch.is_tensor(logp) or logp.dim() != 3 or logp.shape[0] < 2 or logp.shape[1] < 1 or logp.shape[2] < 1:
+        raise BayesLMError("spec_accept: logp must be (G + 1, N, V) with G >= 1, N >= 1 and V >= 1")
+    G, N, V = logp.shape[0] - 1, logp.shape[1], logp.shape[2]
+    if logq is None and tau > 0.0:
+        raise BayesLMError("spec_accept: logq may be None at temperature 0 only")
+    logp, ldp = _spec_rows(logp, "logp", V)
+    ldq = V
+    if logq is not None:
+        if not torch.is_tensor(logq) or tuple(logq.shape) != (G, N, V):
+            raise BayesLMError("spec_accept: logq must be (G, N, V) = (%d, %d, %d)" % (G, N, V))
+        logq, ldq = _spec_rows(logq, "logq", V)
+    if not torch.is_tensor(draft) or tuple(draft.shape) != (G, N):
+        raise BayesLMError("spec_accept: draft must be (G, N) = (%d, %d) int64" % (G, N))
+    draft = dev_tensor(draft, "draft", torch.int64)
+    dev = logp.device
+    accept = torch.empty(G, N, device=dev, dtype=torch.uint8)
+    cand = torch.empty(G + 1, N, device=dev, dtype=torch.int64)
+    n_acc = torch.empty(N, device=dev, dtype=torch.int32)
+    token = torch.empty(N, device=dev, dtype=torch.int64)
+    r = L.rng(seed, stream_id, step)
+    L.require_gfx950()
+    calls().blm_spec_accept(ptr(logp), ldp, ptr(logq), ldq, ptr(draft), G, N, V, tau, C.byref(r), ptr(accept), ptr(cand), ptr(n_acc),
+                            ptr(token), stream())
+    return SpecAccept(n_acc, token, accept, cand)
+
+
 def topk_rows(x, k):
     """The k best entries of every row of the (R, V) matrix x, best first (blm_topk_rows): value descending, then index
     ascending, NaN below -inf; values are copied bit for bit.  1 <= k <= min(V, _lib.TOPK_MAX).

@@ -653,6 +653,51 @@ int blm_beam_select_pool(const float* cand_vals, const int64_t* cand_ids, const 
  * no floating-point sum depends on an order), not by sorting it. */
 int blm_sample_rows_filtered(const float* x, int64_t ldx, int R, int V, float temperature, int top_k, float top_p, const blm_rng* rng,
                              int64_t* out, void* stream);
+/* Speculative sampling, the verification of G drafted words per stream in one launch (csrc/speculative.hip; Leviathan et al.
+ * 2023, Chen et al. 2023; the loop around it is bayeslms_amd/speculative.py).  The Greek letters of the usual statement are
+ * spelled out: tau, beta, rho.
+ *
+ * The target rows are P (G + 1, N, V) with row stride ldp.  The draft rows are Q (G, N, V) with row stride ldq.  Both hold logits
+ * or log-probabilities: the kernel normalises, as blm_row_stats does.  The drafted ids are x (G, N) int64.  tau = temperature,
+ * and rng is a blm_rng.  Row index r = t * N + n.
+ *
+ * For tau > 0, with beta = float32(1 / tau):
+ *   p = softmax(beta P[t, n]) and q = softmax(beta Q[t, n]) over the first V columns.  A -inf column has mass 0.
+ *   Acceptance.
+ *     u_r is the blm_sample_rows uniform, ((w >> 8) + 0.5) * 2^-24, of the first Philox word at counter
+ *     (0xFFFFFFFF, r, rng->stream, rng->step), key rng->seed.  No vocabulary column can reach that column value.
+ *     accept[t, n] = 1 iff log u_r < min(0, log p(x) - log q(x)), both logs formed from max-shifted values.
+ *     An x outside [0, V) or with q(x) = 0 is rejected.
+ *   Candidate, t < G (the word emitted if t is the first rejected position).
+ *     rho_v = max(p_v - q_v, 0).
+ *     cand[t, n] = argmax over v with rho_v > 0 of log rho_v + g_v, lowest index on ties.
+ *     g_v = -log(-log u) is blm_sample_rows' Gumbel noise at counter (v, r, rng->stream, rng->step), first word.
+ *     If no column has rho_v > 0, the candidate is the plain draw of the next item applied to p.
+ *   Candidate, t = G (the bonus word when every draft was accepted).
+ *     cand[G, n] = argmax_v beta P_v + g_v.  This is exactly what blm_sample_rows returns for that row of P at that row index
+ *     with the same rng.  This is tested bit for bit.
+ *   Finish.
+ *     n_acc[n] = the smallest t with accept[t, n] = 0, or G if there is none.
+ *     token[n] = cand[n_acc[n], n].
+ *
+ * For tau = 0 (greedy):
+ *   Q may be NULL.
+ *   accept[t, n] = 1 iff x equals the lowest index holding the maximum of P[t, n].
+ *   cand[t, n] is that index, for every t <= G.
+ *
+ * A row of P or Q (tau > 0) that holds a NaN gives accept = 0 and cand = -1 in that row only.
+ *
+ * INDEPENDENCE IS THE CALLER'S JOB: the (stream, step) of this call must differ from the ones under which the x were drawn.
+ * Otherwise the residual draw reuses the draft's noise and the output is no longer the target's distribution.
+ *
+ * One workgroup per row (t, n), whether or not an earlier position of the stream rejected; a second small launch walks every
+ * stream's G flags.  No atomics, every reduction in a fixed order: the same bits from every run.  No workspace.  Refused with
+ * BLM_ERR_INVALID before any launch: a NULL pointer (q may be NULL at tau = 0 only; rng may be NULL there too), G < 1, N < 1,
+ * V <= 0, ldp < V or ldq < V, a tau that is negative or not finite or whose 1 / tau is no finite float32, extents beyond
+ * 2^30 each / 2^40 elements together, and outputs that overlap the inputs. */
+int blm_spec_accept(const float* p, int64_t ldp, const float* q, int64_t ldq, const int64_t* draft, int G, int N, int V,
+                    float temperature, const blm_rng* rng, uint8_t* accept /* (G, N) */, int64_t* cand /* (G + 1, N) */,
+                    int32_t* n_acc /* (N) */, int64_t* token /* (N) */, void* stream);
 
 /* Cross entropy over materialised logits (M, V) (train.py:233,332;
  * compute_sentence_scores_bayes_jianwei.py:168):
