@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("BLM_LIB") or os.path.join(_HERE, "libbayeslm_hip.so")
 ABI_VERSION = 1
 TOPK_MAX = 256  # BLM_TOPK_MAX (include/bayeslm.h)
 ROW_TEMPS_MAX = 8  # BLM_ROW_TEMPS_MAX
+CACHE_THETAS_MAX = 8  # BLM_CACHE_THETAS_MAX
 OK = 0
 ERR_INVALID, ERR_ABI, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4  # blm_status (include/bayeslm.h)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -76,6 +77,11 @@ class BeamPoolArgs(C.Structure):
 class RowTemps(C.Structure):
     """blm_row_temps (include/bayeslm.h)."""
     _fields_ = [("abi_version", C.c_uint32), ("count", C.c_int32), ("beta", C.c_float * ROW_TEMPS_MAX)]
+
+
+class CacheThetas(C.Structure):
+    """blm_cache_thetas (include/bayeslm.h)."""
+    _fields_ = [("abi_version", C.c_uint32), ("count", C.c_int32), ("theta", C.c_float * CACHE_THETAS_MAX)]
 
 
 class GemmPlan(C.Structure):
@@ -144,6 +150,7 @@ SIGNATURES = {
     "blm_sample_rows": (_i, [_vp, _i64, _i, _i, _f, _rngp, _vp, _vp]),
     "blm_row_stats": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_row_stats_temps": (_i, [_vp, _i64, _vp, _i, _i, C.POINTER(RowTemps), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "blm_cache_scores": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(CacheThetas), _vp, _vp, _vp, _vp]),
     "blm_topk_rows": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "blm_beam_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "blm_beam_select_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _i, C.POINTER(BeamPoolArgs),

@@ -770,13 +770,15 @@ class EvalReport:
     mean_h_pred: Optional[float] = None    # mean predictive entropy H[pbar]
     mean_mi: Optional[float] = None        # mean mutual information between the word and the weights
     per_token: Optional[dict] = None       # keep_tokens: float / int arrays in text order, skipped tokens included (NaN / -1)
+    cache: Optional[dict] = None           # neural cache (CacheReport.as_dict, with the fit's block after fit_cache); None: no cache
     temperature: Optional[dict] = None     # temperature scaling (temperature_block); None: the distribution as the model gives it
 
     def as_dict(self):
         d = dataclasses.asdict(self)
         del d["per_token"]
-        if d["temperature"] is None:  # a run without a temperature writes what it wrote before there was one
-            del d["temperature"]
+        for k in ("temperature", "cache"):  # a run without one writes what it wrote before there was one
+            if d[k] is None:
+                del d[k]
         return d
 
 
@@ -871,8 +873,10 @@ def temperature_block(beta, fitted_on=None, at_bound=False, before=None, after=N
             "curve": curve}
 
 
-def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, betas):
-    """The walk evaluate_report and evaluate_temperatures share -> (host arrays, text positions per window, V, S).
+def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, betas, rows_out=None):
+    """The walk evaluate_report, evaluate_temperatures and the neural cache share -> (host arrays, text positions per window, V, S).
+    ``rows_out`` (mean weights only): a callable that is handed every window's decoder-input rows (rows, K), in the order of the
+    targets, before the next window runs (the neural cache keeps them on the device).
     ``betas`` None: blm_row_stats reduces each chunk and the float arrays are (tokens,).  A list of J float32 inverse
     temperatures: blm_row_stats_temps reduces it, and nll, conf, entropy and dnll are (J, tokens), those of the tempered
     distributions; nll_s, h_pred and mi stay the untempered (tokens, ...) quantities of ops.linear_mc_logprobs."""
@@ -942,6 +946,8 @@ def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, bet
                 else:
                     x = model(data)
                 reduce_rows(x.reshape(-1, x.shape[-1]), targets)
+                if rows_out is not None:
+                    rows_out(x.reshape(-1, x.shape[-1]))
                 keep["tgt"].append(targets)
                 keep["pos"].append(pos)
         else:
@@ -1178,3 +1184,266 @@ def fit_temperature(model, source, seq_len, mc_samples=0, seed=1111, bins=15, pa
     (before, after), dloss = evaluate_temperatures(model, source, seq_len, [1.0, beta], mc_samples, seed, bins)
     curve += [[b, r.loss, d, r.ece] for b, r, d in zip((1.0, beta), (before, after), dloss)]
     return TemperatureFit(1.0 / beta, beta, search.at_bound, done, curve, before, after)
+
+
+# ----------------------------------------------------------------------------
+# continuous neural cache: a pointer over the recent decoder-input rows of the evaluated text
+# ----------------------------------------------------------------------------
+_CACHE_ROWS_BYTES = 8 << 30  # the decoder-input rows of a text stay on the device: texts beyond this are refused
+
+
+@dataclasses.dataclass
+class CacheReport:
+    """What evaluate_cache returns; ``as_dict()`` is the ``cache`` block the evaluate command writes."""
+    tokens: int              # tokens that entered the figures
+    skipped: int             # tokens whose target is outside [0, V): left out, as evaluate_report leaves them out
+    loss: float              # mean NLL with the cache, nats
+    ppl: float
+    base_loss: float         # mean NLL of the model alone: evaluate_report(...).loss
+    base_ppl: float
+    window: int
+    theta: float             # as the kernel got it (float32)
+    lam: float
+    cache_hit_rate: float    # share of tokens whose target is the label of a key in their window (a finite ``match``)
+    mean_cache_prob: float   # mean p_cache(target)
+    per_token: Optional[dict] = None  # keep_tokens: arrays in text order (tgt, nll_model, nll, lse, match), skipped tokens included
+
+    def as_dict(self):
+        d = dataclasses.asdict(self)
+        del d["per_token"]
+        return d
+
+
+def _cache_args(who, mc_samples, temperature, window):
+    """The refusals of the neural cache that need no model: all before any launch."""
+    if int(mc_samples) != 0:
+        raise ops.BayesLMError("%s: mc_samples = %r: a cache under Monte-Carlo weight samples is not built (whose rows would the "
+                               "keys be?); run it at mean weights" % (who, mc_samples))
+    if float(temperature) != 1.0:
+        raise ops.BayesLMError("%s: temperature = %r: the cache mixes with the model's distribution as it is; a tempered one is "
+                               "not built" % (who, temperature))
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        raise ops.BayesLMError("%s runs in a single process (world size %d): more than one rank is not built, the cache reads "
+                               "the text as one stream" % (who, dist.get_world_size()))
+    if int(window) < 1:
+        raise ops.BayesLMError("%s: window = %r, the cache needs at least one key" % (who, window))
+    return int(window)
+
+
+def _cache_walk(who, model, source, seq_len):
+    """One walk of the text at mean weights (_report_walk: evaluate_report's windows and chunks) that keeps every decoder-input
+    row on the device -> dict: rows (n_tok, K) and tgt / nll (n_tok,) on the device IN TEXT ORDER, hi = arange(n_tok) int32,
+    the host's nll / valid in walk order (what evaluate_report sums), V."""
+    from .model import inference_decoder
+    dec = inference_decoder(model)
+    if dec is None:
+        raise ops.BayesLMError("%s: %s has no decoder that hands back its input rows" % (who, type(model).__name__))
+    K = dec.weight.shape[1]
+    n_tok = max(0, source.shape[0] - 1) * source.shape[1]
+    if n_tok * K * 4 > _CACHE_ROWS_BYTES:
+        raise ops.BayesLMError("%s: the %d decoder-input rows of width %d take %.2f GiB on the device, beyond the %d GiB this keeps "
+                               "(streaming a longer text through the cache is not built)"
+                               % (who, n_tok, K, n_tok * K * 4 / 2.0 ** 30, _CACHE_ROWS_BYTES >> 30))
+    dev = source.device
+    rows = torch.empty(n_tok, K, device=dev, dtype=torch.float32)
+    at = [0]
+
+    def keep_rows(x):
+        rows[at[0]:at[0] + x.shape[0]] = x
+        at[0] += x.shape[0]
+
+    host, pos, V, _ = _report_walk(who, model, source, seq_len, 0, 0, True, None, rows_out=keep_rows)
+    if at[0] != n_tok or len(host["tgt"]) != n_tok:
+        raise ops.BayesLMError("%s: the walk handed back %d rows for %d targets (%d expected)" % (who, at[0], len(host["tgt"]), n_tok))
+    order = np.argsort(np.concatenate(pos), kind="stable") if n_tok else np.zeros(0, np.int64)
+    valid = (host["tgt"] >= 0) & (host["tgt"] < V)
+    text_rows = rows.index_select(0, torch.from_numpy(order).to(dev))  # text order: one gather by pos
+    del rows
+    return {"rows": text_rows, "tgt": torch.from_numpy(host["tgt"][order]).to(dev),
+            "nll": torch.from_numpy(np.ascontiguousarray(host["nll"][order])).to(dev),
+            "valid": torch.from_numpy(valid[order]).to(dev), "hi": torch.arange(n_tok, device=dev, dtype=torch.int32),
+            "host_nll": host["nll"], "host_valid": valid, "order": order, "V": V, "n_tok": n_tok}
+
+
+def _cache_scores(walk, thetas, window):
+    """blm_cache_scores over the stored rows: q = k = the text's rows, hi[t] = t -> CacheScores, both (J, n_tok)"""
+    with torch.no_grad():
+        return ops.cache_scores(walk["rows"], walk["rows"], walk["tgt"], walk["tgt"], walk["hi"], thetas, window)
+
+
+def evaluate_cache(model, source, seq_len, window, theta, lam, keep_tokens=False, mc_samples=0, temperature=1.0):
+    """evaluate_report's held-out loss with the continuous neural cache (Grave, Joulin, Usunier 2017) mixed in -> CacheReport.
+
+    Row t of the text has the decoder input h_t and the target y_t.  The cache of row t holds the ``window`` rows before it,
+    C_t = { i : max(0, t - window) <= i < t } (the target of row t is known only after it), p_cache(y_t) =
+    sum_{i in C_t, y_i = y_t} exp(theta h_t.h_i) / sum_{i in C_t} exp(theta h_t.h_i), and the token is scored with
+    p = (1 - lam) p_model + lam p_cache; the first token (an empty cache) with p_model.  Text order is the order of the text
+    positions: the stream is one text, the columns of ``source`` consecutive pieces of it, so a column's cache reaches back
+    into the column before.
+
+    The walk is evaluate_report's at mean weights (_report_walk) with the decoder-input rows kept on the device (n_tok x K x 4
+    bytes; more than 8 GiB is refused), put in text order by one gather; blm_cache_scores reduces the banded h h^T to the two
+    log-sums per token without storing a score, and ops.cache_mix mixes.  ``base_loss`` is evaluate_report's loss of the same
+    arguments, bit for bit.  A token whose target is outside [0, V) is skipped as there; it still stands in the window as a key.
+
+    Refused, before any launch: mc_samples other than 0, a temperature other than 1, more than one rank, window < 1, theta
+    that is negative or not finite, lam outside [0, 1), a model whose decoder cannot hand back its input rows."""
+    who = "evaluate_cache"
+    window = _cache_args(who, mc_samples, temperature, window)
+    th = ops.cache_thetas([theta], who)
+    lam = float(lam)
+    if not 0.0 <= lam < 1.0:
+        raise ops.BayesLMError("%s: lam = %r outside [0, 1)" % (who, lam))
+    walk = _cache_walk(who, model, source, seq_len)
+    sc = _cache_scores(walk, [theta], window)
+    lse, match = sc.lse[0], sc.match[0]
+    nll = ops.cache_mix(walk["nll"], lse, match, lam)
+    inv = np.argsort(walk["order"], kind="stable")  # text order -> walk order: the sums run as evaluate_report's do
+    base = report_from_tokens(walk["host_nll"], valid=walk["host_valid"])
+    dev_cols = torch.stack([nll, lse, match]).cpu().numpy()
+    with_cache = report_from_tokens(dev_cols[0][inv], valid=walk["host_valid"])
+    ok = walk["host_valid"][walk["order"]]
+    n = int(ok.sum())
+    with np.errstate(invalid="ignore"):
+        p_cache = np.where(np.isneginf(dev_cols[2]), 0.0, np.exp(dev_cols[2].astype(np.float64) - dev_cols[1].astype(np.float64)))
+    rep = CacheReport(tokens=base.tokens, skipped=base.skipped, loss=with_cache.loss, ppl=with_cache.ppl, base_loss=base.loss,
+                      base_ppl=base.ppl, window=window, theta=float(th.theta[0]), lam=lam,
+                      cache_hit_rate=float(np.isfinite(dev_cols[2])[ok].sum() / n) if n else float("nan"),
+                      mean_cache_prob=float(p_cache[ok].sum() / n) if n else float("nan"))
+    if keep_tokens:
+        rep.per_token = {"tgt": walk["tgt"].cpu().numpy(),
+                         "nll_model": walk["host_nll"][walk["order"]], "nll": dev_cols[0], "lse": dev_cols[1], "match": dev_cols[2]}
+    return rep
+
+
+class CacheSearch:
+    """Host-side search for the theta of the neural cache that minimises a held-out loss, from the loss on log-spaced grids of
+    ``points`` thetas (one launch of blm_cache_scores each: eight thetas share the dot products).
+
+    Domain [lo, hi] = [1e-4, 16] by default.  theta multiplies a raw dot product h.h', whose size is about K for
+    post-LayerNorm Transformer rows (|h|^2 = K = 512..1024: useful thetas of 1e-3..1e-1) and at most the hidden width, usually
+    a few tens, for raw LSTM states in (-1, 1)^K (Grave et al. report 0.1..1 there): [1e-4, 16] holds both with a decade to
+    spare on each side.  Three passes of eight points leave a ratio of (1.6e5)^(4/343) = 1.15 between neighbours.
+
+        grid()     the next thetas (float32 values): geometric over the bracket, ends included.
+        update()   takes the thetas and their losses (a non-finite loss raises, naming theta); the bracket becomes the best
+                   theta seen and its two neighbours among everything seen (the domain's end where there is none).
+        result()   the best theta seen; ``at_bound`` is set while that is an end of the domain: the loss may still fall beyond.
+
+    The loss need not be unimodal in theta; the search then ends in the basin of its best grid point."""
+
+    def __init__(self, lo=1e-4, hi=16.0, points=8):
+        self.lo, self.hi, self.points = float(np.float32(lo)), float(np.float32(hi)), int(points)
+        if not (0.0 < self.lo < self.hi < math.inf):
+            raise ops.BayesLMError("CacheSearch: need 0 < lo < hi < inf, got lo = %r, hi = %r" % (lo, hi))
+        if not 3 <= self.points <= 8:
+            raise ops.BayesLMError("CacheSearch: points = %r outside 3..8, what one launch evaluates" % (points,))
+        self.seen = {}  # theta -> loss
+        self.at_bound = False
+
+    @property
+    def best(self):
+        return min(self.seen, key=lambda t: (self.seen[t], t))
+
+    @property
+    def bracket(self):
+        if not self.seen:
+            return self.lo, self.hi
+        ts, b = sorted(self.seen), self.best
+        i = ts.index(b)
+        return (ts[i - 1] if i > 0 else self.lo), (ts[i + 1] if i + 1 < len(ts) else self.hi)
+
+    def grid(self):
+        a, b = self.bracket
+        g = np.exp(np.linspace(math.log(a), math.log(b), self.points))
+        g[0], g[-1] = a, b
+        return sorted({min(self.hi, max(self.lo, float(np.float32(v)))) for v in g})
+
+    def update(self, thetas, loss):
+        for t, l in zip(thetas, loss):
+            t, l = float(t), float(l)
+            if not math.isfinite(l):
+                raise ops.BayesLMError("CacheSearch: loss %r at theta = %r is not finite" % (l, t))
+            self.seen[t] = l
+        self.at_bound = self.best <= self.lo or self.best >= self.hi
+
+    def result(self):
+        if not self.seen:
+            raise ops.BayesLMError("CacheSearch.result: nothing evaluated yet")
+        return self.best
+
+
+def cache_best_lambda(nll_model, lse, match, valid=None, lam_max=0.95, iters=50):
+    """For each row of the (J, n) arrays ``lse`` / ``match`` (or (n,) ones): the lam in [0, lam_max] that minimises the mean NLL
+    of (1 - lam) p_model + lam p_cache over the ``valid`` tokens -> (lam (J,), loss (J,)) float64 tensors on the arrays' device.
+    With r = p_cache / p_model per token the loss is -mean log p_model - mean log(1 + lam (r - 1)), convex in lam; its slope
+    -mean (r - 1) / (1 + lam (r - 1)) changes sign at most once, and ``iters`` bisections on that sign place lam (every
+    bracket moves in one tensor operation: no host round trip inside the loop).  Tokens with an empty cache (lse = -inf) keep
+    p_model and do not enter the slope.  Everything in float64."""
+    lam_max = float(lam_max)
+    if not 0.0 < lam_max < 1.0:
+        raise ops.BayesLMError("cache_best_lambda: lam_max = %r outside (0, 1)" % lam_max)
+    nll = nll_model.double().reshape(1, -1)
+    lse2, match2 = lse.double().reshape(-1, nll.shape[1]), match.double().reshape(-1, nll.shape[1])
+    ok = torch.ones_like(nll, dtype=torch.bool) if valid is None else valid.reshape(1, -1).bool()
+    n = ok.sum().clamp(min=1).double()
+    live = ok & ~torch.isneginf(lse2)  # tokens the cache can move
+    log_r = torch.where(torch.isneginf(match2), match2, match2 - lse2) + nll  # log (p_cache / p_model)
+    d = torch.where(live, torch.exp(log_r) - 1.0, torch.zeros_like(log_r))   # r - 1 >= -1; 0: no contribution
+
+    def slope_sum(lam):  # sum (r - 1) / (1 + lam (r - 1)) = -n d loss / d lam
+        return (d / (1.0 + lam.reshape(-1, 1) * d)).sum(1)
+
+    J = d.shape[0]
+    a, b = torch.zeros(J, dtype=torch.float64, device=d.device), torch.full((J,), lam_max, dtype=torch.float64, device=d.device)
+    falls_at_0, falls_at_max = slope_sum(a) > 0, slope_sum(b) >= 0
+    for _ in range(int(iters)):
+        mid = 0.5 * (a + b)
+        falls = slope_sum(mid) > 0
+        a, b = torch.where(falls, mid, a), torch.where(falls, b, mid)
+    lam = torch.where(falls_at_max, torch.full_like(a, lam_max), torch.where(falls_at_0, 0.5 * (a + b), torch.zeros_like(a)))
+    base = torch.where(ok, nll, torch.zeros_like(nll)).sum() / n
+    loss = base - torch.log1p(lam.reshape(-1, 1) * d).sum(1) / n
+    return lam, loss
+
+
+@dataclasses.dataclass
+class CacheFit:
+    """What fit_cache returns."""
+    theta: float        # a float32 value: what evaluate_cache hands the kernel
+    lam: float
+    at_bound: bool      # theta is an end of the search's domain, or lam its upper bound: the loss may still fall beyond
+    loss_before: float  # the fit text without the cache
+    loss_after: float   # ... with it at (theta, lam); <= loss_before, since lam = 0 is always a candidate
+    curve: list         # [theta, best lam, loss] of every theta evaluated, in the order evaluated
+
+
+def fit_cache(model, source, seq_len, window, passes=3, lo=1e-4, hi=16.0, points=8, lam_max=0.95, mc_samples=0, temperature=1.0):
+    """The theta and lam of the neural cache that minimise the loss of ``model`` on the held-out stream ``source`` at the given
+    ``window`` -> CacheFit.  The model walks the text ONCE (evaluate_cache's walk: the rows stay on the device); each of the
+    ``passes`` search passes relaunches only blm_cache_scores on the stored rows with CacheSearch's ``points`` <= 8 thetas in one
+    launch, and for every theta cache_best_lambda finds its best lam in [0, lam_max] on the device in float64.  lam = 0, the
+    model alone, is always a candidate: loss_after <= loss_before.  Refuses what evaluate_cache refuses, and passes < 1."""
+    who = "fit_cache"
+    window = _cache_args(who, mc_samples, temperature, window)
+    if int(passes) < 1:
+        raise ops.BayesLMError("fit_cache: passes = %r, at least one search pass is needed" % (passes,))
+    search = CacheSearch(lo, hi, points)
+    walk = _cache_walk(who, model, source, seq_len)
+    n = walk["valid"].sum().clamp(min=1).double()
+    loss_before = float(walk["nll"].double()[walk["valid"]].sum() / n)
+    curve, lam_of = [], {}
+    for _ in range(int(passes)):
+        thetas = search.grid()
+        sc = _cache_scores(walk, thetas, window)
+        lam, loss = cache_best_lambda(walk["nll"], sc.lse, sc.match, walk["valid"], lam_max)
+        lam, loss = lam.cpu().tolist(), loss.cpu().tolist()
+        search.update(thetas, loss)
+        for t, la, l in zip(thetas, lam, loss):
+            lam_of[t] = la
+            curve.append([t, la, l])
+    theta = float(np.float32(search.result()))
+    lam, loss_after = lam_of[search.result()], search.seen[search.result()]
+    if not loss_after < loss_before:  # the cache does not help on this text: the model alone
+        lam, loss_after = 0.0, loss_before
+    return CacheFit(theta, float(lam), bool(search.at_bound or lam >= lam_max), loss_before, float(loss_after), curve)

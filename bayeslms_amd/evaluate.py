@@ -23,7 +23,16 @@ that of the model average): loss, ppl, mean_conf, mean_entropy, ece, the bins an
 and entropy are then the tempered figures; accuracy, rank and the Monte-Carlo block do not change.  ``--fit-temperature-on PATH``
 fits T on that text first (tokenised and laid out like ``--data``; engine.fit_temperature, ``--fit-passes`` search walks) --
 the validation text, never ``--data`` itself -- and then evaluates ``--data`` at the fitted T.  With either flag the summary
-line and the report gain a ``temperature`` block; without them both are what they were."""
+line and the report gain a ``temperature`` block; without them both are what they were.
+
+Neural cache.  ``--cache-window N`` also scores ``--data`` with the continuous neural cache (engine.evaluate_cache: a pointer over
+the N decoder-input rows before each word, mixed into the model's distribution with weight lambda): either at the given
+``--cache-theta`` and ``--cache-lambda``, or at the pair that ``--fit-cache-on PATH`` finds on that text first (engine.fit_cache,
+``--cache-fit-passes`` launches of eight thetas on one walk of it).  The summary line gains ``| cache window ... theta ... lambda
+... | loss a -> b | ppl a -> b | hit ...`` and the report a ``cache`` block (CacheReport.as_dict, plus ``fitted_on``,
+``at_bound``, ``fit_loss_before``, ``fit_loss_after`` and ``curve`` after a fit); every other figure stays the model's own.  The
+cache runs at mean weights and at temperature 1: ``--mc-samples``, ``--temperature`` and ``--fit-temperature-on`` are refused with
+it.  Without ``--cache-window`` the line and the report are what they were."""
 import argparse
 import json
 import math
@@ -67,11 +76,44 @@ def build_parser():
     p.add_argument('--fit-temperature-on', type=str, default='', metavar='PATH',
                    help='fit T on this held-out text (the validation text), then evaluate --data at the fitted T')
     p.add_argument('--fit-passes', type=int, default=3, help='search walks of the fit text (1..6), eight temperatures each')
+    p.add_argument('--cache-window', type=int, default=None, metavar='N',
+                   help='also score --data with the neural cache over the N rows before each word')
+    p.add_argument('--cache-theta', type=float, default=None, metavar='THETA', help='sharpness of the pointer (with --cache-lambda)')
+    p.add_argument('--cache-lambda', type=float, default=None, metavar='LAMBDA', help='weight of the cache in the mix, in [0, 1)')
+    p.add_argument('--fit-cache-on', type=str, default='', metavar='PATH',
+                   help='fit theta and lambda on this held-out text (the validation text), then score --data with them')
+    p.add_argument('--cache-fit-passes', type=int, default=3, help='search launches of the cache fit (1..6), eight thetas each')
     return p
+
+
+def check_cache_args(args):
+    """The cache flags' refusals: before any file or device is touched."""
+    given = args.cache_theta is not None or args.cache_lambda is not None
+    if args.cache_window is None:
+        if given or args.fit_cache_on:
+            raise SystemExit("--cache-theta, --cache-lambda and --fit-cache-on need --cache-window")
+        return
+    if args.cache_window < 1:
+        raise SystemExit("--cache-window must be at least 1 (got %d)" % args.cache_window)
+    if args.mc_samples:
+        raise SystemExit("--cache-window with --mc-samples: the cache runs at mean weights")
+    if args.temperature is not None or args.fit_temperature_on:
+        raise SystemExit("--cache-window with --temperature / --fit-temperature-on: the cache mixes with the untempered distribution")
+    if args.fit_cache_on and given:
+        raise SystemExit("--fit-cache-on and --cache-theta / --cache-lambda exclude each other: give the values or the text to fit them on")
+    if not args.fit_cache_on and (args.cache_theta is None or args.cache_lambda is None):
+        raise SystemExit("--cache-window needs --cache-theta together with --cache-lambda, or --fit-cache-on")
+    if given and not (math.isfinite(args.cache_theta) and args.cache_theta >= 0):
+        raise SystemExit("--cache-theta must be finite and >= 0 (got %r)" % args.cache_theta)
+    if given and not 0 <= args.cache_lambda < 1:
+        raise SystemExit("--cache-lambda must lie in [0, 1) (got %r)" % args.cache_lambda)
+    if not 1 <= args.cache_fit_passes <= 6:
+        raise SystemExit("--cache-fit-passes must lie in 1..6 (got %d)" % args.cache_fit_passes)
 
 
 def check_args(args):
     """Refusals that need neither the input files, the model nor a device."""
+    check_cache_args(args)
     if args.temperature is not None and args.fit_temperature_on:
         raise SystemExit("--temperature and --fit-temperature-on exclude each other: give T or the text to fit it on")
     if args.temperature is not None and not (math.isfinite(args.temperature) and args.temperature > 0):
@@ -95,6 +137,10 @@ def summary_line(rep):
         line += " | temperature %.4f" % t["temperature"]
         if t["fitted_on"]:
             line += " | fit loss %.4f -> %.4f | ece %.4f -> %.4f" % (t["loss_before"], t["loss_after"], t["ece_before"], t["ece_after"])
+    c = rep.cache
+    if c:
+        line += " | cache window %d theta %.6g lambda %.4f | loss %.4f -> %.4f | ppl %.2f -> %.2f | hit %.4f" % (
+            c["window"], c["theta"], c["lam"], c["base_loss"], c["loss"], c["base_ppl"], c["ppl"], c["cache_hit_rate"])
     return line
 
 
@@ -128,6 +174,12 @@ def main(argv=None):
         if len(fit_text) // args.batch_size < 2:
             raise SystemExit("--fit-temperature-on holds %d tokens: fewer than two rows of --batch-size %d columns"
                              % (len(fit_text), args.batch_size))
+    cache_fit_text = None
+    if args.fit_cache_on:
+        cache_fit_text = corpus.tokenize(args.fit_cache_on)
+        if len(cache_fit_text) // args.batch_size < 2:
+            raise SystemExit("--fit-cache-on holds %d tokens: fewer than two rows of --batch-size %d columns"
+                             % (len(cache_fit_text), args.batch_size))
     args.interpolation_flag = 0
     model, _ = S.build_models(args, len(corpus.dictionary))
     S.load_partial(model, args.model_path)
@@ -145,6 +197,20 @@ def main(argv=None):
                                  seed=args.mc_seed, bins=args.bins, keep_tokens=bool(args.write_tokens), temperature=temperature)
     if fit is not None:  # also when the fit gave exactly 1
         rep.temperature = engine.temperature_block(fit.beta, args.fit_temperature_on, fit.at_bound, fit.before, fit.after, fit.curve)
+    if args.cache_window is not None:
+        theta, lam, cfit = args.cache_theta, args.cache_lambda, None
+        if args.fit_cache_on:
+            cfit = engine.fit_cache(model, D.batchify(cache_fit_text, args.batch_size, device), args.seq_len, args.cache_window,
+                                    passes=args.cache_fit_passes)
+            theta, lam = cfit.theta, cfit.lam
+            if cfit.at_bound:
+                print("warning: the cache fit on %s ended at a bound of its search, theta %.6g lambda %.4f: the loss may still fall "
+                      "beyond it" % (args.fit_cache_on, theta, lam), file=sys.stderr)
+        rep.cache = engine.evaluate_cache(model, D.batchify(text, args.batch_size, device), args.seq_len, args.cache_window, theta,
+                                          lam).as_dict()
+        if cfit is not None:
+            rep.cache.update(fitted_on=args.fit_cache_on, at_bound=cfit.at_bound, fit_loss_before=cfit.loss_before,
+                             fit_loss_after=cfit.loss_after, curve=cfit.curve)
     print(summary_line(rep), flush=True)
     if args.write_report:
         with open(args.write_report, 'w') as f:

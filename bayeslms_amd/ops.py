@@ -2464,6 +2464,95 @@ def row_stats_temps(x, betas, targets=None, V=None):
     return RowStatsTemps(nll, conf, entropy, dnll, pred, rank)
 
 
+class CacheScores(NamedTuple):
+    """The two log-sums of the neural cache per theta and query (include/bayeslm.h, blm_cache_scores)."""
+    lse: torch.Tensor    # (J, M) float32 log sum over the query's key range of exp(theta q.k); -inf over an empty range
+    match: torch.Tensor  # (J, M) float32 the same sum over the keys whose label is the query's target; -inf without one
+
+
+def cache_thetas(thetas, what="cache_scores"):
+    """The blm_cache_thetas struct of 1..8 finite thetas >= 0, each rounded to float32 once."""
+    try:
+        ts = [float(t) for t in thetas]
+    except (TypeError, ValueError):
+        raise BayesLMError("%s: thetas must be 1..%d finite numbers >= 0, got %r" % (what, L.CACHE_THETAS_MAX, thetas))
+    if not 1 <= len(ts) <= L.CACHE_THETAS_MAX:
+        raise BayesLMError("%s: %d thetas, blm_cache_scores takes 1..%d per launch" % (what, len(ts), L.CACHE_THETAS_MAX))
+    t = L.CacheThetas()
+    t.abi_version, t.count = L.ABI_VERSION, len(ts)
+    for j, v in enumerate(ts):
+        t.theta[j] = v if math.isfinite(v) else 0.0  # ctypes rounds to float32 (an overflow to inf is caught below)
+        if not (math.isfinite(v) and v >= 0.0 and t.theta[j] < math.inf):
+            raise BayesLMError("%s: thetas[%d] = %r is not a finite float32 number >= 0" % (what, j, v))
+    return t
+
+
+def _cache_rows(t, name):
+    """(rows, K) fp32 with unit inner stride, read in place where its row stride allows (a view of padded rows)"""
+    if torch.is_tensor(t) and t.dim() == 2 and t.stride(-1) == 1 and t.stride(0) >= t.shape[1] and not t.is_contiguous():
+        dev_tensor(t[:1], name)  # the device checks of the product path; the view itself is what the kernel reads
+        return t
+    t = _f32(t, name)
+    if t.dim() != 2:
+        raise BayesLMError("cache_scores: %s must be a (rows, K) matrix" % name)
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+def cache_scores(q, k, labels, targets, hi, thetas, window, lo=None):
+    """Inference only: the neural cache's two log-sums for the M rows of ``q`` (M, K) over the Nk rows of ``k`` (Nk, K) at the
+    J = len(thetas) <= 8 values ``thetas`` from the same dot products (blm_cache_scores: fp32 matrix cores, no score stored).
+    Query m reads keys [max(lo[m], hi[m] - window, 0), min(hi[m], Nk)): ``hi`` (M,) and ``lo`` (M,) or None (= 0) are int32
+    device arrays that the kernel clamps; ``labels`` (Nk,) and ``targets`` (M,) are int64.  Chunked over queries where q passes
+    the 32-bit offset limit.  Bit-identical run to run.  -> CacheScores(lse, match), both (J, M)"""
+    _inference_only("cache_scores", q, k)
+    th = cache_thetas(thetas)
+    J, window = th.count, int(window)
+    if window < 1:
+        raise BayesLMError("cache_scores: window = %d, at least one key is needed" % window)
+    q, k = _cache_rows(q, "q"), _cache_rows(k, "k")
+    M, K = q.shape
+    Nk = k.shape[0]
+    if K < 1 or k.shape[1] != K:
+        raise BayesLMError("cache_scores: q is (%d, %d) and k is (%d, %d): one width K >= 1 expected" % (M, K, Nk, k.shape[1]))
+    labels = dev_tensor(labels.reshape(-1), "labels", torch.int64)
+    targets = dev_tensor(targets.reshape(-1), "targets", torch.int64)
+    hi = dev_tensor(hi.reshape(-1), "hi", torch.int32)
+    lo = None if lo is None else dev_tensor(lo.reshape(-1), "lo", torch.int32)
+    if labels.numel() != Nk or targets.numel() != M or hi.numel() != M or (lo is not None and lo.numel() != M):
+        raise BayesLMError("cache_scores: %d labels for %d keys, %d targets, %d hi%s for %d queries"
+                           % (labels.numel(), Nk, targets.numel(), hi.numel(), "" if lo is None else ", %d lo" % lo.numel(), M))
+    lse, match = (torch.empty(J, M, device=q.device, dtype=torch.float32) for _ in range(2))
+    if M == 0 or Nk == 0:  # nothing to launch: no query, or no key for any of them
+        return CacheScores(lse.fill_(-math.inf), match.fill_(-math.inf))
+    L.require_gfx950()
+    ldq, ldk = (q.stride(0) if M > 1 else max(q.stride(0), K)), (k.stride(0) if Nk > 1 else max(k.stride(0), K))
+    chunks = _row_chunks(M, ldq)
+    for r0, r1 in chunks:
+        one = len(chunks) == 1
+        ls, mt = (lse, match) if one else (torch.empty(J, r1 - r0, device=q.device, dtype=torch.float32) for _ in range(2))
+        calls().blm_cache_scores(ptr(q[r0:r1]), ldq, ptr(k), ldk, ptr(labels), ptr(targets[r0:r1]),
+                                 None if lo is None else ptr(lo[r0:r1]), ptr(hi[r0:r1]), window, r1 - r0, Nk, K, C.byref(th), ptr(ls),
+                                 ptr(mt), None, stream())
+        if not one:
+            lse[:, r0:r1], match[:, r0:r1] = ls, mt
+    return CacheScores(lse, match)
+
+
+def cache_mix(nll_model, lse, match, lam):
+    """The NLL of p = (1 - lam) p_model + lam p_cache with p_cache = exp(match - lse):
+    -logaddexp(log(1 - lam) - nll_model, log(lam) + match - lse), elementwise over arrays of one shape (torch, not a kernel: a
+    few passes over (tokens,) arrays).  Where lse = -inf (an empty cache) p = p_model and nll_model is returned; lam = 0
+    returns nll_model bit for bit.  0 <= lam < 1."""
+    lam = float(lam)
+    if not 0.0 <= lam < 1.0:
+        raise BayesLMError("cache_mix: lam = %r outside [0, 1)" % lam)
+    if lam == 0.0:
+        return nll_model
+    log_cache = torch.where(torch.isneginf(match), match, match - lse)  # -inf - -inf never formed
+    mixed = -torch.logaddexp(math.log1p(-lam) - nll_model, math.log(lam) + log_cache)
+    return torch.where(torch.isneginf(lse), nll_model, mixed)
+
+
 def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=1.0):
     """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
     with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64

@@ -573,6 +573,39 @@ int blm_row_stats_temps(const float* x, int64_t ldx, const int64_t* tgt, int R, 
                         float* conf, float* entropy, float* dnll, int32_t* pred, int32_t* rank, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Continuous neural cache (csrc/cache.hip; Grave, Joulin, Usunier, ICLR 2017): a pointer distribution over recent hidden
+ * states.  Row i of a text has the decoder input h_i and the target y_i, the word that followed; with a window N, theta >= 0
+ * and C_t = { i : max(0, t - N) <= i < t }:
+ *   lse[t]   = log sum_{i in C_t}            exp(theta h_t . h_i)      (-inf: C_t is empty)
+ *   match[t] = log sum_{i in C_t, y_i = y_t} exp(theta h_t . h_i)      (-inf: no key matches)
+ *   p_cache(y_t) = exp(match - lse);   p(y_t) = (1 - lambda) p_model(y_t) + lambda p_cache(y_t),  0 <= lambda < 1;
+ *   an empty cache takes p = p_model.
+ * The entry point is the general banded form: M queries q (row stride ldq >= K), Nk keys k (row stride ldk >= K) with
+ * label[i], a target tgt[m] per query, and per query the key range [max(lo[m], hi[m] - window, 0), min(hi[m], Nk)) -- lo and hi
+ * are DEVICE arrays, clamped by the kernel: whatever they hold, nothing outside k and label is read, and a reversed or empty
+ * range gives -inf in both outputs.  lo may be NULL (= 0).  The evaluation passes q = k = the text's rows and hi[t] = t.
+ * Labels and targets are compared as 64-bit integers, nothing else is asked of them.
+ * The dot products run on the fp32 matrix cores; the scores are reduced on chip (one running maximum of the raw score serves
+ * every theta), never stored; only key tiles between the least start and the greatest end of a workgroup's 128 queries are
+ * visited.  A matching key whose weight underflows float32 beside the range's maximum (theta (max - score) > 87) leaves match
+ * at -inf.  The figures of theta[j] are those of a launch with theta[j] alone up to rounding, and the same bits in every run.
+ * -------------------------------------------------------------------------- */
+#define BLM_CACHE_THETAS_MAX 8
+typedef struct blm_cache_thetas {
+  uint32_t abi_version; /* BLM_ABI_VERSION */
+  int32_t count;        /* 1 .. BLM_CACHE_THETAS_MAX */
+  float theta[BLM_CACHE_THETAS_MAX]; /* theta[j] finite and >= 0 for j < count; the others are not read */
+} blm_cache_thetas;
+/* lse / match: (count, M) contiguous, theta j's figure of query m at [j * M + m].  Kernel forms exist for 1, 2, 4 and 8
+ * thetas, a count in between runs the next larger one with its surplus slots idle and unwritten.  ws: unused, may be NULL (no
+ * workspace: nothing leaves the registers but the two log-sums).  BLM_ERR_INVALID, before any launch: NULL q, k, label, tgt,
+ * hi, thetas, lse or match; count outside 1..BLM_CACHE_THETAS_MAX; a theta that is negative or not finite; M < 0, Nk < 0,
+ * K < 1, ldq < K, ldk < K, window < 1, extents too large; BLM_ERR_ABI: abi_version.  M == 0: BLM_OK, nothing launched. */
+int blm_cache_scores(const float* q, int64_t ldq, const float* k, int64_t ldk, const int64_t* label, const int64_t* tgt,
+                     const int32_t* lo, const int32_t* hi, int window, int M, int Nk, int K, const blm_cache_thetas* thetas,
+                     float* lse, float* match, float* ws, void* stream);
+
+/* --------------------------------------------------------------------------
  * Search on the incremental path (csrc/beam.hip): the k best next words, beam selection, top-k / nucleus sampling.
  *
  * One total order of a row's entries is used throughout: value descending, then index ascending; -0 equals +0 and every NaN
