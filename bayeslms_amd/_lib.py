@@ -17,6 +17,7 @@ ABI_VERSION = 1
 TOPK_MAX = 256  # BLM_TOPK_MAX (include/bayeslm.h)
 ROW_TEMPS_MAX = 8  # BLM_ROW_TEMPS_MAX
 CACHE_THETAS_MAX = 8  # BLM_CACHE_THETAS_MAX
+DYNEVAL_RMS_WS_FLOATS = 4096  # BLM_DYNEVAL_RMS_WS_FLOATS
 OK = 0
 ERR_INVALID, ERR_ABI, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4  # blm_status (include/bayeslm.h)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -151,6 +152,9 @@ SIGNATURES = {
     "blm_row_stats": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_row_stats_temps": (_i, [_vp, _i64, _vp, _i, _i, C.POINTER(RowTemps), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_cache_scores": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(CacheThetas), _vp, _vp, _vp, _vp]),
+    "blm_dyneval_accum": (_i, [_vp, _vp, _i64, _vp]),
+    "blm_dyneval_rms": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "blm_dyneval_update": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _i, _vp]),
     "blm_topk_rows": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "blm_beam_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "blm_beam_select_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _i, C.POINTER(BeamPoolArgs),

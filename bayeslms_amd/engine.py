@@ -771,12 +771,13 @@ class EvalReport:
     mean_mi: Optional[float] = None        # mean mutual information between the word and the weights
     per_token: Optional[dict] = None       # keep_tokens: float / int arrays in text order, skipped tokens included (NaN / -1)
     cache: Optional[dict] = None           # neural cache (CacheReport.as_dict, with the fit's block after fit_cache); None: no cache
+    dyneval: Optional[dict] = None         # dynamic evaluation (DynEvalReport.as_dict beside the static loss, with the fit's block); None: none
     temperature: Optional[dict] = None     # temperature scaling (temperature_block); None: the distribution as the model gives it
 
     def as_dict(self):
         d = dataclasses.asdict(self)
         del d["per_token"]
-        for k in ("temperature", "cache"):  # a run without one writes what it wrote before there was one
+        for k in ("temperature", "cache", "dyneval"):  # a run without one writes what it wrote before there was one
             if d[k] is None:
                 del d[k]
         return d
@@ -1447,3 +1448,266 @@ def fit_cache(model, source, seq_len, window, passes=3, lo=1e-4, hi=16.0, points
     if not loss_after < loss_before:  # the cache does not help on this text: the model alone
         lam, loss_after = 0.0, loss_before
     return CacheFit(theta, float(lam), bool(search.at_bound or lam >= lam_max), loss_before, float(loss_after), curve)
+
+
+# ----------------------------------------------------------------------------
+# dynamic evaluation (Krause, Kahembwe, Murray, Renals 2018): the weights adapt to the text while it is scored
+# ----------------------------------------------------------------------------
+# The model families whose eval-mode forward back-propagates through the engine's ops into every mean weight (each tried once
+# on the GPU, tests/test_gpu_dyneval.py); any other class is refused by name.
+_DYNEVAL_FAMILIES = ("TransformerModel", "BayesTransformerModel", "RNNModel", "BayesRNNModel", "GaussTransformerModel",
+                     "VTransformerModel", "GaussRNNModel", "VariationalRNNModel")
+
+
+@dataclasses.dataclass
+class DynEvalStats:
+    """What dyneval_stats returns: the gradient statistics of the rms rule, in the layout of FlatBuffers(model)."""
+    rms: torch.Tensor   # (FlatBuffers.total,) float32 on the device: sqrt of the mean of g^2 over the windows; 0 in padding and log sigma
+    mean: torch.Tensor  # (2,) float32 on the device: rbar, the mean of rms over the live entries (rms > 0), and their number
+    live: int           # the number of live entries
+    windows: int        # windows that entered the statistics
+
+
+@dataclasses.dataclass
+class DynEvalReport:
+    """What evaluate_dynamic returns; ``as_dict()`` is the core of the ``dyneval`` block the evaluate command writes."""
+    tokens: int      # tokens that entered the figures (targets inside [0, V))
+    loss: float      # mean NLL, nats, every window scored BEFORE its update
+    ppl: float
+    lr: float
+    decay: float
+    eps: float
+    rule: str        # "sgd" | "rms"
+    windows: int
+    updates: int     # windows - 1: none follows the last window
+    per_token: Optional[dict] = None  # keep_tokens: tgt and nll in text order
+
+    def as_dict(self):
+        d = dataclasses.asdict(self)
+        del d["per_token"]
+        return d
+
+
+@dataclasses.dataclass
+class DynEvalFit:
+    """What fit_dyneval returns."""
+    lr: float
+    decay: float
+    loss: float         # the least loss of the curve; <= loss_static, since (0, 0) is always a candidate
+    loss_static: float  # the fit text at lr = decay = 0: the walk without adaptation
+    curve: list         # [lr, decay, loss] of every candidate, in the order evaluated
+
+
+def _dyneval_rate(who, name, v):
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ops.BayesLMError("%s: %s = %r is not a finite number >= 0" % (who, name, v))
+    return v
+
+
+def _dyneval_rates(who, lr, decay, eps):
+    return tuple(_dyneval_rate(who, k, v) for k, v in (("lr", lr), ("decay", decay), ("eps", eps)))
+
+
+def _dyneval_check_stats(who, flat, stats):
+    if stats is not None and (not isinstance(stats, DynEvalStats) or stats.rms.numel() != flat.total):
+        raise ops.BayesLMError("%s: stats must be the DynEvalStats of this model (%d flat entries), got %s" % (
+            who, flat.total, "%d entries" % stats.rms.numel() if isinstance(stats, DynEvalStats) else type(stats).__name__))
+
+
+def _dyneval_args(who, mc_samples=0, temperature=1.0, cache_window=None):
+    """The refusals of dynamic evaluation that need no model: all before any launch."""
+    if int(mc_samples) != 0:
+        raise ops.BayesLMError("%s: mc_samples = %r: dynamic evaluation under Monte-Carlo weight samples is not built (the update "
+                               "moves the mean weights, which sample would it follow?); run it at mean weights" % (who, mc_samples))
+    if float(temperature) != 1.0:
+        raise ops.BayesLMError("%s: temperature = %r: the gradient step is taken on the model's own NLL; a tempered one is not "
+                               "built" % (who, temperature))
+    if cache_window is not None:
+        raise ops.BayesLMError("%s: cache_window = %r: the neural cache together with dynamic evaluation is not built (its keys "
+                               "would come from weights that move)" % (who, cache_window))
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        raise ops.BayesLMError("%s runs in a single process (world size %d): more than one rank is not built, every column "
+                               "shares one set of adapting weights" % (who, dist.get_world_size()))
+
+
+@contextlib.contextmanager
+def _dyneval_session(who, model):
+    """The model re-homed into a FlatBuffers for one walk -> (flat, theta*: a copy of the flat weights).  On the way out, return
+    or exception alike, every parameter gets back its ORIGINAL storage (never written: the trained values bit for bit) and its
+    .grad, every module its training flag, and ops its gradient hook and embedding sink."""
+    name = type(model).__name__
+    if name not in _DYNEVAL_FAMILIES:
+        raise ops.BayesLMError("%s: %s: the eval-mode forward of this family is not known to back-propagate through the engine's "
+                               "ops (supported: %s)" % (who, name, ", ".join(_DYNEVAL_FAMILIES)))
+    state = getattr(model, "noise_state", None)
+    if state is not None and state.source == "torch":
+        raise ops.BayesLMError("%s: noise source 'torch' is a parity mode of training runs; dynamic evaluation runs at mean weights "
+                               "with the engine's own kernels (set_noise_source('philox'))" % who)
+    params = [p for p in model.parameters() if p.requires_grad]
+    if not params:
+        raise ops.BayesLMError("%s: %s has no trainable parameter" % (who, name))
+    saved = [(p, p.data, p.grad) for p in params]
+    flags = [(m, m.training) for m in model.modules()]
+    hook, sink = ops._GRAD_HOOK, ops._EMBED_SINK
+    try:
+        ops.set_grad_ready_hook(None)
+        ops.set_embed_grad_sink(None)
+        model.eval()
+        flat = FlatBuffers(model)
+        flat.flat_mom = None  # no momentum in this rule
+        yield flat, flat.flat_param.clone()
+    finally:
+        for p, data, grad in saved:
+            p.data = data
+            p.grad = grad
+        for m, t in flags:
+            m.training = t
+        ops.set_grad_ready_hook(hook)
+        ops.set_embed_grad_sink(sink)
+
+
+def _dyneval_windows(who, source, seq_len, limit=None):
+    """(start row, data, flat targets) of every window of ``seq_len`` rows, one at a time, the ragged last one included"""
+    from .data import get_batch
+    if int(seq_len) < 1:
+        raise ops.BayesLMError("%s: seq_len = %r" % (who, seq_len))
+    if source.dim() != 2 or source.shape[0] < 2:
+        raise ops.BayesLMError("%s: the stream holds %s rows: two are the least that give a target" % (who, tuple(source.shape)))
+    starts = list(range(0, source.size(0) - 1, int(seq_len)))
+    return [(i,) + tuple(get_batch(source, i, int(seq_len))) for i in (starts if limit is None else starts[:limit])]
+
+
+def _dyneval_walk(who, model, flat, windows, cols, after_backward):
+    """Steps 1 and 2 of every window: eval-mode forward in grad mode, the per-token NLL, the gradient of the window's mean NLL
+    into flat.flat_grad (which must be zero on entry to every window: ``after_backward(k, nll, last)`` sees to it) -> the
+    per-token NLLs, one device array per window."""
+    from .model import repackage_hidden
+    recurrent = hasattr(model, "init_hidden")
+    hidden = model.init_hidden(cols) if recurrent else None
+    nlls = []
+    with torch.enable_grad():
+        for k, (_, data, targets) in enumerate(windows):
+            if recurrent:
+                out, hidden = model(data, hidden)
+                hidden = repackage_hidden(hidden)
+            else:
+                out = model(data)
+            if not out.requires_grad:
+                raise ops.BayesLMError("%s: the eval-mode forward of %s gave logits without a gradient path" % (who, type(model).__name__))
+            loss, nll = ops.cross_entropy(out.view(-1, out.shape[-1]), targets, unit_grad=True)
+            loss.backward()
+            nlls.append(nll)
+            after_backward(k, nll, k == len(windows) - 1)
+    return nlls
+
+
+def dyneval_stats(model, source, seq_len, windows):
+    """The gradient statistics of the rms rule from the first ``windows`` windows of ``source`` (the training text), walked as
+    evaluate_dynamic walks its text but with NO update: MS = the mean over those windows of g^2, rms = sqrt(MS), and rbar, the
+    mean of rms over the live entries MS > 0 (blm_dyneval_accum per window, blm_dyneval_rms once) -> DynEvalStats.  A text with
+    fewer windows gives them all (``windows`` of the result says how many).  Leaves the model as it found it."""
+    who = "dyneval_stats"
+    _dyneval_args(who)
+    if int(windows) < 1:
+        raise ops.BayesLMError("%s: windows = %r, the statistics need at least one" % (who, windows))
+    with _dyneval_session(who, model) as (flat, _):
+        wins = _dyneval_windows(who, source, seq_len, int(windows))
+        ms = torch.zeros_like(flat.flat_grad)
+
+        def accumulate(k, nll, last):
+            ops.dyneval_accum(ms, flat.flat_grad)
+            flat.zero_grad()
+
+        _dyneval_walk(who, model, flat, wins, source.shape[1], accumulate)
+        rms, mean = ops.dyneval_rms(ms, len(wins))
+        return DynEvalStats(rms, mean, int(mean[1].item()), len(wins))
+
+
+def _dyneval_run(who, model, flat, theta0, source, wins, lr, decay, stats, eps, keep_tokens, on_window):
+    """One adapted walk from theta* inside a session -> DynEvalReport"""
+    with torch.no_grad():
+        flat.flat_param.copy_(theta0)
+    flat.zero_grad()
+    rms, mean = (None, None) if stats is None else (stats.rms, stats.mean)
+
+    def update(k, nll, last):
+        if on_window is not None:
+            on_window(k, nll)
+        if not last:
+            ops.dyneval_update(flat.flat_param, flat.flat_grad, theta0, lr, decay, rms, mean, eps, zero_grad=True)
+
+    nlls = _dyneval_walk(who, model, flat, wins, source.shape[1], update)
+    V = model.decoder.weight.shape[0]  # targets outside [0, V) are skipped, as evaluate_report skips them
+    tgt = torch.cat([w[2] for w in wins]).cpu().numpy()
+    nll = torch.cat(nlls).cpu().numpy()
+    valid = (tgt >= 0) & (tgt < V)
+    base = report_from_tokens(nll, valid=valid)
+    rep = DynEvalReport(tokens=base.tokens, loss=base.loss, ppl=base.ppl, lr=lr, decay=decay, eps=eps,
+                        rule="sgd" if stats is None else "rms", windows=len(wins), updates=max(0, len(wins) - 1))
+    if keep_tokens:
+        nrows, cols = source.shape
+        col0 = np.arange(cols, dtype=np.int64) * nrows
+        pos = np.concatenate([(np.arange(i + 1, i + 1 + len(d), dtype=np.int64)[:, None] + col0[None, :]).reshape(-1)
+                              for i, d, _ in wins])
+        order = np.argsort(pos, kind="stable")
+        rep.per_token = {"tgt": tgt[order], "nll": nll[order]}
+    return rep
+
+
+def evaluate_dynamic(model, source, seq_len, lr, decay, stats=None, eps=0.01, keep_tokens=False, on_window=None, mc_samples=0,
+                     temperature=1.0, cache_window=None):
+    """Held-out loss of ``model`` over the batchified stream ``source`` under dynamic evaluation -> DynEvalReport.
+
+    The text is walked in windows of ``seq_len`` rows, ONE at a time (no grouping as in evaluate: a window must not see weights
+    adapted on its own future); all columns share one set of weights.  Window k is scored in eval mode (mean weights, no dropout,
+    no noise) under the weights theta_k -- that NLL is what the report sums -- then the gradient g of its mean NLL (no KL, no
+    clip) moves the weights by one fused pass over the flat buffers (ops.dyneval_update, blm_dyneval_update):
+        sgd rule (``stats`` None):  theta <- theta - lr g                    + min(1, decay)          (theta* - theta)
+        rms rule (dyneval_stats):   theta <- theta - lr g / (r + eps rbar)   + min(1, decay r / rbar) (theta* - theta)
+    and clears g in the same pass.  No update follows the last window.  An LSTM's state is carried and detached between windows,
+    a Transformer's windows are independent.  ``on_window(k, nll)`` is called after window k's backward, before its update.
+    The walk synchronises with the host only at its end (and wherever ``on_window`` does).
+
+    The model is left as it was found, on return and on an exception: every parameter in its original storage with its values
+    bit for bit, every .grad, the training flags, ops' gradient hook and embedding sink.
+
+    Refused: mc_samples other than 0, a temperature other than 1, a cache window, more than one rank, noise source 'torch', a
+    model family outside _DYNEVAL_FAMILIES, lr / decay / eps negative or not finite, stats of another model."""
+    who = "evaluate_dynamic"
+    _dyneval_args(who, mc_samples, temperature, cache_window)
+    lr, decay, eps = _dyneval_rates(who, lr, decay, eps)
+    with _dyneval_session(who, model) as (flat, theta0):
+        _dyneval_check_stats(who, flat, stats)
+        wins = _dyneval_windows(who, source, seq_len)
+        return _dyneval_run(who, model, flat, theta0, source, wins, lr, decay, stats, eps, keep_tokens, on_window)
+
+
+def fit_dyneval(model, source, seq_len, lrs, decays, stats=None, eps=0.01, max_windows=None, mc_samples=0, temperature=1.0,
+                cache_window=None):
+    """The (lr, decay) of the grid ``lrs`` x ``decays`` that minimises evaluate_dynamic's loss on the held-out stream ``source``
+    (its first ``max_windows`` windows, default all) -> DynEvalFit.  A plain grid: every candidate starts from the trained
+    weights and is one evaluate_dynamic walk, bit for bit.  (0, 0), the walk without adaptation, is always a candidate and comes
+    first, so the fitted loss never exceeds ``loss_static``; among equal losses the earlier candidate wins."""
+    who = "fit_dyneval"
+    _dyneval_args(who, mc_samples, temperature, cache_window)
+    if max_windows is not None and int(max_windows) < 1:
+        raise ops.BayesLMError("%s: max_windows = %r" % (who, max_windows))
+    eps = _dyneval_rate(who, "eps", eps)
+    cands = [(0.0, 0.0)]
+    for a in lrs:
+        for b in decays:
+            c = (_dyneval_rate(who, "lr", a), _dyneval_rate(who, "decay", b))
+            if c not in cands:
+                cands.append(c)
+    with _dyneval_session(who, model) as (flat, theta0):
+        _dyneval_check_stats(who, flat, stats)
+        if max_windows is not None:
+            source = source[:int(max_windows) * int(seq_len) + 1]
+        wins = _dyneval_windows(who, source, seq_len)
+        curve = [[a, b, _dyneval_run(who, model, flat, theta0, source, wins, a, b, stats, eps, False, None).loss] for a, b in cands]
+    best = min(curve, key=lambda c: c[2])
+    return DynEvalFit(lr=best[0], decay=best[1], loss=best[2], loss_static=curve[0][2], curve=curve)

@@ -32,7 +32,18 @@ the N decoder-input rows before each word, mixed into the model's distribution w
 ... | loss a -> b | ppl a -> b | hit ...`` and the report a ``cache`` block (CacheReport.as_dict, plus ``fitted_on``,
 ``at_bound``, ``fit_loss_before``, ``fit_loss_after`` and ``curve`` after a fit); every other figure stays the model's own.  The
 cache runs at mean weights and at temperature 1: ``--mc-samples``, ``--temperature`` and ``--fit-temperature-on`` are refused with
-it.  Without ``--cache-window`` the line and the report are what they were."""
+it.  Without ``--cache-window`` the line and the report are what they were.
+
+Dynamic evaluation.  ``--dyneval-lr ETA --dyneval-decay LAMBDA`` also scores ``--data`` with the weights adapting to it
+(engine.evaluate_dynamic: the text window by window, one gradient step on each window after it was scored, pulled back towards the
+trained weights), or ``--fit-dyneval-on PATH --dyneval-lr-grid a,b,c --dyneval-decay-grid a,b,c`` picks the pair on that text
+first (engine.fit_dyneval, a plain grid over its first ``--dyneval-fit-windows`` windows).  ``--dyneval-stats-on PATH`` selects the
+rms rule: the step of every weight is scaled by the root mean square of its gradient over the first ``--dyneval-stats-windows``
+windows of that text (the training text).  The summary line gains ``| dyneval rule ... lr ... decay ... | loss a -> b | ppl a ->
+b`` and the report a ``dyneval`` block (DynEvalReport.as_dict, ``base_loss`` / ``base_ppl`` of the static report, and
+``fitted_on``, ``fit_loss_before``, ``fit_loss_after`` and ``curve`` after a fit); every other figure, ``--write-tokens`` included,
+stays the static model's.  Refused with it: ``--mc-samples``, ``--temperature``, ``--fit-temperature-on``, ``--cache-window``.
+Without these flags the line and the report are what they were."""
 import argparse
 import json
 import math
@@ -83,7 +94,76 @@ def build_parser():
     p.add_argument('--fit-cache-on', type=str, default='', metavar='PATH',
                    help='fit theta and lambda on this held-out text (the validation text), then score --data with them')
     p.add_argument('--cache-fit-passes', type=int, default=3, help='search launches of the cache fit (1..6), eight thetas each')
+    p.add_argument('--dyneval-lr', type=float, default=None, metavar='ETA',
+                   help='also score --data under dynamic evaluation with this learning rate (with --dyneval-decay)')
+    p.add_argument('--dyneval-decay', type=float, default=None, metavar='LAMBDA', help='pull of the weights back towards the trained ones')
+    p.add_argument('--dyneval-epsilon', type=float, default=0.01, metavar='EPS',
+                   help='rms rule: floor of the gradient scale, relative to the mean scale (default 0.01; nobody has measured '
+                        'this default here)')
+    p.add_argument('--dyneval-stats-on', type=str, default='', metavar='PATH',
+                   help='the rms rule: gradient statistics from this text (the training text); without it the sgd rule')
+    p.add_argument('--dyneval-stats-windows', type=int, default=100, metavar='W', help='windows of --dyneval-stats-on that are read')
+    p.add_argument('--fit-dyneval-on', type=str, default='', metavar='PATH',
+                   help='pick the learning rate and decay on this held-out text (the validation text) from the two grids')
+    p.add_argument('--dyneval-lr-grid', type=str, default='', metavar='a,b,c')
+    p.add_argument('--dyneval-decay-grid', type=str, default='', metavar='a,b,c')
+    p.add_argument('--dyneval-fit-windows', type=int, default=None, metavar='N', help='windows of --fit-dyneval-on a candidate walks (default all)')
     return p
+
+
+def dyneval_grid(text, flag):
+    """"a,b,c" -> [a, b, c]: finite numbers >= 0, at least one"""
+    try:
+        vals = [float(v) for v in text.split(",") if v.strip()]
+    except ValueError:
+        raise SystemExit("%s must be numbers separated by commas (got %r)" % (flag, text))
+    if not vals or not all(math.isfinite(v) and v >= 0 for v in vals):
+        raise SystemExit("%s needs at least one value, each finite and >= 0 (got %r)" % (flag, text))
+    return vals
+
+
+def check_dyneval_args(args):
+    """The dynamic-evaluation flags' refusals: before any file or device is touched."""
+    given = args.dyneval_lr is not None or args.dyneval_decay is not None
+    fit = bool(args.fit_dyneval_on)
+    if not given and not fit:
+        if args.dyneval_stats_on or args.dyneval_lr_grid or args.dyneval_decay_grid or args.dyneval_fit_windows is not None:
+            raise SystemExit("--dyneval-stats-on, --dyneval-lr-grid, --dyneval-decay-grid and --dyneval-fit-windows need "
+                             "--dyneval-lr with --dyneval-decay, or --fit-dyneval-on")
+        return
+    if fit and given:
+        raise SystemExit("--fit-dyneval-on and --dyneval-lr / --dyneval-decay exclude each other: give the values or the text to fit them on")
+    if fit and not (args.dyneval_lr_grid and args.dyneval_decay_grid):
+        raise SystemExit("--fit-dyneval-on needs --dyneval-lr-grid and --dyneval-decay-grid")
+    if not fit and (args.dyneval_lr_grid or args.dyneval_decay_grid or args.dyneval_fit_windows is not None):
+        raise SystemExit("--dyneval-lr-grid, --dyneval-decay-grid and --dyneval-fit-windows need --fit-dyneval-on")
+    if not fit and (args.dyneval_lr is None or args.dyneval_decay is None):
+        raise SystemExit("--dyneval-lr and --dyneval-decay go together")
+    if args.mc_samples:
+        raise SystemExit("dynamic evaluation with --mc-samples: the update moves the mean weights, it runs at mean weights")
+    if args.temperature is not None or args.fit_temperature_on:
+        raise SystemExit("dynamic evaluation with --temperature / --fit-temperature-on: the gradient step is taken on the untempered NLL")
+    if args.cache_window is not None:
+        raise SystemExit("dynamic evaluation with --cache-window: the two together are not built")
+    for flag, v in (("--dyneval-lr", args.dyneval_lr), ("--dyneval-decay", args.dyneval_decay), ("--dyneval-epsilon", args.dyneval_epsilon)):
+        if v is not None and not (math.isfinite(v) and v >= 0):
+            raise SystemExit("%s must be finite and >= 0 (got %r)" % (flag, v))
+    if fit:
+        dyneval_grid(args.dyneval_lr_grid, "--dyneval-lr-grid")
+        dyneval_grid(args.dyneval_decay_grid, "--dyneval-decay-grid")
+    if args.dyneval_stats_windows < 1:
+        raise SystemExit("--dyneval-stats-windows must be at least 1 (got %d)" % args.dyneval_stats_windows)
+    if args.dyneval_fit_windows is not None and args.dyneval_fit_windows < 1:
+        raise SystemExit("--dyneval-fit-windows must be at least 1 (got %d)" % args.dyneval_fit_windows)
+
+
+def dyneval_block(rep, base, fit=None, fitted_on=None):
+    """The ``dyneval`` block of the report: the DynEvalReport ``rep`` beside the static EvalReport ``base``, and the DynEvalFit"""
+    d = rep.as_dict()
+    d.update(base_loss=base.loss, base_ppl=base.ppl)
+    if fit is not None:
+        d.update(fitted_on=fitted_on, fit_loss_before=fit.loss_static, fit_loss_after=fit.loss, curve=fit.curve)
+    return d
 
 
 def check_cache_args(args):
@@ -114,6 +194,7 @@ def check_cache_args(args):
 def check_args(args):
     """Refusals that need neither the input files, the model nor a device."""
     check_cache_args(args)
+    check_dyneval_args(args)
     if args.temperature is not None and args.fit_temperature_on:
         raise SystemExit("--temperature and --fit-temperature-on exclude each other: give T or the text to fit it on")
     if args.temperature is not None and not (math.isfinite(args.temperature) and args.temperature > 0):
@@ -141,6 +222,10 @@ def summary_line(rep):
     if c:
         line += " | cache window %d theta %.6g lambda %.4f | loss %.4f -> %.4f | ppl %.2f -> %.2f | hit %.4f" % (
             c["window"], c["theta"], c["lam"], c["base_loss"], c["loss"], c["base_ppl"], c["ppl"], c["cache_hit_rate"])
+    d = rep.dyneval
+    if d:
+        line += " | dyneval rule %s lr %.6g decay %.6g | loss %.4f -> %.4f | ppl %.2f -> %.2f" % (
+            d["rule"], d["lr"], d["decay"], d["base_loss"], d["loss"], d["base_ppl"], d["ppl"])
     return line
 
 
@@ -180,6 +265,13 @@ def main(argv=None):
         if len(cache_fit_text) // args.batch_size < 2:
             raise SystemExit("--fit-cache-on holds %d tokens: fewer than two rows of --batch-size %d columns"
                              % (len(cache_fit_text), args.batch_size))
+    dyn_texts = {}
+    for flag, path in (("--dyneval-stats-on", args.dyneval_stats_on), ("--fit-dyneval-on", args.fit_dyneval_on)):
+        if path:
+            dyn_texts[flag] = corpus.tokenize(path)
+            if len(dyn_texts[flag]) // args.batch_size < 2:
+                raise SystemExit("%s holds %d tokens: fewer than two rows of --batch-size %d columns"
+                                 % (flag, len(dyn_texts[flag]), args.batch_size))
     args.interpolation_flag = 0
     model, _ = S.build_models(args, len(corpus.dictionary))
     S.load_partial(model, args.model_path)
@@ -211,6 +303,20 @@ def main(argv=None):
         if cfit is not None:
             rep.cache.update(fitted_on=args.fit_cache_on, at_bound=cfit.at_bound, fit_loss_before=cfit.loss_before,
                              fit_loss_after=cfit.loss_after, curve=cfit.curve)
+    if args.dyneval_lr is not None or args.fit_dyneval_on:
+        lr, decay, stats, dfit = args.dyneval_lr, args.dyneval_decay, None, None
+        if args.dyneval_stats_on:
+            stats = engine.dyneval_stats(model, D.batchify(dyn_texts["--dyneval-stats-on"], args.batch_size, device), args.seq_len,
+                                         args.dyneval_stats_windows)
+        if args.fit_dyneval_on:
+            dfit = engine.fit_dyneval(model, D.batchify(dyn_texts["--fit-dyneval-on"], args.batch_size, device), args.seq_len,
+                                      dyneval_grid(args.dyneval_lr_grid, "--dyneval-lr-grid"),
+                                      dyneval_grid(args.dyneval_decay_grid, "--dyneval-decay-grid"), stats=stats,
+                                      eps=args.dyneval_epsilon, max_windows=args.dyneval_fit_windows)
+            lr, decay = dfit.lr, dfit.decay
+        dyn = engine.evaluate_dynamic(model, D.batchify(text, args.batch_size, device), args.seq_len, lr, decay, stats=stats,
+                                      eps=args.dyneval_epsilon)
+        rep.dyneval = dyneval_block(dyn, rep, dfit, args.fit_dyneval_on)
     print(summary_line(rep), flush=True)
     if args.write_report:
         with open(args.write_report, 'w') as f:

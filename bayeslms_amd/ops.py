@@ -2553,6 +2553,73 @@ def cache_mix(nll_model, lse, match, lam):
     return torch.where(torch.isneginf(lse), nll_model, mixed)
 
 
+def _dyneval_flat(who, **arrays):
+    """The flat operands of the dynamic-evaluation kernels: float32, contiguous, on this process's GPU, of one length (they
+    are updated in place or read at the same index, so a copy of a strided one would be the wrong tensor) -> that length"""
+    n = None
+    for name, t in arrays.items():
+        if not torch.is_tensor(t):
+            raise BayesLMError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+        if dev_tensor(t, "%s: %s" % (who, name)) is not t:
+            raise BayesLMError("%s: %s must be contiguous (it is used in place)" % (who, name))
+        if n is None:
+            n, first = t.numel(), name
+        elif t.numel() != n:
+            raise BayesLMError("%s: %s has %d elements, %s has %d" % (who, name, t.numel(), first, n))
+    return n
+
+
+def _dyneval_rate(who, name, v):
+    v = float(v)
+    if not (math.isfinite(v) and v >= 0.0 and float(torch.tensor(v, dtype=torch.float32)) < math.inf):
+        raise BayesLMError("%s: %s = %r is not a finite float32 number >= 0" % (who, name, v))
+    return v
+
+
+def dyneval_accum(ms, g):
+    """ms += g * g over two flat float32 arrays of one length (blm_dyneval_accum): one window's share of the gradient
+    statistics of dynamic evaluation.  In place; -> ms"""
+    n = _dyneval_flat("dyneval_accum", ms=ms, g=g)
+    L.require_gfx950()
+    calls().blm_dyneval_accum(ptr(ms), ptr(g), n, stream())
+    return ms
+
+
+def dyneval_rms(ms, count):
+    """-> (rms, mean): rms = sqrt(ms / count) and the DEVICE pair mean = [rbar, live] -- rbar the mean of rms over the live
+    entries (ms > 0), live their number (blm_dyneval_rms: double partial sums in a fixed order, the same bits in every run).
+    Raises when no entry is live (rbar = 0: the rms rule would divide by it); that check reads the pair back once."""
+    n = _dyneval_flat("dyneval_rms", ms=ms)
+    count = int(count)
+    if count < 1:
+        raise BayesLMError("dyneval_rms: count = %d, the statistics need at least one window" % count)
+    L.require_gfx950()
+    rms, mean = torch.empty_like(ms), torch.empty(2, device=ms.device, dtype=torch.float32)
+    ws = torch.empty(L.DYNEVAL_RMS_WS_FLOATS, device=ms.device, dtype=torch.float32)
+    calls().blm_dyneval_rms(ptr(ms), n, count, ptr(rms), ptr(mean), ptr(ws), stream())
+    if not float(mean[1]) > 0.0:
+        raise BayesLMError("dyneval_rms: no live entry among %d (every mean square is zero): rbar = 0 and the rms rule is undefined"
+                           % n)
+    return rms, mean
+
+
+def dyneval_update(p, g, p0, lr, decay, rms=None, mean=None, eps=0.01, zero_grad=True):
+    """The per-window update of dynamic evaluation over flat float32 arrays of one length, in place on ``p``
+    (blm_dyneval_update, one pass): p <- p - step + d (p0 - p) with step = lr g, d = min(1, decay) (sgd rule: ``rms`` and
+    ``mean`` None) or step = lr g / (rms + eps rbar), d = min(1, decay rms / rbar) (rms rule: both from dyneval_rms; rbar is read
+    on the device).  ``zero_grad``: g = 0 in the same pass.  -> p"""
+    if (rms is None) != (mean is None):
+        raise BayesLMError("dyneval_update: rms and mean go together (both from dyneval_rms for the rms rule, neither for sgd)")
+    arrays = dict(p=p, g=g, p0=p0) if rms is None else dict(p=p, g=g, p0=p0, rms=rms)
+    n = _dyneval_flat("dyneval_update", **arrays)
+    if mean is not None and (_dyneval_flat("dyneval_update", mean=mean) != 2):
+        raise BayesLMError("dyneval_update: mean must hold 2 floats (rbar, live), got %d" % mean.numel())
+    lr, decay, eps = (_dyneval_rate("dyneval_update", k, v) for k, v in (("lr", lr), ("decay", decay), ("eps", eps)))
+    L.require_gfx950()
+    calls().blm_dyneval_update(ptr(p), ptr(g), ptr(p0), ptr(rms), ptr(mean), n, lr, decay, eps, 1 if zero_grad else 0, stream())
+    return p
+
+
 def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=1.0):
     """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
     with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64

@@ -606,6 +606,50 @@ int blm_cache_scores(const float* q, int64_t ldq, const float* k, int64_t ldk, c
                      float* lse, float* match, float* ws, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Dynamic evaluation (csrc/dyneval.hip; Krause, Kahembwe, Murray, Renals, ICML 2018): the weights adapt to the text while it is
+ * scored.  The text is laid out as the evaluation lays it out, in columns, and walked in windows of seq_len rows, ONE window at
+ * a time (no grouping of windows: a window must not see weights adapted on its own future); all columns share one set of
+ * weights (one column is the paper's setting).  For window k with weights theta_k (theta_0 = theta*, the trained weights):
+ *   1. score     eval mode (mean weights, no dropout, no noise), grad enabled; NLL_k, the per-token NLL of the window under
+ *                theta_k, is what the report sums.  An LSTM's state is carried and detached between windows, a Transformer's
+ *                windows are independent, as in the static evaluation.
+ *   2. gradient  g = gradient of the window's MEAN NLL over its tokens.  No KL term, no clip.
+ *   3. update    none after the last window; element-wise over every trainable parameter
+ *        sgd rule (no statistics):  theta <- theta - eta g                     + min(1, lambda)          (theta* - theta)
+ *        rms rule:                  theta <- theta - eta g / (r + eps rbar)    + min(1, lambda r / rbar) (theta* - theta)
+ *        r_i = sqrt(MS_i), MS_i the mean of g_i^2 over the statistics windows; rbar the mean of r over the LIVE entries, those
+ *        with MS_i > 0 (in eval mode log sigma never receives a gradient and a flat buffer has padding: neither may dilute
+ *        rbar).  eps is RELATIVE to rbar (the paper's absolute epsilon is eps rbar): it bounds the step of an entry the
+ *        statistics never saw, such as an embedding row absent from the statistics text, to 1 / eps average steps whatever the
+ *        scale of the gradients.
+ *   4. statistics  steps 1-2 on another text (the training text) for its first W windows with NO update; MS = sum of g^2 / W.
+ * In fp32 the update is evaluated as exactly  p - step + d * (p0 - p)  without contraction, with
+ *   sgd: step = lr * g,                                     d = min(1, decay)
+ *   rms: step = g == 0 ? 0 : (lr * g) / (r + eps * rbar),   d = min(1, (decay / rbar) * r)
+ * (eps * rbar and decay / rbar rounded once per launch), so an entry with g = 0 and p = p0 keeps its bits under either rule.
+ *
+ * The three entry points work on flat arrays of n floats (one call covers a whole model held in one flat buffer; no pointer
+ * table).  Arrays that are 16-byte aligned take 16-byte loads and stores over the body and a scalar tail; any other alignment
+ * (of a float) is ACCEPTED and takes the scalar path for the whole array.  BLM_ERR_INVALID, before any launch: a NULL array,
+ * n < 0 or n > 2^40, count < 1, lr / decay / eps negative or not finite, rms given without mean or mean without rms, ws not
+ * 8-byte aligned.  n == 0: BLM_OK (blm_dyneval_rms still writes mean = {0, 0}).
+ * -------------------------------------------------------------------------- */
+/* floats of workspace blm_dyneval_rms needs (two doubles per workgroup of its first stage), 8-byte aligned */
+#define BLM_DYNEVAL_RMS_WS_FLOATS 4096
+/* ms[i] += g[i]^2 */
+int blm_dyneval_accum(float* ms, const float* g, int64_t n, void* stream);
+/* rms[i] = sqrt(ms[i] / count); mean (DEVICE float[2]) = { rbar = mean of rms over the entries with ms > 0 (0 without one), the
+ * number of those entries as a float (exact up to 2^24, rounded beyond) }.  The partial sums are doubles, added in two stages
+ * in a fixed order without atomics: the same bits in every run, deterministic option or not.  rms must not overlap ms. */
+int blm_dyneval_rms(const float* ms, int64_t n, int count, float* rms, float* mean, float* ws, void* stream);
+/* One grid-stride pass over p (updated in place), g, p0 and, for the rms rule, rms.  rms == NULL and mean == NULL: the sgd rule
+ * (eps unused).  mean is the DEVICE pair blm_dyneval_rms wrote: rbar is read on the device, so a walk needs no host
+ * synchronisation; it must be > 0 (a statistics run without a live entry is the caller's error to report).  zero_grad != 0
+ * also writes g = 0 in the same pass.  p, g, p0 and rms must not overlap one another. */
+int blm_dyneval_update(float* p, float* g, const float* p0, const float* rms, const float* mean, int64_t n, float lr, float decay,
+                       float eps, int zero_grad, void* stream);
+
+/* --------------------------------------------------------------------------
  * Search on the incremental path (csrc/beam.hip): the k best next words, beam selection, top-k / nucleus sampling.
  *
  * One total order of a row's entries is used throughout: value descending, then index ascending; -0 equals +0 and every NaN
