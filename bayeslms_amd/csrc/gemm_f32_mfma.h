@@ -251,6 +251,16 @@ template <int S> struct FragG<false, 2, S> {
       for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(v[s][0]), "+v"(v[s][1]));
     }
   }
+  // sum[i] += the group's four k-steps of MFMA tile i, as (even steps, odd steps): the ST64 registers are already
+  // k-step pairs, so one v_pk_add_f32 per pair and no register move (the wgrad bias gradient, compute_dma).  Inline asm:
+  // the C++ form under a wave-uniform condition is if-converted -- every wave then executes the adds plus a v_cndmask per
+  // register -- where the statement must stay behind its scalar branch.
+  __device__ __forceinline__ void add_k(f32x2 (&sum)[2]) {
+    static_assert(ST64, "summed from the unpadded LDS-DMA images only");
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      asm volatile("v_pk_add_f32 %0, %0, %1\n\tv_pk_add_f32 %0, %0, %2" : "+v"(sum[i]) : "v"(w[i][0]), "v"(w[i][1]));
+  }
 };
 template <int S> struct FragG<false, 1, S> {
   static constexpr bool ST64 = S % 64 == 0;  // see FragG<false, 2, S>
@@ -279,6 +289,10 @@ template <int S> struct FragG<false, 1, S> {
 #pragma unroll
       for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(v[s]));
     }
+  }
+  __device__ __forceinline__ void add_k(f32x2 (&sum)[1]) {  // see FragG<false, 2, S>
+    static_assert(ST64, "summed from the unpadded LDS-DMA images only");
+    asm volatile("v_pk_add_f32 %0, %0, %1\n\tv_pk_add_f32 %0, %0, %2" : "+v"(sum[0]) : "v"(w[0]), "v"(w[1]));
   }
 };
 // ---- LDS-DMA loaders ----------------------------------------------------------------------------
@@ -1031,10 +1045,26 @@ __global__ __launch_bounds__(128 * WGN, WGN == 2 ? 2 : 1) void gemm_f32_kernel(c
 
   // LDS-DMA path: fragment addresses of the swizzled tiles and the per-wave DMA sources
   const int swz = (li >> 1) & 7;  // (row >> 1) & 7 of this lane's MFMA row (same for both 32-row tiles)
-  float cs1 = 0.f;                // LDS-DMA wgrad: this thread's column of the bias gradient (threads 0..BM-1)
+  // LDS-DMA wgrad: the bias gradient (column sums of A = dY) is summed from the A fragments the wave holds for its MFMAs anyway:
+  // lane (li, lh) has A[k = 8 t4 + 4 lh + s][row 32 i + li of the wave's row group], csf.p[i] = its partial sum over k as (even s,
+  // odd s).  The WGN wave columns of a row group read identical fragments and share the groups: wave column wn adds the groups
+  // with t4 % WGN == wn (csf.wn: wave uniform, -1 = this workgroup sums nothing) -- 4 / WGN groups x 2 WTM packed adds per K tile
+  // and wave, no LDS read, no wait.  Reduced once after the K loop.
+  // (The opt-in split-bf16 kernels keep the walk over the LDS tile by threads 0..BM-1, cs1: the partials' registers would cost
+  // their 64 x 64 form a workgroup per CU.)
+  constexpr bool CS_FRAG = DMA && !A_KMAJ && SPLIT == 0, CS_WALK = DMA && !A_KMAJ && SPLIT != 0;
+  struct CsOff {};  // every other instantiation (NT / NN, register-staged): no such state at all
+  struct CsPartials { f32x2 p[WTM]; int wn; };
+  typename std::conditional<CS_FRAG, CsPartials, CsOff>::type csf;
+  if constexpr (CS_FRAG) {
+#pragma unroll
+    for (int i = 0; i < WTM; ++i) csf.p[i] = (f32x2)(0.f);
+    csf.wn = do_cs ? __builtin_amdgcn_readfirstlane(wn) : -1;
+  }
+  typename std::conditional<CS_WALK, float, CsOff>::type cs1{};
   auto compute_dma = [&](int cur) {
     if constexpr (DMA) {
-      if constexpr (!A_KMAJ) {
+      if constexpr (CS_WALK) {
         if (do_cs && t < BM) {  // column sums of the A tile (= dY tile) straight from LDS
           const float* col = As + cur * TA + t;
 #pragma unroll 8
@@ -1125,6 +1155,13 @@ __global__ __launch_bounds__(128 * WGN, WGN == 2 ? 2 : 1) void gemm_f32_kernel(c
         }
         a[t4 & 1].tie();
         b[t4 & 1].tie();
+        if constexpr (CS_FRAG) {  // behind the counted wait and the ties: the group has landed, nothing LGKM-counted is added
+          // the compare stays here, on a scalar register (hoisted out of the loop it comes back as a lane mask that hipcc
+          // rebuilds through a VGPR every trip: two vector instructions per group for every wave)
+          int sel = csf.wn;
+          asm volatile("" : "+s"(sel));
+          if (sel == t4 % WGN) a[t4 & 1].add_k(csf.p);
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4)
@@ -1337,8 +1374,23 @@ __global__ __launch_bounds__(128 * WGN, WGN == 2 ? 2 : 1) void gemm_f32_kernel(c
     __syncthreads();
   }
 
-  if constexpr (!A_KMAJ && DMA) {
+  if constexpr (CS_WALK) {
     if (do_cs && t < BM && m0 + t < p.M) atomicAdd(p.colsum_a + m0 + t, cs1 * p.alpha);
+  }
+  if constexpr (CS_FRAG) {
+    if (do_cs) {  // uniform over the workgroup.  The partials meet in LDS as [wn][lh][row] and are added in that order
+      float* red = smem;  // every tile is consumed and the K loop ended in a barrier: the staging buffers are free
+#pragma unroll
+      for (int i = 0; i < WTM; ++i) red[(2 * wn + lh) * BM + wm * (32 * WTM) + 32 * i + li] = csf.p[i].x + csf.p[i].y;  // the operand read's lane -> row map
+      __syncthreads();
+      if (t < BM && m0 + t < p.M) {
+        float sum = 0.f;
+#pragma unroll
+        for (int g = 0; g < 2 * WGN; ++g) sum += red[g * BM + t];
+        atomicAdd(p.colsum_a + m0 + t, sum * p.alpha);
+      }
+      __syncthreads();  // epilogue_rows stages in the same memory
+    }
   }
   if constexpr (!A_KMAJ && !DMA) {
     if (do_cs) {  // reduce the per-thread partial column sums over the k-row groups through LDS

@@ -60,7 +60,7 @@ def main():
                 bad += 1
                 print("SCRATCH IN LOOP", kern, i, t)
         print(f, "counted-wait regions:", regions)
-        bad += valu_in_loops(lines, r"^(_ZN3blm15gemm_f32_kernelILi\dELi\dELi\dELb0ELb1ELi0E\S+):", "global_load_lds", 4 if f != "gemm_tn" else 16)  # TN: + the bias-gradient column sums' branch and the second tile's read bases
+        bad += valu_in_loops(lines, r"^(_ZN3blm15gemm_f32_kernelILi\dELi\dELi\dELb0ELb1ELi0E\S+):", "global_load_lds", 4 if f != "gemm_tn" else 16)  # TN: + the second tile's read bases.  The bias-gradient sums are 16 (one MFMA row tile per wave) or 32 (two) v_pk_add_f32 per two-tile trip behind eight wave-uniform branches, one per fragment group: a wave of the n0 == 0 workgroups runs 2 of the 8 (eight-wave tile) or 4 of the 8, every other wave none.  With those branches hipcc closes a trip with a conditional exit and an unconditional s_branch back, which this finder does not follow: the TN steady loops are NOT counted at present (profiles/r18_isa_audit_matrix_loops.txt has them counted by hand)
     bad += audit_lstm()
     print("OK" if bad == 0 else "%d problems" % bad)
     return 1 if bad else 0
