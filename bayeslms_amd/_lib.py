@@ -18,6 +18,8 @@ TOPK_MAX = 256  # BLM_TOPK_MAX (include/bayeslm.h)
 ROW_TEMPS_MAX = 8  # BLM_ROW_TEMPS_MAX
 CACHE_THETAS_MAX = 8  # BLM_CACHE_THETAS_MAX
 DYNEVAL_RMS_WS_FLOATS = 4096  # BLM_DYNEVAL_RMS_WS_FLOATS
+EDIT_MAX_LEN = 1023  # BLM_EDIT_MAX_LEN
+NBEST_GRID_MAX = 64  # BLM_NBEST_GRID_MAX
 OK = 0
 ERR_INVALID, ERR_ABI, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4  # blm_status (include/bayeslm.h)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -83,6 +85,13 @@ class RowTemps(C.Structure):
 class CacheThetas(C.Structure):
     """blm_cache_thetas (include/bayeslm.h)."""
     _fields_ = [("abi_version", C.c_uint32), ("count", C.c_int32), ("theta", C.c_float * CACHE_THETAS_MAX)]
+
+
+class NbestGrid(C.Structure):
+    """blm_nbest_grid (include/bayeslm.h)."""
+    _fields_ = [("abi_version", C.c_uint32), ("G", C.c_int32), ("lmwt", C.c_double * NBEST_GRID_MAX),
+                ("nnweight", C.c_double * NBEST_GRID_MAX), ("wip", C.c_double * NBEST_GRID_MAX),
+                ("pscale", C.c_double * NBEST_GRID_MAX)]
 
 
 class GemmPlan(C.Structure):
@@ -155,6 +164,9 @@ SIGNATURES = {
     "blm_dyneval_accum": (_i, [_vp, _vp, _i64, _vp]),
     "blm_dyneval_rms": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "blm_dyneval_update": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _i, _vp]),
+    "blm_edit_distance": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "blm_nbest_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(NbestGrid), _vp, _vp]),
+    "blm_nbest_mbr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, C.POINTER(NbestGrid), _vp, _vp, _vp]),
     "blm_topk_rows": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "blm_beam_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "blm_beam_select_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _i, C.POINTER(BeamPoolArgs),

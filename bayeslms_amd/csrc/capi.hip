@@ -48,6 +48,7 @@ OptEntry g_opts[blm::OPT_COUNT] = {
     // vocabulary row in position order: two runs from one seed give bit-identical parameters (tests/test_gpu_deterministic.py)
     {"deterministic", "BLM_DETERMINISTIC", 0, 0, 1, 0, false},
     {"lstm_mb2", "BLM_LSTM_MB2", 1, 0, 1, 1, false},     // 1: the search cell's forward step takes two batch tiles per workgroup at B > 32 (W streamed once, one round)
+    {"edit_lane_max", "BLM_EDIT_LANE_MAX", 32, 0, 32, 32, false},  // blm_edit_distance: pairs whose shorter sequence has at most this many words take the lane-per-pair form
 };
 std::mutex g_opt_mu;
 void opt_init(OptEntry& e) {

@@ -425,7 +425,7 @@ def set_gemm_mode(mode):
 
 def set_option(name, value):
     """Kernel-selection options of the library (include/bayeslm.h blm_set_option): "attn_hpw", "attn_short", "attn_valu",
-    "lstm_gemv", "lstm_pipe", "lstm_tail", "deterministic" (see set_deterministic).  Each of the others picks between two BUILT and parity-tested forms of a kernel; the defaults are
+    "lstm_gemv", "lstm_pipe", "lstm_tail", "lstm_mb2", "edit_lane_max", "deterministic" (see set_deterministic).  Each of the others picks between two BUILT and parity-tested forms of a kernel; the defaults are
     the measured winners (INTEGRATION.md lists them with their tests and BLM_* environment variables)."""
     calls().blm_set_option(name.encode(), int(value))
 
@@ -4135,3 +4135,160 @@ class _LSTMSearchLayer(torch.autograd.Function):
 
 def lstm_search_layer(x, h0, c0, w8_ih, w8_hh, bias8, probs):
     return _LSTMSearchLayer.apply(x, h0, c0, w8_ih, w8_hh, bias8, probs)
+
+
+# ----------------------------------------------------------------------------
+# word error rate of n-best lists: alignment in bulk, selection over a weight grid, minimum Bayes risk (csrc/nbest.hip)
+# ----------------------------------------------------------------------------
+def _i32(t, name):
+    return dev_tensor(t, name, torch.int32)
+
+
+def _i64(t, name):
+    return dev_tensor(t, name, torch.int64)
+
+
+def _f64_or_none(t, name, H=None):
+    if t is None:
+        return None
+    t = dev_tensor(t, name, torch.float64).reshape(-1)
+    if H is not None and t.numel() != H:
+        raise BayesLMError("%s holds %d values for %d hypotheses" % (name, t.numel(), H))
+    return t
+
+
+def nbest_grids(points, what="nbest_select"):
+    """The blm_nbest_grid structs of a list of grid points (L, w, p) or (L, w, p, s) (s = 1 where it is left out), 64 points
+    to a struct: L finite and > 0, s finite and >= 0 (include/bayeslm.h).  -> [(first point, struct), ...]"""
+    pts = []
+    for k, pt in enumerate(points):
+        try:
+            pt = tuple(float(v) for v in pt)
+        except (TypeError, ValueError):
+            pt = ()
+        if len(pt) == 3:
+            pt = pt + (1.0,)
+        if len(pt) != 4:
+            raise BayesLMError("%s: grid point %d must be (lmwt, nnweight, wip[, posterior scale]), got %r" % (what, k, points[k]))
+        if not (math.isfinite(pt[0]) and pt[0] > 0.0):
+            raise BayesLMError("%s: grid point %d: lmwt = %r is not a positive finite LM weight" % (what, k, pt[0]))
+        if not (math.isfinite(pt[3]) and pt[3] >= 0.0):
+            raise BayesLMError("%s: grid point %d: posterior scale = %r is not a finite number >= 0" % (what, k, pt[3]))
+        pts.append(pt)
+    if not pts:
+        raise BayesLMError("%s: an empty grid" % what)
+    out = []
+    for k0 in range(0, len(pts), L.NBEST_GRID_MAX):
+        chunk = pts[k0:k0 + L.NBEST_GRID_MAX]
+        s = L.NbestGrid()
+        s.abi_version, s.G = L.ABI_VERSION, len(chunk)
+        for k, (lw, w, p, ps) in enumerate(chunk):
+            s.lmwt[k], s.nnweight[k], s.wip[k], s.pscale[k] = lw, w, p, ps
+        out.append((k0, s))
+    return out
+
+
+def edit_distance(tok, off, a, b, breakdown=False):
+    """Word-level alignment of P pairs of sequences (blm_edit_distance): ``tok`` int32 word ids, flat; ``off`` (n_seq + 1,) int64
+    offsets; ``a`` / ``b`` (P,) int32 sequence indices, a the hypothesis and b the reference.  -> cost (P,) int32, the minimum
+    number of substitutions + insertions + deletions; with ``breakdown`` also sid (P, 3) int32 = sub / ins / del of the
+    minimum-cost alignment with the fewest insertions.  A bad pair (an index outside the sequences, a reversed offset range or one
+    that leaves tok, more than 1023 words) gets -1 everywhere.  Integer and exact."""
+    tok, off = _i32(tok, "tok").reshape(-1), _i64(off, "off").reshape(-1)
+    a, b = _i32(a, "a").reshape(-1), _i32(b, "b").reshape(-1)
+    if off.numel() < 1:
+        raise BayesLMError("edit_distance: off must hold n_seq + 1 offsets")
+    if a.numel() != b.numel():
+        raise BayesLMError("edit_distance: %d indices in a, %d in b" % (a.numel(), b.numel()))
+    P = a.numel()
+    cost = torch.empty(P, device=a.device, dtype=torch.int32)
+    sid = torch.empty(P, 3, device=a.device, dtype=torch.int32) if breakdown else None
+    if P:
+        L.require_gfx950()
+        calls().blm_edit_distance(ptr(tok) if tok.numel() else None, tok.numel(), ptr(off), off.numel() - 1, ptr(a), ptr(b), P,
+                                  ptr(cost), ptr(sid), stream())
+    return (cost, sid) if breakdown else cost
+
+
+def pairwise_edit_distance(tok, off, uoff):
+    """The distance blocks blm_nbest_mbr reads: group u owns sequences uoff[u] .. uoff[u + 1] of (tok, off), N of them; every
+    pair i < j of a group is aligned once (blm_edit_distance) and written to both halves of the group's dense N x N block.
+    -> (dist (sum of N^2,) int32, doff (U,) int64 block offsets).  Index building and the fill are plain torch."""
+    tok, off, uoff = _i32(tok, "tok").reshape(-1), _i64(off, "off").reshape(-1), _i64(uoff, "uoff").reshape(-1)
+    if uoff.numel() < 1:
+        raise BayesLMError("pairwise_edit_distance: uoff must hold U + 1 offsets")
+    dev = uoff.device
+    n = (uoff[1:] - uoff[:-1]).clamp_(min=0)
+    sq = n * n
+    ends = torch.cumsum(sq, 0)
+    doff = ends - sq
+    total = int(ends[-1]) if ends.numel() else 0
+    dist = torch.zeros(total, device=dev, dtype=torch.int32)
+    if total == 0:
+        return dist, doff
+    if total > 2 ** 30:
+        raise BayesLMError("pairwise_edit_distance: %d block elements in one call, at most 2^30 (batch the utterances)" % total)
+    grp = torch.repeat_interleave(torch.arange(n.numel(), device=dev), sq)
+    local = torch.arange(total, device=dev) - doff[grp]
+    ng = n[grp]
+    i, j = torch.div(local, ng, rounding_mode="floor"), local % ng
+    upper = i < j
+    grp, i, j, ng = grp[upper], i[upper], j[upper], ng[upper]
+    base = uoff[grp]
+    cost = edit_distance(tok, off, (base + i).to(torch.int32), (base + j).to(torch.int32))
+    dist[doff[grp] + i * ng + j] = cost
+    dist[doff[grp] + j * ng + i] = cost
+    return dist, doff
+
+
+def _nbest_costs(what, ac, g, lm, nn, length, uoff):
+    uoff = _i64(uoff, "uoff").reshape(-1)
+    if uoff.numel() < 1:
+        raise BayesLMError("%s: uoff must hold U + 1 offsets" % what)
+    given = [t for t in (ac, g, lm, nn, length) if t is not None]
+    H = given[0].numel() if given else None
+    arrs = [_f64_or_none(t, n, H) for t, n in ((ac, "ac"), (g, "g"), (lm, "lm"), (nn, "nn"), (length, "length"))]
+    return arrs, uoff, H
+
+
+def nbest_select(ac, g, lm, nn, length, uoff, grid):
+    """The best hypothesis of every group at every grid point (blm_nbest_select).  ac / g / lm / nn / length: (H,) float64
+    COSTS per hypothesis, each may be None (zeros); group u owns uoff[u] .. uoff[u + 1]; ``grid``: points (L, w, p[, s]).
+    T = ac + L (g + w nn + (1 - w) lm + p length); -> pick (G, U) int32, per point and group the index WITHIN the group of the
+    least T, lowest index on ties (a non-finite T never wins; none finite: 0; an empty group: -1).  A grid of more than 64
+    points takes one launch per 64."""
+    arrs, uoff, _ = _nbest_costs("nbest_select", ac, g, lm, nn, length, uoff)
+    chunks = nbest_grids(grid, "nbest_select")
+    U = uoff.numel() - 1
+    G = chunks[-1][0] + chunks[-1][1].G
+    pick = torch.empty(G, U, device=uoff.device, dtype=torch.int32)
+    if U:
+        L.require_gfx950()
+        for k0, s in chunks:
+            calls().blm_nbest_select(*[ptr(t) for t in arrs], ptr(uoff), U, C.byref(s), ptr(pick[k0:k0 + s.G]), stream())
+    return pick
+
+
+def nbest_mbr(ac, g, lm, nn, length, uoff, dist, doff, grid, want_risk=True):
+    """Minimum-Bayes-risk selection (blm_nbest_mbr): with T as in nbest_select, P_i = exp(-s (T_i - min T) / L) / sum over the
+    group and R_i = sum_j P_j d(i, j) over the group's symmetric distance block (pairwise_edit_distance's ``dist`` / ``doff``).
+    At least one cost array must be given (it fixes H).  -> (risk (G, H) float64 or None, pick (G, U) int32: the argmin of R,
+    lowest index on ties, -1 for an empty group).  A grid of more than 64 points takes one launch per 64."""
+    arrs, uoff, H = _nbest_costs("nbest_mbr", ac, g, lm, nn, length, uoff)
+    if H is None:
+        raise BayesLMError("nbest_mbr: at least one of ac, g, lm, nn, length must be given")
+    dist, doff = _i32(dist, "dist").reshape(-1), _i64(doff, "doff").reshape(-1)
+    U = uoff.numel() - 1
+    if doff.numel() != U:
+        raise BayesLMError("nbest_mbr: %d block offsets for %d groups" % (doff.numel(), U))
+    chunks = nbest_grids(grid, "nbest_mbr")
+    G = chunks[-1][0] + chunks[-1][1].G
+    pick = torch.empty(G, U, device=uoff.device, dtype=torch.int32)
+    risk = torch.zeros(G, H, device=uoff.device, dtype=torch.float64) if want_risk else None
+    if U:
+        L.require_gfx950()
+        for k0, s in chunks:
+            # every group empty: no block is read, and an empty tensor has no address to pass for the required pointer
+            calls().blm_nbest_mbr(*[ptr(t) for t in arrs], ptr(uoff), U, H, ptr(dist) if dist.numel() else ptr(doff), ptr(doff),
+                                  C.byref(s), ptr(risk[k0:k0 + s.G]) if want_risk else None, ptr(pick[k0:k0 + s.G]), stream())
+    return risk, pick

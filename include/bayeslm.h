@@ -338,6 +338,8 @@ int blm_linear_nll2_edges(const float* x1, int64_t ldx1, const float* w1, int64_
  *   "lstm_tail"  (BLM_LSTM_TAIL,  0) 1: the general (K tail) form of the pipelined LSTM step kernels also for whole chunks
  *   "lstm_mb2"   (BLM_LSTM_MB2,   1) the architecture-search cell's forward step (blm_lstm_search_step_fwd) takes two batch tiles per
  *                                    workgroup at B > 32: the stacked 8H x H weight streams once, one round of workgroups (0: one tile)
+ *   "edit_lane_max" (BLM_EDIT_LANE_MAX, 32) blm_edit_distance: pairs whose shorter sequence has at most this many words (0..32) take
+ *                                    the lane-per-pair form, the others the wavefront form (0: every pair with two non-empty sides)
  * and one MODE, off by default:
  *   "deterministic" (BLM_DETERMINISTIC, 0) 1: every reduction of the library in a fixed order -- blm_gemm / blm_linear_nll* plans are
  *                                    legalised to ONE K slice (no float atomics into C; colsum_a then has one writer per element),
@@ -648,6 +650,71 @@ int blm_dyneval_rms(const float* ms, int64_t n, int count, float* rms, float* me
  * also writes g = 0 in the same pass.  p, g, p0 and rms must not overlap one another. */
 int blm_dyneval_update(float* p, float* g, const float* p0, const float* rms, const float* mean, int64_t n, float lr, float decay,
                        float eps, int zero_grad, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Word error rate of rescored n-best lists (csrc/nbest.hip; bayeslms_amd/nbest_wer.py): word-level alignment in bulk, selection
+ * over a grid of score weights, minimum-Bayes-risk selection (Stolcke, Koenig, Weintraub 1997).
+ *
+ * Sequences are int32 word ids in one flat buffer tok (n_tok words); off holds n_seq + 1 int64 offsets, sequence q is
+ * tok[off[q] .. off[q + 1]).  The ids are the caller's, assigned from the SURFACE words of hypotheses and references together
+ * (not an LM vocabulary: an out-of-vocabulary word must not collapse to <unk>); they are only compared for equality, any
+ * int32 is an id.
+ *
+ * Alignment of a pair (a = hypothesis, b = reference): matches at cost 0; substitutions, insertions (a word of a left
+ * unmatched) and deletions (a word of b left unmatched) at cost 1 each.  cost is the minimum total; among the minimum-cost
+ * alignments the one with the FEWEST INSERTIONS is reported.  ins - del = len(a) - len(b) holds for every alignment, so that
+ * one also has the fewest deletions and the most substitutions, and one integer fixes the breakdown; the rule is symmetric:
+ * (b, a) gives the same cost and sub with ins and del exchanged.  Integer arithmetic, exact.
+ * Lengths run from 0 to BLM_EDIT_MAX_LEN.  A BAD pair gets -1 in every output and reads nothing out of range: a sequence
+ * index outside [0, n_seq), an offset range that is reversed or leaves [0, n_tok], a length over the limit.  (off, a and b
+ * live on the device: this is the kernel's check, not the host's.)
+ * cost: (P) int32; sid: (P, 3) int32 sub / ins / del, may be NULL.  Two kernel forms share a call, each taking its own pairs:
+ * a lane per pair where the shorter sequence has at most "edit_lane_max" words (option, 0..32, default 32), a wave per pair
+ * on a blocked anti-diagonal otherwise; both give the same integers.  No atomics, no workspace.
+ * BLM_ERR_INVALID, before any launch: NULL off, a, b or cost, NULL tok with n_tok > 0, a negative count, extents too large
+ * (n_tok, n_seq, P at most 2^30).  P == 0: BLM_OK, nothing launched.
+ * -------------------------------------------------------------------------- */
+#define BLM_EDIT_MAX_LEN 1023
+int blm_edit_distance(const int32_t* tok, int64_t n_tok, const int64_t* off, int n_seq, const int32_t* a, const int32_t* b, int P,
+                      int32_t* cost, int32_t* sid, void* stream);
+/* Selection.  Utterance u owns hypotheses uoff[u] .. uoff[u + 1] (U + 1 int64 offsets on the device; a reversed range is an
+ * empty group).  Each hypothesis has, in float64 and all as COSTS (lower is better): the acoustic cost ac, the graph cost g
+ * (lmwt.nolm), the old LM's cost lm (lmwt.lmonly), the neural cost nn (what the scorer writes) and the word count len.  Each of
+ * the five arrays may be NULL and then counts as zeros.  A grid point is (L, w, p, s): the LM weight L, finite and > 0; the
+ * nnweight w; the word insertion penalty p; the posterior scale s, finite and >= 0 (blm_nbest_mbr alone reads it).
+ *   T = ac + L * (((g + w * nn) + (1 - w) * lm) + p * len)
+ * evaluated in float64 exactly as written, without contraction: stage 7's sum, ranked as Kaldi ranks it at
+ * --inv-acoustic-scale=L, multiplied through by L so that no division enters.
+ * pick (G, U) int32, grid point k's choice for utterance u at [k * U + u], an index WITHIN the group: the argmin of T with the
+ * lowest index on ties; a non-finite T never wins; if every T is non-finite the pick is 0; an empty group gives -1.
+ * The grid travels in this host struct, read and validated before the launch and handed to the kernel by value. */
+#define BLM_NBEST_GRID_MAX 64
+typedef struct blm_nbest_grid {
+  uint32_t abi_version; /* BLM_ABI_VERSION */
+  int32_t G;            /* 1 .. BLM_NBEST_GRID_MAX points; the entries from G on are not read */
+  double lmwt[BLM_NBEST_GRID_MAX];     /* L: finite, > 0 */
+  double nnweight[BLM_NBEST_GRID_MAX]; /* w */
+  double wip[BLM_NBEST_GRID_MAX];      /* p */
+  double pscale[BLM_NBEST_GRID_MAX];   /* s: finite, >= 0 */
+} blm_nbest_grid;
+/* One workgroup per utterance, lanes over hypotheses, grid points in a loop; (T, index) reduced in a fixed order.
+ * BLM_ERR_INVALID, before any launch: NULL uoff, grid or pick, U < 0, G outside 1..BLM_NBEST_GRID_MAX, an L that is not finite
+ * or not > 0, an s that is negative or not finite, extents too large; BLM_ERR_ABI: abi_version.  U == 0: BLM_OK. */
+int blm_nbest_select(const double* ac, const double* g, const double* lm, const double* nn, const double* len, const int64_t* uoff,
+                     int U, const blm_nbest_grid* grid, int32_t* pick, void* stream);
+/* Minimum Bayes risk.  With T as above over the group's N hypotheses, H hypotheses in all (uoff must stay inside [0, H]: a range
+ * that does not is an empty group):
+ *   P_i = exp(-(s * (T_i - min T) / L)) / sum_j of the same;   R_i = sum_j P_j d(i, j), j ascending, in float64
+ * and the pick is the argmin of R with the lowest index on ties (-1 for an empty group).  A non-finite T has P = 0; if no T is
+ * finite the posterior is uniform.  d is the utterance's dense N x N int32 distance block at dist + doff[u] (doff: U int64 on
+ * the device), SYMMETRIC as a distance is: the kernel reads element (j, i) for d(i, j), the order in which neighbouring lanes
+ * read neighbouring words.  One workgroup per (utterance, grid point); P is formed in LDS (once when N <= 2048, else chunk by
+ * chunk); each lane sums its own rows; no atomics: the same bits in every run.
+ * risk: (G, H) float64, R of hypothesis h at grid point k at [k * H + h], may be NULL.  pick as blm_nbest_select's.
+ * BLM_ERR_INVALID: as blm_nbest_select, and NULL dist or doff, H < 0. */
+int blm_nbest_mbr(const double* ac, const double* g, const double* lm, const double* nn, const double* len, const int64_t* uoff,
+                  int U, int64_t H, const int32_t* dist, const int64_t* doff, const blm_nbest_grid* grid, double* risk, int32_t* pick,
+                  void* stream);
 
 /* --------------------------------------------------------------------------
  * Search on the incremental path (csrc/beam.hip): the k best next words, beam selection, top-k / nucleus sampling.
