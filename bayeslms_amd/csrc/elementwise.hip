@@ -1055,16 +1055,22 @@ extern "C" int blm_gp_coef_grad(const float* g, const float* z, float* dcoef, in
 int blm::colsum_scaled(const float* x, int64_t ld, float* out, float* out2, int M, int N, int accumulate, float scale, void* stream) {
   if (!x || !out || !blm::extents_ok({M, N}) || ld < N || !blm::extents_ok({M, ld}) || out == out2) return blm_fail(BLM_ERR_INVALID, "blm_colsum: bad arguments");
   if (N == 0) return BLM_OK;
+  // accumulate == 0: out2 is a COPY of out.  The row chunks reach a vector through float atomics in whatever order they land, so
+  // from three chunks on, two vectors filled by atomics differ in their last bits -- and the two bias gradients of an LSTM layer
+  // are one sum.  (accumulate != 0: each vector has a previous value of its own and takes the atomics.)
+  const bool copy2 = out2 && !accumulate;
   if (!accumulate) {
     BLM_HIP(hipMemsetAsync(out, 0, (size_t)N * sizeof(float), ST));
-    if (out2) BLM_HIP(hipMemsetAsync(out2, 0, (size_t)N * sizeof(float), ST));
+    if (out2 && M == 0) BLM_HIP(hipMemsetAsync(out2, 0, (size_t)N * sizeof(float), ST));
   }
   if (M == 0) return BLM_OK;
   int gy = (M + 255) / 256;
   if (gy > 64) gy = 64;
   if (blm::option(blm::OPT_DETERMINISTIC)) gy = 1;  // one row chunk: each sum has one writer, rows added in a fixed order
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 127) / 128, gy), dim3(TPB), 0, ST, x, (long)ld, out, M, N, out2, scale);
+  hipLaunchKernelGGL(colsum_kernel, dim3((N + 127) / 128, gy), dim3(TPB), 0, ST, x, (long)ld, out, M, N, copy2 ? nullptr : out2,
+                     scale);
   BLM_HIP(hipGetLastError());
+  if (copy2) BLM_HIP(hipMemcpyAsync(out2, out, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, ST));
   return BLM_OK;
 }
 

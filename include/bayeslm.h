@@ -957,8 +957,10 @@ int blm_colsum(const float* x, int64_t ld, float* out, int M, int N, int accumul
 /* ... and the same sums into a second vector out2 (NULL: none) from the same pass: nn.LSTM's b_ih and b_hh receive the same
  * gradient (model.py:35 / _VF.lstm :812).  For callers that bind the ABI directly: the Python host of this repository takes the
  * bias gradients out of the weight-gradient GEMM (blm_gemm_args.colsum_a) and adds them to both leaves with blm_init_multi, so
- * nothing under bayeslms_amd/ calls this entry point (it is covered at kernel level, tests/test_gpu_kernels.py).  In
- * deterministic mode (blm_set_option("deterministic", 1)) both column-sum entry points use one row chunk: one writer per sum. */
+ * nothing under bayeslms_amd/ calls this entry point (it is covered at kernel level, tests/test_gpu_kernels.py and
+ * tests/test_gpu_update_kernels.py).  With accumulate == 0 out2 is a copy of out, bit for bit; with accumulate != 0 each vector
+ * takes the row chunks' float atomics in an order of its own.  In deterministic mode (blm_set_option("deterministic", 1)) both
+ * column-sum entry points use one row chunk: one writer per sum, and two vectors that start equal stay equal. */
 int blm_colsum2(const float* x, int64_t ld, float* out, float* out2, int M, int N, int accumulate, void* stream);
 /* Up to 8 small vectors set by ONE launch: dst[i][0..n[i]) = (src[i] ? src[i][j] : 0) + (src2[i] ? src2[i][j] : 0); src / src2
  * may be NULL altogether.  dst, src, src2, n are HOST arrays (copied into the launch).  The set-up of a recurrent layer -- initial
