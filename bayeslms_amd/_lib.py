@@ -20,6 +20,9 @@ CACHE_THETAS_MAX = 8  # BLM_CACHE_THETAS_MAX
 DYNEVAL_RMS_WS_FLOATS = 4096  # BLM_DYNEVAL_RMS_WS_FLOATS
 EDIT_MAX_LEN = 1023  # BLM_EDIT_MAX_LEN
 NBEST_GRID_MAX = 64  # BLM_NBEST_GRID_MAX
+SWAG_RANK_MAX = 32  # BLM_SWAG_RANK_MAX
+SWAG_DRAWS_MAX = 8  # BLM_SWAG_DRAWS_MAX
+SWAG_SAMPLES_MAX = 64  # BLM_SWAG_SAMPLES_MAX
 OK = 0
 ERR_INVALID, ERR_ABI, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4  # blm_status (include/bayeslm.h)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -28,6 +31,7 @@ GEMM_ACCUMULATE = 1
 STREAM_WEIGHT = 0x10000000   # stream class in the top 4 bits, tensor / site id in the low 28: the classes cannot alias
 STREAM_DROPOUT = 0x20000000
 STREAM_LRT = 0x30000000      # pre-activation noise of local reparameterisation (ops.bayes_linear_lrt), + site id
+STREAM_SWAG = 0x40000000     # a SWAG sample's noise: + 0 diagonal, + 1 low rank; the step is the sample id
 
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
@@ -92,6 +96,12 @@ class NbestGrid(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("G", C.c_int32), ("lmwt", C.c_double * NBEST_GRID_MAX),
                 ("nnweight", C.c_double * NBEST_GRID_MAX), ("wip", C.c_double * NBEST_GRID_MAX),
                 ("pscale", C.c_double * NBEST_GRID_MAX)]
+
+
+class SwagDraw(C.Structure):
+    """blm_swag_draw (include/bayeslm.h)."""
+    _fields_ = [("abi_version", C.c_uint32), ("count", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("inv_n", C.c_float),
+                ("var_floor", C.c_float), ("sample_id", C.c_uint32 * SWAG_DRAWS_MAX), ("rng", Rng)]
 
 
 class GemmPlan(C.Structure):
@@ -164,6 +174,9 @@ SIGNATURES = {
     "blm_dyneval_accum": (_i, [_vp, _vp, _i64, _vp]),
     "blm_dyneval_rms": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "blm_dyneval_update": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _i, _vp]),
+    "blm_swag_collect": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "blm_swag_sample": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _i64, C.POINTER(SwagDraw), _vp]),
+    "blm_logp_avg_accum": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "blm_edit_distance": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "blm_nbest_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(NbestGrid), _vp, _vp]),
     "blm_nbest_mbr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, C.POINTER(NbestGrid), _vp, _vp, _vp]),

@@ -770,6 +770,7 @@ class EvalReport:
     mean_h_pred: Optional[float] = None    # mean predictive entropy H[pbar]
     mean_mi: Optional[float] = None        # mean mutual information between the word and the weights
     per_token: Optional[dict] = None       # keep_tokens: float / int arrays in text order, skipped tokens included (NaN / -1)
+    swag: Optional[dict] = None            # SWAG (SwagPosterior.describe with scale, diag, samples, seed, path); None: the model's own weights
     cache: Optional[dict] = None           # neural cache (CacheReport.as_dict, with the fit's block after fit_cache); None: no cache
     dyneval: Optional[dict] = None         # dynamic evaluation (DynEvalReport.as_dict beside the static loss, with the fit's block); None: none
     temperature: Optional[dict] = None     # temperature scaling (temperature_block); None: the distribution as the model gives it
@@ -777,7 +778,7 @@ class EvalReport:
     def as_dict(self):
         d = dataclasses.asdict(self)
         del d["per_token"]
-        for k in ("temperature", "cache", "dyneval"):  # a run without one writes what it wrote before there was one
+        for k in ("temperature", "cache", "dyneval", "swag"):  # a run without one writes what it wrote before there was one
             if d[k] is None:
                 del d[k]
         return d
@@ -1543,10 +1544,20 @@ def _dyneval_session(who, model):
     if name not in _DYNEVAL_FAMILIES:
         raise ops.BayesLMError("%s: %s: the eval-mode forward of this family is not known to back-propagate through the engine's "
                                "ops (supported: %s)" % (who, name, ", ".join(_DYNEVAL_FAMILIES)))
+    with _rehomed(who, model, "dynamic evaluation runs at mean weights") as flat:
+        yield flat, flat.flat_param.clone()
+
+
+@contextlib.contextmanager
+def _rehomed(who, model, what):
+    """The model re-homed into a FlatBuffers (no momentum buffer) for one walk that overwrites its weights in place -> flat.  On
+    the way out, return or exception alike, every parameter gets back its ORIGINAL storage (never written: the trained values bit
+    for bit) and its .grad, every module its training flag, and ops its gradient hook and embedding sink."""
+    name = type(model).__name__
     state = getattr(model, "noise_state", None)
     if state is not None and state.source == "torch":
-        raise ops.BayesLMError("%s: noise source 'torch' is a parity mode of training runs; dynamic evaluation runs at mean weights "
-                               "with the engine's own kernels (set_noise_source('philox'))" % who)
+        raise ops.BayesLMError("%s: noise source 'torch' is a parity mode of training runs; %s "
+                               "with the engine's own kernels (set_noise_source('philox'))" % (who, what))
     params = [p for p in model.parameters() if p.requires_grad]
     if not params:
         raise ops.BayesLMError("%s: %s has no trainable parameter" % (who, name))
@@ -1558,8 +1569,8 @@ def _dyneval_session(who, model):
         ops.set_embed_grad_sink(None)
         model.eval()
         flat = FlatBuffers(model)
-        flat.flat_mom = None  # no momentum in this rule
-        yield flat, flat.flat_param.clone()
+        flat.flat_mom = None  # no momentum in these walks
+        yield flat
     finally:
         for p, data, grad in saved:
             p.data = data
@@ -1711,3 +1722,98 @@ def fit_dyneval(model, source, seq_len, lrs, decays, stats=None, eps=0.01, max_w
         curve = [[a, b, _dyneval_run(who, model, flat, theta0, source, wins, a, b, stats, eps, False, None).loss] for a, b in cands]
     best = min(curve, key=lambda c: c[2])
     return DynEvalFit(lr=best[0], decay=best[1], loss=best[2], loss_static=curve[0][2], curve=curve)
+
+
+# ----------------------------------------------------------------------------
+# SWAG: the model average over samples of a Gaussian fitted to the SGD iterates (bayeslms_amd/swag.py)
+# ----------------------------------------------------------------------------
+def evaluate_swag(model, source, seq_len, posterior, samples, seed=1111, scale=0.5, diag=False, bins=15, temperature=1.0,
+                  keep_tokens=False):
+    """evaluate_report's figures under the average of S = ``samples`` weight samples of the SWAG ``posterior``
+    (swag.SwagPosterior) -> EvalReport with the Monte-Carlo block (mc_samples = S, sample_loss, mean_h_pred, mean_mi) and a
+    ``per_token["nll_s"]`` of (tokens, S) under ``keep_tokens``.  Any model family, variational or not: every sample is a full
+    set of weights, decoder included, which is what blm_linear_mc_logprobs (one decoder for all samples) cannot serve.
+
+    The model is re-homed into a FlatBuffers for the walk (every parameter gets back its original storage, .grad and training
+    flag, by return or by exception) and the S samples are drawn once (SwagPosterior.draw: sample s is a function of
+    (posterior, seed, s, scale, diag) alone; S x P floats, refused beyond its byte budget).  The walk is evaluate_report's
+    (_report_windows), one window at a time: for every s the flat buffer is overwritten with sample s, the eval-mode forward
+    runs (a recurrent model carries S hidden sets), the decoder's logits are formed in chunks of _REPORT_ROWS rows and
+    blm_logp_avg_accum folds them into the window's (rows, V) running log-average, with each sample's NLL and entropy; after the
+    last sample blm_row_stats (blm_row_stats_temps with one beta under a ``temperature`` other than 1: pbar^(1/T) / Z, as
+    under mc_samples) reduces log pbar.  mi = H[pbar] - mean_s H[p_s], both untempered.
+
+    Refused: samples outside 2..64, a world size above 1, noise source 'torch', a posterior made for another model."""
+    from .model import inference_decoder, repackage_hidden
+    who = "evaluate_swag"
+    S = int(samples)
+    if not 2 <= S <= 64:
+        raise ops.BayesLMError("%s: samples must lie in 2..64, got %d (the SWA mean alone is evaluate_report of "
+                               "SwagPosterior.mean_state_dict)" % (who, S))
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        raise ops.BayesLMError("%s runs in a single process (world size %d)" % (who, dist.get_world_size()))
+    betas = None
+    if _float32_beta(who, temperature, "temperature") and float(temperature) != 1.0:
+        betas = [_float32_beta(who, 1.0 / float(temperature), "1 / temperature")]
+    dec = inference_decoder(model)
+    if dec is None:
+        raise ops.BayesLMError("%s: %s has no decoder that hands back its input rows" % (who, type(model).__name__))
+    posterior.check(model)
+    recurrent = hasattr(model, "init_hidden")
+    V, cols = dec.weight.shape[0], source.shape[1]
+    keep = {k: [] for k in ("tgt", "pos", "nll", "conf", "entropy", "pred", "rank", "nll_s", "h_pred", "mi")}
+    with _rehomed(who, model, "a SWAG sample replaces every weight and runs") as flat:
+        posterior.check(flat)
+        draws = posterior.draw(S, seed, scale, diag)
+        dev = flat.flat_param.device
+        with torch.no_grad(), dec.inference(input_rows=True):
+            hidden = [model.init_hidden(cols) for _ in range(S)] if recurrent else None
+            for data, targets, pos in _report_windows(source, seq_len, recurrent):
+                R = targets.numel()
+                chunks = [(a, min(R, a + _REPORT_ROWS)) for a in range(0, R, _REPORT_ROWS)]
+                acc = torch.empty(R, V, device=dev, dtype=torch.float32)
+                hsum = torch.empty(R, device=dev, dtype=torch.float32)
+                nll_s = [torch.empty(S, b - a, device=dev, dtype=torch.float32) for a, b in chunks]
+                for s in range(S):
+                    flat.flat_param.copy_(draws[s])
+                    if recurrent:
+                        x, h = model(data, hidden[s])
+                        hidden[s] = repackage_hidden(h)
+                    else:
+                        x = model(data)
+                    x = x.reshape(-1, x.shape[-1])
+                    for c, (a, b) in enumerate(chunks):
+                        ops.logp_avg_accum(ops.linear(x[a:b], dec.weight, dec.bias), acc[a:b], s, S, targets[a:b], hsum[a:b], nll_s[c])
+                for a, b in chunks:
+                    st = ops.row_stats(acc[a:b], targets[a:b], V)
+                    h_pred = st.entropy
+                    if betas is not None:
+                        tt = ops.row_stats_temps(acc[a:b], betas, targets[a:b], V)
+                        st = ops.RowStats(tt.nll[0], tt.conf[0], tt.entropy[0], tt.pred, tt.rank)
+                    for k, v in (("nll", st.nll), ("conf", st.conf), ("entropy", st.entropy), ("pred", st.pred), ("rank", st.rank),
+                                 ("h_pred", h_pred), ("mi", h_pred - hsum[a:b] / S)):
+                        keep[k].append(v)
+                keep["nll_s"].append(torch.cat(nll_s, 1).t())
+                keep["tgt"].append(targets)
+                keep["pos"].append(pos)
+    if keep["tgt"]:
+        fl = ("nll", "conf", "entropy", "h_pred", "mi")
+        packed = torch.stack([torch.cat(keep[k]) for k in fl]).cpu().numpy()
+        host = {k: packed[j] for j, k in enumerate(fl)}
+        host["tgt"] = torch.cat(keep["tgt"]).cpu().numpy()
+        host["pred"], host["rank"] = torch.stack([torch.cat(keep["pred"]), torch.cat(keep["rank"])]).cpu().numpy()
+        host["nll_s"] = torch.cat(keep["nll_s"]).cpu().numpy()
+    else:
+        z = np.zeros(0, np.float32)
+        host = {"nll": z, "conf": z, "entropy": z, "h_pred": z, "mi": z, "tgt": np.zeros(0, np.int64), "pred": np.zeros(0, np.int32),
+                "rank": np.zeros(0, np.int32), "nll_s": np.zeros((0, S), np.float32)}
+    valid = (host["tgt"] >= 0) & (host["tgt"] < V)
+    rep = report_from_tokens(host["nll"], host["conf"], host["entropy"], host["rank"], valid, bins, host["nll_s"], host["h_pred"],
+                             host["mi"])
+    rep.mc_samples = S
+    if betas is not None:
+        rep.temperature = temperature_block(betas[0])
+    if keep_tokens:
+        order = np.argsort(np.concatenate(keep["pos"])) if len(host["tgt"]) else np.zeros(0, np.int64)
+        rep.per_token = {k: v[order] for k, v in host.items()}
+    return rep

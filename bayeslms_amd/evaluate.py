@@ -43,7 +43,15 @@ windows of that text (the training text).  The summary line gains ``| dyneval ru
 b`` and the report a ``dyneval`` block (DynEvalReport.as_dict, ``base_loss`` / ``base_ppl`` of the static report, and
 ``fitted_on``, ``fit_loss_before``, ``fit_loss_after`` and ``curve`` after a fit); every other figure, ``--write-tokens`` included,
 stays the static model's.  Refused with it: ``--mc-samples``, ``--temperature``, ``--fit-temperature-on``, ``--cache-window``.
-Without these flags the line and the report are what they were."""
+Without these flags the line and the report are what they were.
+
+SWAG.  ``--swag PATH --swag-samples S`` evaluates ``--data`` under the average of S (2..64) weight samples of the SWAG posterior
+that ``python -m bayeslms_amd.train --swag-save PATH`` wrote (engine.evaluate_swag; ``--swag-scale`` c, default 0.5,
+``--swag-diag 1`` for the diagonal form, ``--mc-seed`` keys the samples); any model family, ``--uncertainty none`` included.
+``--swag-samples 0`` evaluates the SWA mean through the ordinary mean-weight report.  ``--temperature`` is honoured.  The summary
+line gains ``| swag n ... rank ... scale ... samples ...`` and the report a ``swag`` block.  Refused beside ``--swag``:
+``--mc-samples``, ``--fit-temperature-on``, ``--cache-window`` and the dyneval flags.  Without ``--swag`` the line and the report
+are what they were."""
 import argparse
 import json
 import math
@@ -108,7 +116,40 @@ def build_parser():
     p.add_argument('--dyneval-lr-grid', type=str, default='', metavar='a,b,c')
     p.add_argument('--dyneval-decay-grid', type=str, default='', metavar='a,b,c')
     p.add_argument('--dyneval-fit-windows', type=int, default=None, metavar='N', help='windows of --fit-dyneval-on a candidate walks (default all)')
+    p.add_argument('--swag', type=str, default='', metavar='PATH',
+                   help='evaluate under the SWAG posterior that train --swag-save wrote (with --swag-samples)')
+    p.add_argument('--swag-samples', type=int, default=None, metavar='S',
+                   help='with --swag: 2..64 weight samples whose distributions are averaged; 0: the SWA mean alone')
+    p.add_argument('--swag-scale', type=float, default=None, metavar='C',
+                   help='with --swag: the scale of the sampled covariance (default 0.5, the value of Maddox et al. 2019; unmeasured here)')
+    p.add_argument('--swag-diag', type=int, default=None, choices=[0, 1], help='with --swag: 1 = the diagonal form, no low-rank term')
     return p
+
+
+def check_swag_args(args):
+    """The SWAG flags' refusals: before any file or device is touched."""
+    if not args.swag:
+        for flag, v in (("--swag-samples", args.swag_samples), ("--swag-scale", args.swag_scale), ("--swag-diag", args.swag_diag)):
+            if v is not None:
+                raise SystemExit("%s needs --swag" % flag)
+        return
+    if args.swag_samples is None:
+        raise SystemExit("--swag needs --swag-samples (2..64 samples, or 0 for the SWA mean)")
+    S = args.swag_samples
+    if S != 0 and not 2 <= S <= 64:
+        raise SystemExit("--swag-samples must be 0 (the SWA mean) or lie in 2..64 (got %d)" % S)
+    if S == 0 and (args.swag_scale is not None or args.swag_diag is not None):
+        raise SystemExit("--swag-scale and --swag-diag shape the samples: --swag-samples 0 draws none")
+    if args.swag_scale is not None and not (math.isfinite(args.swag_scale) and args.swag_scale >= 0):
+        raise SystemExit("--swag-scale must be finite and >= 0 (got %r)" % args.swag_scale)
+    if args.mc_samples:
+        raise SystemExit("--swag with --mc-samples: the SWAG samples are the Monte-Carlo samples of this run (--swag-samples)")
+    if args.fit_temperature_on:
+        raise SystemExit("--swag with --fit-temperature-on: fitting a temperature under SWAG is not built (--temperature T is honoured)")
+    if args.cache_window is not None:
+        raise SystemExit("--swag with --cache-window: the cache runs at the model's own mean weights")
+    if args.dyneval_lr is not None or args.dyneval_decay is not None or args.fit_dyneval_on:
+        raise SystemExit("--swag with dynamic evaluation: the two together are not built")
 
 
 def dyneval_grid(text, flag):
@@ -195,6 +236,7 @@ def check_args(args):
     """Refusals that need neither the input files, the model nor a device."""
     check_cache_args(args)
     check_dyneval_args(args)
+    check_swag_args(args)
     if args.temperature is not None and args.fit_temperature_on:
         raise SystemExit("--temperature and --fit-temperature-on exclude each other: give T or the text to fit it on")
     if args.temperature is not None and not (math.isfinite(args.temperature) and args.temperature > 0):
@@ -222,6 +264,9 @@ def summary_line(rep):
     if c:
         line += " | cache window %d theta %.6g lambda %.4f | loss %.4f -> %.4f | ppl %.2f -> %.2f | hit %.4f" % (
             c["window"], c["theta"], c["lam"], c["base_loss"], c["loss"], c["base_ppl"], c["ppl"], c["cache_hit_rate"])
+    w = rep.swag
+    if w:
+        line += " | swag n %d rank %d scale %.6g samples %d" % (w["n"], w["rank"], w["scale"], w["samples"])
     d = rep.dyneval
     if d:
         line += " | dyneval rule %s lr %.6g decay %.6g | loss %.4f -> %.4f | ppl %.2f -> %.2f" % (
@@ -278,6 +323,8 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
     model = model.to(device).eval()
     temperature, fit = (1.0 if args.temperature is None else args.temperature), None
+    if args.swag:
+        return swag_main(args, model, corpus, text, device, temperature)
     if args.fit_temperature_on:
         fit = engine.fit_temperature(model, D.batchify(fit_text, args.batch_size, device), args.seq_len, mc_samples=args.mc_samples,
                                      seed=args.mc_seed, bins=args.bins, passes=args.fit_passes)
@@ -317,6 +364,35 @@ def main(argv=None):
         dyn = engine.evaluate_dynamic(model, D.batchify(text, args.batch_size, device), args.seq_len, lr, decay, stats=stats,
                                       eps=args.dyneval_epsilon)
         rep.dyneval = dyneval_block(dyn, rep, dfit, args.fit_dyneval_on)
+    print(summary_line(rep), flush=True)
+    if args.write_report:
+        with open(args.write_report, 'w') as f:
+            json.dump(rep.as_dict(), f)
+    if args.write_tokens:
+        write_tokens(rep, corpus.dictionary.idx2word, args.write_tokens)
+    return rep
+
+
+def swag_main(args, model, corpus, text, device, temperature):
+    """--swag: the report under the posterior's samples, or, --swag-samples 0, the mean-weight report of the SWA weights"""
+    from . import swag
+    from ._lib import BayesLMError
+    try:
+        posterior = swag.SwagPosterior.load(args.swag, device)
+        posterior.check(model)
+    except BayesLMError as e:
+        raise SystemExit("--swag %s: %s" % (args.swag, e))
+    source = D.batchify(text, args.batch_size, device)
+    scale = 0.5 if args.swag_scale is None else args.swag_scale
+    if args.swag_samples == 0:
+        model.load_state_dict(posterior.mean_state_dict(model))
+        rep = engine.evaluate_report(model, source, args.seq_len, bins=args.bins, keep_tokens=bool(args.write_tokens), temperature=temperature)
+        scale = 0.0
+    else:
+        rep = engine.evaluate_swag(model, source, args.seq_len, posterior, args.swag_samples, seed=args.mc_seed, scale=scale,
+                                   diag=bool(args.swag_diag), bins=args.bins, temperature=temperature, keep_tokens=bool(args.write_tokens))
+    rep.swag = dict(posterior.describe(), scale=scale, diag=bool(args.swag_diag), samples=args.swag_samples, seed=args.mc_seed,
+                    path=args.swag)
     print(summary_line(rep), flush=True)
     if args.write_report:
         with open(args.write_report, 'w') as f:

@@ -2620,6 +2620,125 @@ def dyneval_update(p, g, p0, lr, decay, rms=None, mean=None, eps=0.01, zero_grad
     return p
 
 
+def _swag_rows(who, name, t, n):
+    """A (rows, >= n) float32 device matrix with unit inner stride, used in place (a row of it may start at any float) -> its
+    row stride as the kernel takes it"""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.stride(-1) != 1 or t.shape[1] != n:
+        raise BayesLMError("%s: %s must be a (rows, %d) matrix with unit inner stride" % (who, name, n))
+    dev_tensor(t[:1], "%s: %s" % (who, name))
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), n)
+    if ld < n:
+        raise BayesLMError("%s: the rows of %s overlap (row stride %d < %d)" % (who, name, ld, n))
+    return ld
+
+
+def swag_collect(theta, mean, m2, count, dev_row=None):
+    """One iterate into a SWAG posterior, in place over flat float32 arrays of one length (blm_swag_collect, one pass):
+    Welford's update of ``mean`` and ``m2`` by ``theta`` as iterate number ``count`` (0: mean = theta, m2 = 0, and neither is read)
+    and the deviation theta - mean' into ``dev_row`` (None: a diagonal posterior keeps none)."""
+    arrays = dict(theta=theta, mean=mean, m2=m2) if dev_row is None else dict(theta=theta, mean=mean, m2=m2, dev_row=dev_row)
+    n = _dyneval_flat("swag_collect", **arrays)
+    count = int(count)
+    if not 0 <= count < 1 << 24:
+        raise BayesLMError("swag_collect: count = %d outside 0..2^24-1" % count)
+    L.require_gfx950()
+    calls().blm_swag_collect(ptr(theta), ptr(mean), ptr(m2), ptr(dev_row), n, count, stream())
+
+
+def swag_draw(sample_ids, seed, a, b, inv_n, floor):
+    """The blm_swag_draw struct of 1..8 sample ids; a, b, inv_n and floor are rounded to float32 once, here."""
+    ids = [int(i) for i in sample_ids]
+    if not 1 <= len(ids) <= L.SWAG_DRAWS_MAX or any(not 0 <= i < 1 << 32 for i in ids):
+        raise BayesLMError("swag_sample: %d sample ids (%r): blm_swag_sample takes 1..%d per launch, each in 0..2^32-1"
+                           % (len(ids), ids[:9], L.SWAG_DRAWS_MAX))
+    d = L.SwagDraw()
+    d.abi_version, d.count = L.ABI_VERSION, len(ids)
+    for name, v, positive in (("a", a, False), ("b", b, False), ("inv_n", inv_n, True), ("var_floor", floor, False)):
+        v = float(v)
+        setattr(d, name, v if math.isfinite(v) else 0.0)  # ctypes rounds to float32
+        got = getattr(d, name)
+        if not (math.isfinite(v) and v >= 0.0 and got < math.inf and (got > 0.0 or not positive)):
+            raise BayesLMError("swag_sample: %s = %r is not a finite float32 number %s 0" % (name, v, ">" if positive else ">="))
+    for j, i in enumerate(ids):
+        d.sample_id[j] = i
+    d.rng = L.rng(seed, L.STREAM_SWAG, 0)
+    return d
+
+
+def swag_z2(sample_ids, seed, k_live, device):
+    """(len(sample_ids), k_live) device array: row j the first k_live normals of the Philox stream (seed, STREAM_SWAG + 1,
+    step = sample_ids[j]), as blm_philox_normal writes them."""
+    z2 = torch.empty(len(sample_ids), k_live, device=device, dtype=torch.float32)
+    for j, i in enumerate(sample_ids):
+        r = L.rng(seed, L.STREAM_SWAG + 1, int(i))
+        calls().blm_philox_normal(ptr(z2[j]), k_live, C.byref(r), stream())
+    return z2
+
+
+def swag_sample(out, mean, m2, sample_ids, seed, a, b, inv_n, floor, dev=None, k_live=0, z2=None):
+    """Weight samples of a SWAG posterior into the rows of ``out`` (len(sample_ids) <= 8, P), all from one read of ``mean``,
+    ``m2`` (P,) and the first ``k_live`` rows of ``dev`` (K, P) (blm_swag_sample):
+    out[j] = mean + a sqrt(max(m2 inv_n, floor)) z1_j + b sum_k dev[k] z2[j, k], z1_j the Philox normals of (seed, STREAM_SWAG,
+    step = sample_ids[j]).  ``z2`` (len(sample_ids), k_live): default swag_z2's.  Row j is a function of its own id alone: the
+    same bits alone, in a longer list and at another slot.  -> out"""
+    n = _dyneval_flat("swag_sample", mean=mean, m2=m2)
+    ids = [int(i) for i in sample_ids]
+    draw = swag_draw(ids, seed, a, b, inv_n, floor)
+    ld_out = _swag_rows("swag_sample", "out", out, n)
+    if out.shape[0] != len(ids):
+        raise BayesLMError("swag_sample: %d rows of out for %d sample ids" % (out.shape[0], len(ids)))
+    k_live, ld_dev = int(k_live), 0
+    if not 0 <= k_live <= L.SWAG_RANK_MAX:
+        raise BayesLMError("swag_sample: k_live = %d outside 0..%d" % (k_live, L.SWAG_RANK_MAX))
+    L.require_gfx950()
+    if k_live:
+        if dev is None:
+            raise BayesLMError("swag_sample: k_live = %d without deviation rows" % k_live)
+        ld_dev = _swag_rows("swag_sample", "dev", dev, n)
+        if dev.shape[0] < k_live:
+            raise BayesLMError("swag_sample: k_live = %d of %d deviation rows" % (k_live, dev.shape[0]))
+        z2 = swag_z2(ids, seed, k_live, mean.device) if z2 is None else dev_tensor(z2, "swag_sample: z2")
+        if tuple(z2.shape) != (len(ids), k_live):
+            raise BayesLMError("swag_sample: z2 is %s, (%d, %d) expected" % (tuple(z2.shape), len(ids), k_live))
+    else:
+        dev = z2 = None
+    calls().blm_swag_sample(ptr(out), ld_out, ptr(mean), ptr(m2), ptr(dev), ld_dev, k_live, ptr(z2), n, C.byref(draw), stream())
+    return out
+
+
+def logp_avg_accum(logits, acc, s, S, targets=None, hsum=None, nll_s=None, V=None):
+    """Sample ``s`` of ``S`` into the running model average of a chunk of rows (blm_logp_avg_accum): with logp = log-softmax of
+    the first V columns of ``logits`` (R, >= V), ``acc`` (R, >= V) becomes logp at s = 0 (it is not read) and
+    logaddexp(acc, logp) after, less log S at s = S - 1: log mean_s p_s once every sample is in.  ``hsum`` (R,) gathers the
+    samples' entropies the same way; ``nll_s`` (S, R) gets row s = -logp[r, targets[r]] (0 for a target outside [0, V)).
+    Row strides are honoured; both matrices are used in place.  The same bits in every run."""
+    for name, t in (("logits", logits), ("acc", acc)):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.stride(-1) != 1:
+            raise BayesLMError("logp_avg_accum: %s must be a row-major (R, V) matrix" % name)
+        dev_tensor(t[:1], "logp_avg_accum: %s" % name)
+    R, V = logits.shape[0], int(V if V is not None else logits.shape[1])
+    if acc.shape[0] != R or not 1 <= V <= min(logits.shape[1], acc.shape[1]):
+        raise BayesLMError("logp_avg_accum: logits %s, acc %s, V = %d" % (tuple(logits.shape), tuple(acc.shape), V))
+    s, S = int(s), int(S)
+    if not (1 <= S <= L.SWAG_SAMPLES_MAX and 0 <= s < S):
+        raise BayesLMError("logp_avg_accum: sample %d of %d (1..%d samples)" % (s, S, L.SWAG_SAMPLES_MAX))
+    if (targets is None) != (nll_s is None):
+        raise BayesLMError("logp_avg_accum: targets and nll_s go together")
+    tgt = None
+    if targets is not None:
+        tgt = dev_tensor(targets.reshape(-1), "logp_avg_accum: targets", torch.int64)
+        if dev_tensor(nll_s, "logp_avg_accum: nll_s") is not nll_s or tuple(nll_s.shape) != (S, R) or tgt.numel() != R:
+            raise BayesLMError("logp_avg_accum: nll_s must be a contiguous (%d, %d) matrix beside %d targets" % (S, R, R))
+    if hsum is not None and (dev_tensor(hsum, "logp_avg_accum: hsum") is not hsum or hsum.numel() != R):
+        raise BayesLMError("logp_avg_accum: hsum must be a contiguous array of %d" % R)
+    if R == 0:
+        return acc
+    L.require_gfx950()
+    ld, lda = ((t.stride(0) if R > 1 else max(t.stride(0), V)) for t in (logits, acc))
+    calls().blm_logp_avg_accum(ptr(logits), ld, ptr(acc), lda, ptr(tgt), R, V, s, S, ptr(hsum), ptr(nll_s), stream())
+    return acc
+
+
 def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=1.0):
     """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
     with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64

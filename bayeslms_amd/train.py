@@ -127,7 +127,52 @@ def build_parser():
                         '2015): the student\'s softmax(logits / T) is trained against the teacher raised to 1 / T and renormalised, '
                         'times T^2; the hard-label term stays at temperature 1.  With --distill-top-k the K entries are renormalised '
                         '(T other than 1 needs --distill-top-k-renorm 1), and one --distill-cache file serves every temperature')
+    p.add_argument('--swag-save', type=str, default='', metavar='PATH',
+                   help='new, optional: collect a SWAG posterior over all weights from the SGD iterates (bayeslms_amd/swag.py; Maddox et '
+                        'al. 2019) and write it to PATH at the end of training; bayeslms_amd.evaluate --swag PATH reads it.  Single '
+                        'process only')
+    p.add_argument('--swag-start', type=int, default=None, metavar='E',
+                   help='new, optional (with --swag-save): the first epoch, 1-based, that collects (default 1)')
+    p.add_argument('--swag-every', type=int, default=None, metavar='N',
+                   help='new, optional (with --swag-save): 0 = one iterate at each epoch\'s end (the default), else one every N '
+                        'optimisation steps from epoch E on')
+    p.add_argument('--swag-rank', type=int, default=None, metavar='K',
+                   help='new, optional (with --swag-save): deviations kept for the low-rank term, 0..32 (default 20; 0: diagonal only)')
+    p.add_argument('--swag-lr', type=float, default=None, metavar='LR',
+                   help='new, optional (with --swag-save): from epoch E on the learning rate is this constant and the halving rule is '
+                        'suspended (default: the schedule is untouched)')
     return p
+
+
+SWAG_FLAGS = ("swag_save", "swag_start", "swag_every", "swag_rank", "swag_lr")
+
+
+def take_swag_args(args, world):
+    """The --swag-* flags, taken OUT of ``args`` (a run without them prints the configuration it printed before there were any)
+    and refused before anything is loaded -> a namespace (save, start, every, rank, lr), or None without --swag-save."""
+    got = {f: getattr(args, f) for f in SWAG_FLAGS}
+    for f in SWAG_FLAGS:
+        delattr(args, f)
+    if not got["swag_save"]:
+        for f in SWAG_FLAGS[1:]:
+            if got[f] is not None:
+                raise SystemExit("--%s needs --swag-save" % f.replace("_", "-"))
+        return None
+    if world > 1:
+        raise SystemExit("--swag-save runs in a single process: data-parallel collection is not built (world size %d)" % world)
+    w = argparse.Namespace(save=got["swag_save"], start=1 if got["swag_start"] is None else got["swag_start"],
+                           every=got["swag_every"] or 0, rank=20 if got["swag_rank"] is None else got["swag_rank"], lr=got["swag_lr"])
+    if w.start < 1:
+        raise SystemExit("--swag-start is a 1-based epoch (got %d)" % w.start)
+    if w.every < 0:
+        raise SystemExit("--swag-every must be 0 (each epoch's end) or a positive number of steps (got %d)" % w.every)
+    if not 0 <= w.rank <= 32:
+        raise SystemExit("--swag-rank must lie in 0..32 (got %d)" % w.rank)
+    if w.lr is not None and not (math.isfinite(w.lr) and w.lr > 0):
+        raise SystemExit("--swag-lr must be positive and finite (got %r)" % w.lr)
+    if w.start > args.epochs:
+        raise SystemExit("--swag-start %d lies beyond --epochs %d: nothing would be collected" % (w.start, args.epochs))
+    return w
 
 
 # the flags build_model reads: what --distill-teacher-args may set for the teacher
@@ -321,13 +366,18 @@ class ValidationSchedule:
         dist.broadcast(t, src=0, group=self.group)
         return float(t.item())
 
-    def update(self, val_loss):
-        """-> (the job's validation loss, improved, stop).  ``improved`` False means: lr has been halved."""
+    def observe(self, val_loss):
+        """-> (the job's validation loss, improved): the comparison alone, no halving (a held learning rate, --swag-lr)"""
         val_loss = self.agree(val_loss)
         improved = (not self.best_val) or val_loss < self.best_val  # train.py:497
         if improved:
             self.best_val = val_loss
-        else:
+        return val_loss, improved
+
+    def update(self, val_loss):
+        """-> (the job's validation loss, improved, stop).  ``improved`` False means: lr has been halved."""
+        val_loss, improved = self.observe(val_loss)
+        if not improved:
             self.lr /= 2.
             self.counter += 1
         return val_loss, improved, self.counter == self.patience
@@ -344,6 +394,7 @@ def main(argv=None, history=None):
         history = {}
     history.update({"interval_loss": [], "valid_loss": [], "halved_epochs": [], "test_loss": None, "ms_per_batch": []})
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    swag_args = take_swag_args(args, world)
     check_report_args(args, world)
     teacher_shape = check_distill_args(args, world)
     teacher_sd = load_teacher_state(args) if teacher_shape is not None else None
@@ -463,6 +514,18 @@ def main(argv=None, history=None):
     trainer = engine.Trainer(model, lr=args.lr, clip=args.clip, momentum=0.9, kl_scale=kl_scale, seed=args.seed,
                              rank=rank, world=world, overlap=bool(args.dp_overlap), late_rows=bool(args.dp_late_rows))
     is_rnn = args.model != 'Transformer'
+    collector = None
+    if swag_args is not None:
+        from . import swag
+        collector = swag.SwagCollector(trainer, swag_args.rank, swag_args.start, swag_args.every)
+        say("swag: collecting from epoch %d, %s, rank %d%s, into %s" % (
+            swag_args.start, "every %d steps" % swag_args.every if swag_args.every else "at each epoch's end", swag_args.rank,
+            "" if swag_args.lr is None else ", lr %g held from there" % swag_args.lr, swag_args.save))
+
+    def swag_collected(epoch, n):
+        if n is not None:
+            say('| swag n {:d} | epoch {:3d} | step {:d} | rank {:d} | k_live {:d} |'.format(
+                n, epoch, trainer.step_no, collector.posterior.rank, collector.posterior.k_live))
 
     def train_epoch(epoch, lr):
         total_loss = 0.
@@ -489,6 +552,8 @@ def main(argv=None, history=None):
                     logq, _ = teacher.logprobs(data)
                 loss, kl, hidden = trainer.step(data, targets, hidden, kl_fn, soft=(logq, args.distill_weight, args.distill_temperature))
                 total_soft, total_kd = total_soft + trainer.last_soft.soft, total_kd + trainer.last_soft.kl
+            if collector is not None:
+                swag_collected(epoch, collector.after_step(epoch))
             total_loss = total_loss + loss  # stays on the device: one host sync per log interval (train.py:422 syncs per step)
             if batch % args.log_interval == 0 and batch > 0:
                 if world > 1:  # the mean over the GLOBAL batch, as the single-process log line prints it
@@ -521,10 +586,18 @@ def main(argv=None, history=None):
     try:
         for epoch in range(1, args.epochs + 1):
             t0 = time.time()
-            train_epoch(epoch, sched.lr)
+            held = collector is not None and swag_args.lr is not None and collector.active(epoch)
+            if held:  # a constant rate from --swag-start on; the halving rule is suspended below
+                trainer.lr = swag_args.lr
+            train_epoch(epoch, swag_args.lr if held else sched.lr)
+            if collector is not None:
+                swag_collected(epoch, collector.epoch_end(epoch))
             if world > 1:
                 engine.heartbeat("epoch %d trained" % epoch, rank)
-            val_loss, improved, stop = sched.update(engine.evaluate(model, val_data, args.seq_len, rank=rank, world=world))
+            if held:
+                (val_loss, improved), stop = sched.observe(engine.evaluate(model, val_data, args.seq_len, rank=rank, world=world)), False
+            else:
+                val_loss, improved, stop = sched.update(engine.evaluate(model, val_data, args.seq_len, rank=rank, world=world))
             say('-' * 89)
             say('| end of epoch {:3d} | time: {:5.2f}s | valid loss {:5.2f} | valid ppl {:8.2f}'.format(
                 epoch, time.time() - t0, val_loss, math.exp(val_loss)))
@@ -535,7 +608,7 @@ def main(argv=None, history=None):
                 if is_main:
                     with open(args.save, 'wb') as f:
                         torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, f)
-            else:  # train.py:503-508: halve LR, fresh SGD (momentum reset), reload best
+            elif not held:  # train.py:503-508: halve LR, fresh SGD (momentum reset), reload best
                 history["halved_epochs"].append(epoch)
                 trainer.reset_optimizer(sched.lr)
                 if world > 1:
@@ -551,6 +624,12 @@ def main(argv=None, history=None):
         say('-' * 89)
         say('Exiting from training early')
 
+    if collector is not None:
+        if collector.posterior.n < 1:
+            say("swag: no iterate was collected: %s is not written" % swag_args.save)
+        else:
+            collector.posterior.save(swag_args.save)
+            say("swag: wrote %s (n %d, rank %d)" % (swag_args.save, collector.posterior.n, collector.posterior.rank))
     if world > 1:
         dist.barrier()
     if os.path.exists(args.save):

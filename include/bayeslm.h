@@ -41,6 +41,7 @@ typedef enum blm_status {
 #define BLM_STREAM_WEIGHT  0x10000000u  /* class in the top 4 bits + tensor id (low 28 bits) */
 #define BLM_STREAM_DROPOUT 0x20000000u  /* + site id */
 #define BLM_STREAM_LRT     0x30000000u  /* + site id: the pre-activation noise of local reparameterisation */
+#define BLM_STREAM_SWAG    0x40000000u  /* + 0: a SWAG sample's diagonal noise, + 1: its low-rank noise; step = sample id */
 
 typedef struct blm_rng {
   uint64_t seed;    /* Philox key                                             */
@@ -650,6 +651,66 @@ int blm_dyneval_rms(const float* ms, int64_t n, int count, float* rms, float* me
  * also writes g = 0 in the same pass.  p, g, p0 and rms must not overlap one another. */
 int blm_dyneval_update(float* p, float* g, const float* p0, const float* rms, const float* mean, int64_t n, float lr, float decay,
                        float eps, int zero_grad, void* stream);
+
+/* --------------------------------------------------------------------------
+ * SWAG (csrc/swag.hip; Maddox, Garipov, Izmailov, Vetrov, Wilson, NeurIPS 2019): a Gaussian over ALL weights fitted to the SGD
+ * iterates, and the model average over its samples.  P floats of weights in one flat buffer, n iterates collected so far, a
+ * ring of K <= BLM_SWAG_RANK_MAX deviation rows.
+ *
+ * Collection of iterate theta as number n (count = n), Welford form (no sq - mean^2 cancellation), in fp32 in this order and
+ * without contraction, inv = 1 / (n + 1) rounded once:
+ *   d = theta - mean;  mean' = mean + d * inv;  dev = theta - mean';  m2' = m2 + d * dev
+ * and dev goes to row n mod K of the ring (the caller passes that row).  count == 0 writes mean' = theta, m2' = 0, dev = 0 and
+ * reads neither mean nor m2, which may be uninitialised.  var = m2 / n is the population variance; K_live = min(n, K).
+ *
+ * Sample j:  theta_j = mean + a sqrt(max(var, floor)) z1_j + b sum_{k < K_live} D[k] z2[j][k], evaluated in fp32 as
+ *   sd = a * sqrt(max(m2 * inv_n, floor));  base = fma(sd, z1, mean);  low = fma(D[k], z2[j][k], low), k ascending from low = 0;
+ *   out = fma(b, low, base)
+ * with a, b, inv_n = 1 / n and floor rounded to fp32 once by the caller (full form, K_live >= 2: a = sqrt(c / 2),
+ * b = sqrt(c / (2 (K_live - 1))) for a scale c; diagonal form: a = sqrt(c), k_live = 0).  z1_j[i] is element i of the Philox
+ * normal stream (rng.seed, rng.stream, step = sample_id[j]): the values blm_philox_normal writes for that blm_rng; rng.step is
+ * not read.  By convention rng.stream = BLM_STREAM_SWAG + 0 and z2[j][.] are the first K_live elements of
+ * (seed, BLM_STREAM_SWAG + 1, step = sample_id[j]).  A sample is a pure function of (mean, m2, D, seed, id, a, b, inv_n, floor):
+ * the same bits alone, in a longer list, at another slot and on either the 16-byte or the scalar path.
+ *
+ * Average of the S samples' next-word distributions, row by row: for sample s with logits z_s,
+ *   logp_s = z_s - lse(z_s);  acc = log((1 / S) sum_s exp(logp_s));  H_s = -sum_v p_s log p_s;  hsum = sum_s H_s
+ * accumulated one sample per call: s == 0 writes acc = logp_0 and hsum = H_0 without reading either, every later s folds
+ * acc = max(acc, logp) + log1p(exp(-|acc - logp|)) (both -inf: -inf), and s == S - 1 then subtracts log S.
+ * -------------------------------------------------------------------------- */
+#define BLM_SWAG_RANK_MAX 32
+#define BLM_SWAG_DRAWS_MAX 8
+#define BLM_SWAG_SAMPLES_MAX 64
+typedef struct blm_swag_draw {
+  uint32_t abi_version; /* BLM_ABI_VERSION */
+  int32_t count;        /* 1 .. BLM_SWAG_DRAWS_MAX samples in this launch */
+  float a, b;           /* finite, >= 0 */
+  float inv_n;          /* 1 / n: finite, > 0 */
+  float var_floor;      /* the floor under var: finite, >= 0 */
+  uint32_t sample_id[BLM_SWAG_DRAWS_MAX]; /* sample_id[j] for j < count; the others are not read */
+  blm_rng rng;          /* seed and stream of z1; step is not read (sample_id[j] takes its place) */
+} blm_swag_draw;
+/* One streaming pass.  dev_row == NULL: diagonal posterior, no deviation is written.  Arrays that are 16-byte aligned take
+ * 16-byte accesses over the body and a scalar tail; any other alignment of a float takes the scalar path whole.  The arrays must
+ * not overlap.  BLM_ERR_INVALID, before any launch: NULL theta, mean or m2, n_floats outside 0..2^40, count outside 0..2^24-1.
+ * n_floats == 0: BLM_OK. */
+int blm_swag_collect(const float* theta, float* mean, float* m2, float* dev_row, int64_t n_floats, int64_t count, void* stream);
+/* out: draw->count rows of n_floats at stride ld_out; dev: k_live rows at stride ld_dev; z2: draw->count rows of k_live floats,
+ * contiguous, on the device (NULL with k_live == 0, as dev).  A count of 3 or 5..7 runs the form of 4 or 8 slots with the surplus
+ * slots idle: nothing is computed or written for them.  All slots come from one read of mean, m2 and the deviation rows.
+ * BLM_ERR_INVALID, before any launch: NULL out, mean, m2 or draw, count outside 1..BLM_SWAG_DRAWS_MAX, k_live outside
+ * 0..BLM_SWAG_RANK_MAX, k_live > 0 without dev or z2, ld_out or ld_dev < n_floats, n_floats outside 0..2^40, a / b / floor negative
+ * or not finite, inv_n not finite or not > 0; BLM_ERR_ABI: abi_version.  n_floats == 0: BLM_OK. */
+int blm_swag_sample(float* out, int64_t ld_out, const float* mean, const float* m2, const float* dev, int64_t ld_dev, int k_live,
+                    const float* z2, int64_t n_floats, const blm_swag_draw* draw, void* stream);
+/* logits (rows, V) at row stride ld, acc (rows, V) at row stride ld_acc, not overlapping.  hsum (rows,) may be NULL.  targets
+ * (rows,) int64 and nll_s (S, rows) go together or are both NULL: nll_s[s * rows + r] = -logp_s[r, targets[r]], and 0 for a
+ * target outside [0, V), as in blm_ce_fwd_bwd.  One workgroup per row: rows held in registers for V <= 36864 when both bases
+ * are 16-byte aligned and both strides multiples of 4, two sweeps otherwise.  No atomics, fixed order.
+ * BLM_ERR_INVALID, before any launch: NULL logits or acc, targets without nll_s or the reverse, rows < 0, V <= 0, ld or ld_acc
+ * < V, S outside 1..BLM_SWAG_SAMPLES_MAX, s outside [0, S), extents too large.  rows == 0: BLM_OK. */
+int blm_logp_avg_accum(const float* logits, int64_t ld, float* acc, int64_t ld_acc, const int64_t* targets, int rows, int V, int s,
+                       int S, float* hsum, float* nll_s, void* stream);
 
 /* --------------------------------------------------------------------------
  * Word error rate of rescored n-best lists (csrc/nbest.hip; bayeslms_amd/nbest_wer.py): word-level alignment in bulk, selection
