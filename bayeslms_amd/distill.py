@@ -29,7 +29,7 @@ import torch
 
 from . import incremental, ops
 from ._lib import TOPK_MAX
-from .model import inference_decoder, mc_sampling, repackage_hidden, require_variational_sites
+from .model import CarriedState, inference_decoder, mc_sampling, require_variational_sites
 
 __all__ = ["Teacher", "TeacherCache", "CacheMismatch", "sha256_file", "sha256_tensor"]
 
@@ -62,30 +62,19 @@ class Teacher:
                                        "is not one model over a stream" % (type(model).__name__, cell))
         self.model, self.S, self.seed = model, S, int(seed)
         self.vocab = self.dec.weight.shape[0]
-        self.hidden = None
+        self.state = None if self.recurrent else CarriedState(model, 0)  # a stateless teacher carries nothing: no reset needed
         self._mc_dec = None
 
     def reset(self, columns):
         """Start a walk over a stream of ``columns`` batch columns: a recurrent teacher's state -- one (h, c) set, or one per
         sample -- starts from zero."""
-        self.hidden = None
-        if self.recurrent:
-            self.hidden = [self.model.init_hidden(columns) for _ in range(self.S)] if self.S else self.model.init_hidden(columns)
+        self.state = CarriedState(self.model, columns, max(self.S, 1))
 
-    def _forward(self, data, slot):
-        """Decoder input rows (T * B, K) of one pass; ``slot``: the sample whose carried state is used (None: the only one)."""
-        m = self.model
-        if not self.recurrent:
-            x = m(data)
-        else:
-            if self.hidden is None:
-                raise ops.BayesLMError("Teacher.logprobs: call reset(columns) before the first batch of a recurrent teacher")
-            x, h = m(data, self.hidden if slot is None else self.hidden[slot])
-            h = repackage_hidden(h)
-            if slot is None:
-                self.hidden = h
-            else:
-                self.hidden[slot] = h
+    def _forward(self, data, slot=0):
+        """Decoder input rows (T * B, K) of one pass; ``slot``: the sample whose carried state is used."""
+        if self.state is None:
+            raise ops.BayesLMError("Teacher.logprobs: call reset(columns) before the first batch of a recurrent teacher")
+        x = self.state(data, slot)
         return x.reshape(-1, x.shape[-1])
 
     def logprobs(self, data):
@@ -95,7 +84,7 @@ class Teacher:
             with torch.no_grad(), dec.inference(input_rows=True):
                 if self.S == 0:
                     m.eval()
-                    logits = ops.linear(self._forward(data, None), dec.weight, dec.bias)
+                    logits = ops.linear(self._forward(data), dec.weight, dec.bias)
                     rows = logits
                     if not logits.is_contiguous():  # an odd vocabulary's padded rows (ops.linear): normalised where they are
                         rows = logits.as_strided((logits.shape[0], logits.stride(0)), (logits.stride(0), 1))

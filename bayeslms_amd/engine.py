@@ -12,6 +12,7 @@ import contextlib
 import dataclasses
 import datetime
 import gc
+import itertools
 import math
 import os
 import sys
@@ -671,62 +672,28 @@ def evaluate(model, source, seq_len, eval_batch_size=None, rank=0, world=1, grou
     single process walks the whole stream, and with W ranks doing that each the validation pass would be the part of an epoch
     that does not scale (it is ~1 % of a one-GPU epoch of the AMI recipe, ~10 % of an 8-GPU one).  Every rank returns the
     same value up to the all-reduce (callers that branch on it take rank 0's: train.ValidationSchedule)."""
-    from .data import get_batch
-    from .model import inference_decoder, repackage_hidden
+    from .model import CarriedState, inference_decoder
     model.eval()
     cols = source.shape[1]
     lo, hi = (rank * cols) // world, ((rank + 1) * cols) // world
     mine = source if world == 1 else source[:, lo:hi].contiguous()
     total = torch.zeros((), device=source.device, dtype=torch.float64)
-    hidden = model.init_hidden(mine.shape[1]) if (hasattr(model, "init_hidden") and hi > lo) else None
     # the decoder returns the per-token NLL itself when it can (ops.linear_nll: the (T*B, V) logits are never stored);
     # BLM_EVAL_FUSED_NLL=0 keeps decoder + cross-entropy kernel
     dec = inference_decoder(model)
     fused = (os.environ.get("BLM_EVAL_FUSED_NLL", "1") != "0" and dec is not None
              and ops.linear_nll_supported(dec.weight, dec.bias))
-    # A model without carried state (the Transformers) sees every window on its own: G full windows are evaluated as ONE batch of
-    # G x columns independent columns (same positions, same causal mask per column) -- the reference's eval batch of 10-20 columns
-    # gives the matrix cores 1280-2560 rows per product, G of them ~16384 (headline model, 12 windows of 20 x 128: 1.085 M tokens/s
-    # window by window, 1.178 M in threes, 1.197 M in sixes, tools/eval_windows_probe.py).  total = sum over windows of len * mean is unchanged up
-    # to the order of the additions.  BLM_EVAL_WINDOWS=1 walks the windows one by one as train.py:441-458 does.
-    # (_report_windows below restates this grouping for evaluate_report: a change here belongs there too;
-    # tests/test_gpu_eval_report.py compares the batches the two hand to the model)
-    n_full = max(0, (source.size(0) - 1) // seq_len)  # windows of exactly seq_len rows; the ragged last one goes alone
-    n_win = 1
-    if hi > lo:
-        rows = 16384 if hidden is None else 2400  # recurrent: the time loop is issued step by step, three windows of 700 rows pay, more do not
-        n_win = int(os.environ.get("BLM_EVAL_WINDOWS", "0")) or max(1, min(max(n_full, 1), rows // max(1, seq_len * (hi - lo))))
-    # A recurrent model carries its state from window to window (repackage_hidden), so G consecutive windows ARE one window of
-    # G seq_len steps: the same recurrence step for step, with the input / decoder products over G times the rows (the LSTM
-    # language models' evaluation batch gives them 700 rows per window) and the layer wavefront over a longer stretch
-    # (configs[1]'s model, 12 windows of 20 x 35: 668 k tokens/s window by window, 765 k in threes; no better and host-bound beyond).
-    stride = seq_len * (n_win if hidden is not None else 1)
+    # The windows come in groups (_eval_windows).  total = sum over windows of len * mean is unchanged up to the order of the
+    # additions: the windows of a group are equally sized, so sum_k len * mean_k = G len * mean of all.
     with torch.no_grad(), (dec.inference() if fused else contextlib.nullcontext()):
-        i, left = 0, n_full
-        while hidden is None and n_win > 1 and left > 1 and hi > lo:
-            g = min(n_win, left)
-            starts = range(i, i + g * seq_len, seq_len)
-            data = torch.cat([mine[k:k + seq_len] for k in starts], 1)
-            targets = torch.cat([mine[k + 1:k + 1 + seq_len] for k in starts], 1).reshape(-1)
-            if fused:
-                dec.set_nll_targets(targets)
-            out = model(data)
-            loss = out.mean() if fused else ops.cross_entropy(out.view(-1, out.shape[-1]), targets)[0]
-            total += (g * seq_len) * loss.double()  # equally sized windows: sum_k len * mean_k = G len * mean of all
-            i, left = i + g * seq_len, left - g
-        for i in range(i, source.size(0) - 1, stride):
-            if hi <= lo:
-                break  # more ranks than columns: nothing of this stream is mine
-            data, targets = get_batch(mine, i, stride)
-            if fused:
-                dec.set_nll_targets(targets)
-            if hidden is None:
-                out = model(data)
-            else:
-                out, hidden = model(data, hidden)
-                hidden = repackage_hidden(hidden)
-            loss = out.mean() if fused else ops.cross_entropy(out.view(-1, out.shape[-1]), targets)[0]
-            total += len(data) * loss.double()
+        if hi > lo:  # else more ranks than columns: nothing of this stream is mine
+            state = CarriedState(model, hi - lo)
+            for data, targets, starts, n in _eval_windows(mine, seq_len, state.hidden is not None):
+                if fused:
+                    dec.set_nll_targets(targets)
+                out = state(data)
+                loss = out.mean() if fused else ops.cross_entropy(out.view(-1, out.shape[-1]), targets)[0]
+                total += (len(starts) * n) * loss.double()
     if world > 1:  # sum_r (columns of r) * (its per-window means, summed) / all columns = the whole batch's per-window means, summed
         total = total * float(hi - lo) / float(cols)
         on_dev = dist.get_backend(group) == "nccl"
@@ -833,35 +800,63 @@ def report_from_tokens(nll, conf=None, entropy=None, rank=None, valid=None, bins
     return rep
 
 
-def _report_windows(source, seq_len, recurrent):
-    """The batches engine.evaluate forms from ``source`` in a single process, in its order -> (data, flat targets, text
-    position of every target): a stateless model gets G full windows side by side as one batch of G x columns and the ragged
-    last window alone; a recurrent one gets G consecutive windows as one longer window (same thresholds, same BLM_EVAL_WINDOWS).
-    Text position: column c of the batchified stream holds the tokens c * rows .. (c + 1) * rows - 1 of the text.
-    This restates the grouping rule inside evaluate (row budgets, BLM_EVAL_WINDOWS, the loop over full windows), which stays as it
-    is: a change to either belongs in both, and tests/test_gpu_eval_report.py compares the batches the two hand to the model."""
+def _eval_windows(source, seq_len, recurrent, group=True, limit=None, who="evaluate"):
+    """The batches every evaluation walk forms from the batchified stream ``source``, in order -> (data, flat targets, starts,
+    rows): ``data`` lays the windows that begin at the rows ``starts`` side by side, ``rows`` rows each (_window_positions
+    places the targets in the text; ``len(starts) * rows`` is the batch's weight in a sum of per-window means).
+
+    A model without carried state (the Transformers) sees every window on its own: G full windows are evaluated as ONE batch of
+    G x columns independent columns (same positions, same causal mask per column) -- the reference's eval batch of 10-20 columns
+    gives the matrix cores 1280-2560 rows per product, G of them ~16384 (headline model, 12 windows of 20 x 128: 1.085 M tokens/s
+    window by window, 1.178 M in threes, 1.197 M in sixes, tools/eval_windows_probe.py).  The ragged last window goes alone.
+    A recurrent model carries its state from window to window, so G consecutive windows ARE one window of G seq_len steps: the
+    same recurrence step for step, with the input / decoder products over G times the rows (the LSTM language models' evaluation
+    batch gives them 700 rows per window; the time loop is issued step by step, three windows of 700 rows pay, more do not) and
+    the layer wavefront over a longer stretch (configs[1]'s model, 12 windows of 20 x 35: 668 k tokens/s window by window, 765 k
+    in threes; no better and host-bound beyond).  BLM_EVAL_WINDOWS=G overrides G; 1 walks the windows one by one as
+    train.py:441-458 does.
+
+    ``group`` False is dynamic evaluation's plan: one window of ``seq_len`` rows at a time whatever the model and the
+    environment say, the first ``limit`` of them (None: all), refusing under the name ``who`` a stream without a target."""
     from .data import get_batch
+    if not group:
+        if int(seq_len) < 1:
+            raise ops.BayesLMError("%s: seq_len = %r" % (who, seq_len))
+        if source.dim() != 2 or source.shape[0] < 2:
+            raise ops.BayesLMError("%s: the stream holds %s rows: two are the least that give a target" % (who, tuple(source.shape)))
+        seq_len = int(seq_len)
     nrows, cols = source.shape
-    n_full = max(0, (nrows - 1) // seq_len)
-    rows = 2400 if recurrent else 16384
-    n_win = int(os.environ.get("BLM_EVAL_WINDOWS", "0")) or max(1, min(max(n_full, 1), rows // max(1, seq_len * cols)))
+    n_full = max(0, (nrows - 1) // seq_len)  # windows of exactly seq_len rows
+    n_win = 1
+    if group:
+        budget = 2400 if recurrent else 16384
+        n_win = int(os.environ.get("BLM_EVAL_WINDOWS", "0")) or max(1, min(max(n_full, 1), budget // max(1, seq_len * cols)))
     stride = seq_len * (n_win if recurrent else 1)
+
+    def plan():
+        i, left = 0, n_full
+        while not recurrent and n_win > 1 and left > 1:
+            g = min(n_win, left)
+            starts = range(i, i + g * seq_len, seq_len)
+            data = torch.cat([source[k:k + seq_len] for k in starts], 1)
+            targets = torch.cat([source[k + 1:k + 1 + seq_len] for k in starts], 1).reshape(-1)
+            yield data, targets, starts, seq_len
+            i, left = i + g * seq_len, left - g
+        for i in range(i, nrows - 1, stride):
+            data, targets = get_batch(source, i, stride)
+            yield data, targets, (i,), len(data)
+
+    return itertools.islice(plan(), limit)
+
+
+def _window_positions(shape, starts, rows):
+    """Text position of every target of one batch of _eval_windows over a stream of ``shape`` = (nrows, columns), flat in the
+    targets' order: column c of the batchified stream holds the tokens c * nrows .. (c + 1) * nrows - 1 of the text, so target
+    r of the window that begins at row ``start`` is token start + 1 + r + c * nrows in column c."""
+    nrows, cols = shape
     col0 = np.arange(cols, dtype=np.int64) * nrows
-
-    def pos(start, n):
-        return (np.arange(start + 1, start + 1 + n, dtype=np.int64)[:, None] + col0[None, :])
-
-    i, left = 0, n_full
-    while not recurrent and n_win > 1 and left > 1:
-        g = min(n_win, left)
-        starts = range(i, i + g * seq_len, seq_len)
-        data = torch.cat([source[k:k + seq_len] for k in starts], 1)
-        targets = torch.cat([source[k + 1:k + 1 + seq_len] for k in starts], 1).reshape(-1)
-        yield data, targets, np.concatenate([pos(k, seq_len) for k in starts], 1).reshape(-1)
-        i, left = i + g * seq_len, left - g
-    for i in range(i, nrows - 1, stride):
-        data, targets = get_batch(source, i, stride)
-        yield data, targets, pos(i, len(data)).reshape(-1)
+    return np.concatenate([np.arange(start + 1, start + 1 + rows, dtype=np.int64)[:, None] + col0[None, :] for start in starts],
+                          1).reshape(-1)
 
 
 def temperature_block(beta, fitted_on=None, at_bound=False, before=None, after=None, curve=None):
@@ -876,14 +871,15 @@ def temperature_block(beta, fitted_on=None, at_bound=False, before=None, after=N
 
 
 def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, betas, rows_out=None):
-    """The walk evaluate_report, evaluate_temperatures and the neural cache share -> (host arrays, text positions per window, V, S).
+    """The walk evaluate_report, evaluate_temperatures and the neural cache share -> (host arrays in walk order, the (starts,
+    rows) of every batch for _text_order, V, S).
     ``rows_out`` (mean weights only): a callable that is handed every window's decoder-input rows (rows, K), in the order of the
     targets, before the next window runs (the neural cache keeps them on the device).
     ``betas`` None: blm_row_stats reduces each chunk and the float arrays are (tokens,).  A list of J float32 inverse
     temperatures: blm_row_stats_temps reduces it, and nll, conf, entropy and dnll are (J, tokens), those of the tempered
     distributions; nll_s, h_pred and mi stay the untempered (tokens, ...) quantities of ops.linear_mc_logprobs."""
     from . import incremental
-    from .model import inference_decoder, mc_sampling, repackage_hidden
+    from .model import CarriedState, inference_decoder, mc_sampling
     S = int(mc_samples)
     model.eval()
     if dist.is_initialized() and dist.get_world_size() > 1:
@@ -906,8 +902,8 @@ def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, bet
             raise ops.BayesLMError("%s: mc_samples on %s: %s draws fresh noise at every time step of a call, so a "
                                    "sample is not one model over a stream" % (who, type(model).__name__, cell))
     V = dec.weight.shape[0]
-    cols = source.shape[1]
-    keep = {k: [] for k in ("tgt", "pos", "nll", "conf", "entropy", "dnll", "pred", "rank", "nll_s", "h_pred", "mi")}
+    keep = {k: [] for k in ("tgt", "nll", "conf", "entropy", "dnll", "pred", "rank", "nll_s", "h_pred", "mi")}
+    placed = []
 
     def row_stats(x, t):
         return ops.row_stats(x, t, V) if betas is None else ops.row_stats_temps(x, betas, t, V)
@@ -938,62 +934,86 @@ def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, bet
                 if betas is not None:
                     keep["dnll"].append(st.dnll)
 
-    with torch.no_grad(), dec.inference(input_rows=True):
-        if S == 0:
-            hidden = model.init_hidden(cols) if recurrent else None
-            for data, targets, pos in _report_windows(source, seq_len, recurrent):
-                if recurrent:
-                    x, hidden = model(data, hidden)
-                    hidden = repackage_hidden(hidden)
-                else:
-                    x = model(data)
-                reduce_rows(x.reshape(-1, x.shape[-1]), targets)
+    with torch.no_grad(), dec.inference(input_rows=True), (mc_sampling(model, seed, S) if S else contextlib.nullcontext()):
+        mc_dec = ops.McDecoder(dec.weight, dec.bias) if S else None  # the vocabulary padded once for the run
+        state = CarriedState(model, source.shape[1], max(S, 1))
+        for data, targets, starts, n in _eval_windows(source, seq_len, recurrent):
+            if S == 0:
+                x = state(data)
+                x = x.reshape(-1, x.shape[-1])
+                reduce_rows(x, targets)
                 if rows_out is not None:
-                    rows_out(x.reshape(-1, x.shape[-1]))
-                keep["tgt"].append(targets)
-                keep["pos"].append(pos)
-        else:
-            with mc_sampling(model, seed, S):
-                mc_dec = ops.McDecoder(dec.weight, dec.bias)  # the vocabulary padded once for the run
-                hidden = [model.init_hidden(cols) for _ in range(S)] if recurrent else None
-                for data, targets, pos in _report_windows(source, seq_len, recurrent):
-                    xs = []
-                    for s in range(S):
-                        model.set_step(s)
-                        if recurrent:
-                            x, h = model(data, hidden[s])
-                            hidden[s] = repackage_hidden(h)
-                        else:
-                            x = model(data)
-                        xs.append(x.reshape(-1, x.shape[-1]))
-                    reduce_rows(torch.stack(xs), targets)
-                    keep["tgt"].append(targets)
-                    keep["pos"].append(pos)
-    # one copy to the host: every float32 array side by side, the integers likewise
-    fl = [k for k in ("nll", "conf", "entropy", "dnll", "h_pred", "mi") if keep[k]]
+                    rows_out(x)
+            else:
+                xs = []
+                for s in range(S):
+                    model.set_step(s)
+                    x = state(data, s)
+                    xs.append(x.reshape(-1, x.shape[-1]))
+                reduce_rows(torch.stack(xs), targets)
+            keep["tgt"].append(targets)
+            placed.append((starts, n))
+    empty = ("nll",) if betas is None else ("nll", "conf", "entropy", "dnll", "pred", "rank")
+    return _tokens_to_host(keep, None if betas is None else len(betas), empty), placed, V, S
+
+
+_TEMPERED = ("nll", "conf", "entropy", "dnll")  # the fields that are (J, tokens) under J inverse temperatures
+
+
+def _tokens_to_host(keep, temps=None, empty=("nll",), samples=0):
+    """The per-window device arrays a walk kept, by field -> one host array per field, in walk order.  The float32 fields come
+    in ONE copy, stacked as rows, ``pred`` and ``rank`` in another.  ``temps`` J: the walk reduced its chunks for J inverse
+    temperatures, the _TEMPERED fields are (J, tokens) and take J rows each.  A text without a token gives the fields ``empty``
+    (and ``tgt``) as typed arrays of no token, ``nll_s`` with ``samples`` columns."""
     n_tok = sum(t.numel() for t in keep["tgt"])
-    host = {}
-    if n_tok:
-        if betas is None:
-            packed = torch.stack([torch.cat(keep[k]) for k in fl]).cpu().numpy()
-            host = {k: packed[j] for j, k in enumerate(fl)}
-        else:  # the tempered fields are (J, tokens), the Monte-Carlo ones one row each
-            rows = [torch.cat(keep[k], -1).reshape(-1, n_tok) for k in fl]
-            packed, at = torch.cat(rows).cpu().numpy(), 0
-            for k, r in zip(fl, rows):
-                host[k] = packed[at:at + r.shape[0]] if k in ("nll", "conf", "entropy", "dnll") else packed[at]
-                at += r.shape[0]
-        host["tgt"] = torch.cat(keep["tgt"]).cpu().numpy()
-        if keep["rank"]:
-            host["pred"], host["rank"] = torch.stack([torch.cat(keep["pred"]), torch.cat(keep["rank"])]).cpu().numpy()
-        if keep["nll_s"]:
-            host["nll_s"] = torch.cat(keep["nll_s"]).cpu().numpy()
-    else:
-        z = np.zeros(0, np.float32) if betas is None else np.zeros((len(betas), 0), np.float32)
-        host = {"nll": z, "tgt": np.zeros(0, np.int64)}
-        if betas is not None:
-            host.update(conf=z, entropy=z, dnll=z, rank=np.zeros(0, np.int32), pred=np.zeros(0, np.int32))
-    return host, keep["pos"], V, S
+    if not n_tok:
+        host = {k: np.zeros((temps, 0) if temps is not None and k in _TEMPERED else 0, np.float32) for k in empty}
+        host.update({k: np.zeros(0, np.int32) for k in ("pred", "rank") if k in empty}, tgt=np.zeros(0, np.int64))
+        if "nll_s" in empty:
+            host["nll_s"] = np.zeros((0, samples), np.float32)
+        return host
+    fl = [k for k in ("nll", "conf", "entropy", "dnll", "h_pred", "mi") if keep.get(k)]
+    rows = [torch.cat(keep[k], -1).reshape(-1, n_tok) for k in fl]
+    packed, at, host = torch.cat(rows).cpu().numpy(), 0, {}
+    for k, r in zip(fl, rows):
+        host[k] = packed[at:at + r.shape[0]] if (temps is not None and k in _TEMPERED) else packed[at]
+        at += r.shape[0]
+    host["tgt"] = torch.cat(keep["tgt"]).cpu().numpy()
+    if keep.get("rank"):
+        host["pred"], host["rank"] = torch.stack([torch.cat(keep["pred"]), torch.cat(keep["rank"])]).cpu().numpy()
+    if keep.get("nll_s"):
+        host["nll_s"] = torch.cat(keep["nll_s"]).cpu().numpy()
+    return host
+
+
+def _text_order(shape, placed):
+    """The permutation that puts a walk's tokens in text order; ``placed``: the (starts, rows) of its batches, in order"""
+    if not placed:
+        return np.zeros(0, np.int64)
+    return np.argsort(np.concatenate([_window_positions(shape, starts, n) for starts, n in placed]), kind="stable")
+
+
+def _betas_of(who, temperature):
+    """``temperature`` T as a report takes it -> None at exactly 1.0 (the untempered kernels run), else [float32(1 / T)]"""
+    if _float32_beta(who, temperature, "temperature") and float(temperature) != 1.0:
+        return [_float32_beta(who, 1.0 / float(temperature), "1 / temperature")]
+    return None
+
+
+def _report_of(host, V, S, bins, betas=None, row=0, order=None):
+    """EvalReport from the host arrays of a walk (_tokens_to_host).  ``betas``: the walk's inverse temperatures, of which the
+    report is that of ``betas[row]``, row ``row`` of the (J, tokens) fields; ``order`` (_text_order) asks for ``per_token``."""
+    if betas is not None:
+        host = {k: (v[row] if k in _TEMPERED else v) for k, v in host.items()}
+    valid = (host["tgt"] >= 0) & (host["tgt"] < V)
+    rep = report_from_tokens(host["nll"], host.get("conf"), host.get("entropy"), host.get("rank"), valid, bins,
+                             host.get("nll_s"), host.get("h_pred"), host.get("mi"))
+    rep.mc_samples = S
+    if betas is not None:
+        rep.temperature = temperature_block(betas[row])
+    if order is not None:
+        rep.per_token = {k: v[order] for k, v in host.items()}
+    return rep
 
 
 def _float32_beta(who, value, name):
@@ -1014,7 +1034,7 @@ def evaluate_report(model, source, seq_len, eval_batch_size=None, mc_samples=0, 
     """Held-out loss / perplexity, accuracy and calibration of ``model`` over the batchified stream ``source``, at mean weights
     (``mc_samples`` 0) or under the average of S = ``mc_samples`` >= 2 Monte-Carlo weight samples -> EvalReport.
 
-    The walk is engine.evaluate's (same windows, same grouping: _report_windows) with the decoder handing back its input rows;
+    The walk is engine.evaluate's (same windows, same grouping: _eval_windows) with the decoder handing back its input rows;
     those go through the decoder in chunks of _REPORT_ROWS rows and blm_row_stats reduces each chunk's (rows, V) matrix to
     per-token NLL, confidence, entropy, prediction and rank in one read.  The per-token float32 arrays stay on the device
     until the walk is over, come to the host in one copy, and every sum is formed there in float64 (report_from_tokens).
@@ -1039,22 +1059,10 @@ def evaluate_report(model, source, seq_len, eval_batch_size=None, mc_samples=0, 
     one other than 1.0 with mc_samples > 0 and calibration=False, where no row of width V exists.  ``eval_batch_size`` is accepted
     for symmetry with the reference's evaluate and unused, like there.  Single process only.  The model is left in eval mode with
     the caller's noise (seed, step, auto_step)."""
-    betas = None
-    if _float32_beta("evaluate_report", temperature, "temperature") and float(temperature) != 1.0:
-        betas = [_float32_beta("evaluate_report", 1.0 / float(temperature), "1 / temperature")]
-    host, pos, V, S = _report_walk("evaluate_report", model, source, seq_len, mc_samples, seed, calibration, betas)
-    if betas is not None:
-        host = {k: (v[0] if k in ("nll", "conf", "entropy", "dnll") else v) for k, v in host.items()}
-    valid = (host["tgt"] >= 0) & (host["tgt"] < V)
-    rep = report_from_tokens(host["nll"], host.get("conf"), host.get("entropy"), host.get("rank"), valid, bins,
-                             host.get("nll_s"), host.get("h_pred"), host.get("mi"))
-    rep.mc_samples = S
-    if betas is not None:
-        rep.temperature = temperature_block(betas[0])
-    if keep_tokens:
-        order = np.argsort(np.concatenate(pos)) if len(host["tgt"]) else np.zeros(0, np.int64)
-        rep.per_token = {k: v[order] for k, v in host.items()}
-    return rep
+    betas = _betas_of("evaluate_report", temperature)
+    host, placed, V, S = _report_walk("evaluate_report", model, source, seq_len, mc_samples, seed, calibration, betas)
+    order = _text_order(source.shape, placed) if keep_tokens else None
+    return _report_of(host, V, S, bins, betas, order=order)
 
 
 def evaluate_temperatures(model, source, seq_len, betas, mc_samples=0, seed=1111, bins=15):
@@ -1075,12 +1083,8 @@ def evaluate_temperatures(model, source, seq_len, betas, mc_samples=0, seed=1111
     valid = (host["tgt"] >= 0) & (host["tgt"] < V)
     n = int(valid.sum())
     reps, dloss = [], []
-    for j, b in enumerate(bs):
-        rep = report_from_tokens(host["nll"][j], host["conf"][j], host["entropy"][j], host.get("rank"), valid, bins,
-                                 host.get("nll_s"), host.get("h_pred"), host.get("mi"))
-        rep.mc_samples = S
-        rep.temperature = temperature_block(b)
-        reps.append(rep)
+    for j in range(len(bs)):
+        reps.append(_report_of(host, V, S, bins, bs, j))
         dloss.append(float(host["dnll"][j].astype(np.float64)[valid].sum() / n) if n else float("nan"))
     return reps, dloss
 
@@ -1254,12 +1258,12 @@ def _cache_walk(who, model, source, seq_len):
         rows[at[0]:at[0] + x.shape[0]] = x
         at[0] += x.shape[0]
 
-    host, pos, V, _ = _report_walk(who, model, source, seq_len, 0, 0, True, None, rows_out=keep_rows)
+    host, placed, V, _ = _report_walk(who, model, source, seq_len, 0, 0, True, None, rows_out=keep_rows)
     if at[0] != n_tok or len(host["tgt"]) != n_tok:
         raise ops.BayesLMError("%s: the walk handed back %d rows for %d targets (%d expected)" % (who, at[0], len(host["tgt"]), n_tok))
-    order = np.argsort(np.concatenate(pos), kind="stable") if n_tok else np.zeros(0, np.int64)
+    order = _text_order(source.shape, placed)
     valid = (host["tgt"] >= 0) & (host["tgt"] < V)
-    text_rows = rows.index_select(0, torch.from_numpy(order).to(dev))  # text order: one gather by pos
+    text_rows = rows.index_select(0, torch.from_numpy(order).to(dev))  # text order: one gather by position
     del rows
     return {"rows": text_rows, "tgt": torch.from_numpy(host["tgt"][order]).to(dev),
             "nll": torch.from_numpy(np.ascontiguousarray(host["nll"][order])).to(dev),
@@ -1581,32 +1585,16 @@ def _rehomed(who, model, what):
         ops.set_embed_grad_sink(sink)
 
 
-def _dyneval_windows(who, source, seq_len, limit=None):
-    """(start row, data, flat targets) of every window of ``seq_len`` rows, one at a time, the ragged last one included"""
-    from .data import get_batch
-    if int(seq_len) < 1:
-        raise ops.BayesLMError("%s: seq_len = %r" % (who, seq_len))
-    if source.dim() != 2 or source.shape[0] < 2:
-        raise ops.BayesLMError("%s: the stream holds %s rows: two are the least that give a target" % (who, tuple(source.shape)))
-    starts = list(range(0, source.size(0) - 1, int(seq_len)))
-    return [(i,) + tuple(get_batch(source, i, int(seq_len))) for i in (starts if limit is None else starts[:limit])]
-
-
 def _dyneval_walk(who, model, flat, windows, cols, after_backward):
     """Steps 1 and 2 of every window: eval-mode forward in grad mode, the per-token NLL, the gradient of the window's mean NLL
     into flat.flat_grad (which must be zero on entry to every window: ``after_backward(k, nll, last)`` sees to it) -> the
     per-token NLLs, one device array per window."""
-    from .model import repackage_hidden
-    recurrent = hasattr(model, "init_hidden")
-    hidden = model.init_hidden(cols) if recurrent else None
+    from .model import CarriedState
+    state = CarriedState(model, cols)
     nlls = []
     with torch.enable_grad():
-        for k, (_, data, targets) in enumerate(windows):
-            if recurrent:
-                out, hidden = model(data, hidden)
-                hidden = repackage_hidden(hidden)
-            else:
-                out = model(data)
+        for k, (data, targets, _, _) in enumerate(windows):
+            out = state(data)
             if not out.requires_grad:
                 raise ops.BayesLMError("%s: the eval-mode forward of %s gave logits without a gradient path" % (who, type(model).__name__))
             loss, nll = ops.cross_entropy(out.view(-1, out.shape[-1]), targets, unit_grad=True)
@@ -1626,8 +1614,8 @@ def dyneval_stats(model, source, seq_len, windows):
     if int(windows) < 1:
         raise ops.BayesLMError("%s: windows = %r, the statistics need at least one" % (who, windows))
     with _dyneval_session(who, model) as (flat, _):
-        wins = _dyneval_windows(who, source, seq_len, int(windows))
-        ms = torch.zeros_like(flat.flat_grad)
+        wins = list(_eval_windows(source, seq_len, False, group=False, limit=int(windows), who=who))
+        ms =torch.zeros_like(flat.flat_grad)
 
         def accumulate(k, nll, last):
             ops.dyneval_accum(ms, flat.flat_grad)
@@ -1653,18 +1641,14 @@ def _dyneval_run(who, model, flat, theta0, source, wins, lr, decay, stats, eps, 
 
     nlls = _dyneval_walk(who, model, flat, wins, source.shape[1], update)
     V = model.decoder.weight.shape[0]  # targets outside [0, V) are skipped, as evaluate_report skips them
-    tgt = torch.cat([w[2] for w in wins]).cpu().numpy()
+    tgt = torch.cat([w[1] for w in wins]).cpu().numpy()
     nll = torch.cat(nlls).cpu().numpy()
     valid = (tgt >= 0) & (tgt < V)
     base = report_from_tokens(nll, valid=valid)
     rep = DynEvalReport(tokens=base.tokens, loss=base.loss, ppl=base.ppl, lr=lr, decay=decay, eps=eps,
                         rule="sgd" if stats is None else "rms", windows=len(wins), updates=max(0, len(wins) - 1))
     if keep_tokens:
-        nrows, cols = source.shape
-        col0 = np.arange(cols, dtype=np.int64) * nrows
-        pos = np.concatenate([(np.arange(i + 1, i + 1 + len(d), dtype=np.int64)[:, None] + col0[None, :]).reshape(-1)
-                              for i, d, _ in wins])
-        order = np.argsort(pos, kind="stable")
+        order = _text_order(source.shape, [w[2:] for w in wins])
         rep.per_token = {"tgt": tgt[order], "nll": nll[order]}
     return rep
 
@@ -1693,7 +1677,7 @@ def evaluate_dynamic(model, source, seq_len, lr, decay, stats=None, eps=0.01, ke
     lr, decay, eps = _dyneval_rates(who, lr, decay, eps)
     with _dyneval_session(who, model) as (flat, theta0):
         _dyneval_check_stats(who, flat, stats)
-        wins = _dyneval_windows(who, source, seq_len)
+        wins = list(_eval_windows(source, seq_len, False, group=False, who=who))
         return _dyneval_run(who, model, flat, theta0, source, wins, lr, decay, stats, eps, keep_tokens, on_window)
 
 
@@ -1718,7 +1702,7 @@ def fit_dyneval(model, source, seq_len, lrs, decays, stats=None, eps=0.01, max_w
         _dyneval_check_stats(who, flat, stats)
         if max_windows is not None:
             source = source[:int(max_windows) * int(seq_len) + 1]
-        wins = _dyneval_windows(who, source, seq_len)
+        wins = list(_eval_windows(source, seq_len, False, group=False, who=who))
         curve = [[a, b, _dyneval_run(who, model, flat, theta0, source, wins, a, b, stats, eps, False, None).loss] for a, b in cands]
     best = min(curve, key=lambda c: c[2])
     return DynEvalFit(lr=best[0], decay=best[1], loss=best[2], loss_static=curve[0][2], curve=curve)
@@ -1737,14 +1721,14 @@ def evaluate_swag(model, source, seq_len, posterior, samples, seed=1111, scale=0
     The model is re-homed into a FlatBuffers for the walk (every parameter gets back its original storage, .grad and training
     flag, by return or by exception) and the S samples are drawn once (SwagPosterior.draw: sample s is a function of
     (posterior, seed, s, scale, diag) alone; S x P floats, refused beyond its byte budget).  The walk is evaluate_report's
-    (_report_windows), one window at a time: for every s the flat buffer is overwritten with sample s, the eval-mode forward
+    (_eval_windows), one batch at a time: for every s the flat buffer is overwritten with sample s, the eval-mode forward
     runs (a recurrent model carries S hidden sets), the decoder's logits are formed in chunks of _REPORT_ROWS rows and
     blm_logp_avg_accum folds them into the window's (rows, V) running log-average, with each sample's NLL and entropy; after the
     last sample blm_row_stats (blm_row_stats_temps with one beta under a ``temperature`` other than 1: pbar^(1/T) / Z, as
     under mc_samples) reduces log pbar.  mi = H[pbar] - mean_s H[p_s], both untempered.
 
     Refused: samples outside 2..64, a world size above 1, noise source 'torch', a posterior made for another model."""
-    from .model import inference_decoder, repackage_hidden
+    from .model import CarriedState, inference_decoder
     who = "evaluate_swag"
     S = int(samples)
     if not 2 <= S <= 64:
@@ -1752,23 +1736,21 @@ def evaluate_swag(model, source, seq_len, posterior, samples, seed=1111, scale=0
                                "SwagPosterior.mean_state_dict)" % (who, S))
     if dist.is_initialized() and dist.get_world_size() > 1:
         raise ops.BayesLMError("%s runs in a single process (world size %d)" % (who, dist.get_world_size()))
-    betas = None
-    if _float32_beta(who, temperature, "temperature") and float(temperature) != 1.0:
-        betas = [_float32_beta(who, 1.0 / float(temperature), "1 / temperature")]
+    betas = _betas_of(who, temperature)
     dec = inference_decoder(model)
     if dec is None:
         raise ops.BayesLMError("%s: %s has no decoder that hands back its input rows" % (who, type(model).__name__))
     posterior.check(model)
-    recurrent = hasattr(model, "init_hidden")
-    V, cols = dec.weight.shape[0], source.shape[1]
-    keep = {k: [] for k in ("tgt", "pos", "nll", "conf", "entropy", "pred", "rank", "nll_s", "h_pred", "mi")}
+    V = dec.weight.shape[0]
+    keep = {k: [] for k in ("tgt", "nll", "conf", "entropy", "pred", "rank", "nll_s", "h_pred", "mi")}
+    placed = []
     with _rehomed(who, model, "a SWAG sample replaces every weight and runs") as flat:
         posterior.check(flat)
         draws = posterior.draw(S, seed, scale, diag)
         dev = flat.flat_param.device
         with torch.no_grad(), dec.inference(input_rows=True):
-            hidden = [model.init_hidden(cols) for _ in range(S)] if recurrent else None
-            for data, targets, pos in _report_windows(source, seq_len, recurrent):
+            state = CarriedState(model, source.shape[1], S)
+            for data, targets, starts, n in _eval_windows(source, seq_len, state.hidden is not None):
                 R = targets.numel()
                 chunks = [(a, min(R, a + _REPORT_ROWS)) for a in range(0, R, _REPORT_ROWS)]
                 acc = torch.empty(R, V, device=dev, dtype=torch.float32)
@@ -1776,44 +1758,20 @@ def evaluate_swag(model, source, seq_len, posterior, samples, seed=1111, scale=0
                 nll_s = [torch.empty(S, b - a, device=dev, dtype=torch.float32) for a, b in chunks]
                 for s in range(S):
                     flat.flat_param.copy_(draws[s])
-                    if recurrent:
-                        x, h = model(data, hidden[s])
-                        hidden[s] = repackage_hidden(h)
-                    else:
-                        x = model(data)
+                    x = state(data, s)
                     x = x.reshape(-1, x.shape[-1])
                     for c, (a, b) in enumerate(chunks):
                         ops.logp_avg_accum(ops.linear(x[a:b], dec.weight, dec.bias), acc[a:b], s, S, targets[a:b], hsum[a:b], nll_s[c])
                 for a, b in chunks:
                     st = ops.row_stats(acc[a:b], targets[a:b], V)
                     h_pred = st.entropy
-                    if betas is not None:
-                        tt = ops.row_stats_temps(acc[a:b], betas, targets[a:b], V)
-                        st = ops.RowStats(tt.nll[0], tt.conf[0], tt.entropy[0], tt.pred, tt.rank)
+                    if betas is not None:  # the tempered fields as (1, rows), as _report_walk keeps them
+                        st = ops.row_stats_temps(acc[a:b], betas, targets[a:b], V)
                     for k, v in (("nll", st.nll), ("conf", st.conf), ("entropy", st.entropy), ("pred", st.pred), ("rank", st.rank),
                                  ("h_pred", h_pred), ("mi", h_pred - hsum[a:b] / S)):
                         keep[k].append(v)
                 keep["nll_s"].append(torch.cat(nll_s, 1).t())
                 keep["tgt"].append(targets)
-                keep["pos"].append(pos)
-    if keep["tgt"]:
-        fl = ("nll", "conf", "entropy", "h_pred", "mi")
-        packed = torch.stack([torch.cat(keep[k]) for k in fl]).cpu().numpy()
-        host = {k: packed[j] for j, k in enumerate(fl)}
-        host["tgt"] = torch.cat(keep["tgt"]).cpu().numpy()
-        host["pred"], host["rank"] = torch.stack([torch.cat(keep["pred"]), torch.cat(keep["rank"])]).cpu().numpy()
-        host["nll_s"] = torch.cat(keep["nll_s"]).cpu().numpy()
-    else:
-        z = np.zeros(0, np.float32)
-        host = {"nll": z, "conf": z, "entropy": z, "h_pred": z, "mi": z, "tgt": np.zeros(0, np.int64), "pred": np.zeros(0, np.int32),
-                "rank": np.zeros(0, np.int32), "nll_s": np.zeros((0, S), np.float32)}
-    valid = (host["tgt"] >= 0) & (host["tgt"] < V)
-    rep = report_from_tokens(host["nll"], host["conf"], host["entropy"], host["rank"], valid, bins, host["nll_s"], host["h_pred"],
-                             host["mi"])
-    rep.mc_samples = S
-    if betas is not None:
-        rep.temperature = temperature_block(betas[0])
-    if keep_tokens:
-        order = np.argsort(np.concatenate(keep["pos"])) if len(host["tgt"]) else np.zeros(0, np.int64)
-        rep.per_token = {k: v[order] for k, v in host.items()}
-    return rep
+                placed.append((starts, n))
+    host = _tokens_to_host(keep, None if betas is None else 1, ("nll", "conf", "entropy", "h_pred", "mi", "pred", "rank", "nll_s"), S)
+    return _report_of(host, V, S, bins, betas, order=_text_order(source.shape, placed) if keep_tokens else None)

@@ -248,6 +248,24 @@ def repackage_hidden(h):
     return tuple(repackage_hidden(v) for v in h)
 
 
+class CarriedState:
+    """What a walk over a stream carries from one window to the next: nothing for a model without ``init_hidden`` (every window
+    stands alone), ``copies`` hidden sets of ``columns`` batch columns for a recurrent one (one per weight sample).
+    ``state(data, copy)`` runs the model on ``data`` from set ``copy``, keeps the new state detached from its history in its
+    place, and returns the model's output."""
+
+    def __init__(self, model, columns, copies=1):
+        self.model = model
+        self.hidden = [model.init_hidden(columns) for _ in range(copies)] if hasattr(model, "init_hidden") else None
+
+    def __call__(self, data, copy=0):
+        if self.hidden is None:
+            return self.model(data)
+        out, h = self.model(data, self.hidden[copy])
+        self.hidden[copy] = repackage_hidden(h)
+        return out
+
+
 # ----------------------------------------------------------------------------
 # Transformer parts
 # ----------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """CPU: blm_row_stats is declared, exported, bound and refuses bad arguments on the host; the report arithmetic
-(engine.report_from_tokens: binning, ECE, top-5, skipped tokens) against hand-computed cases; the evaluate command line's
-arguments; train.py refuses --test-report under more than one rank."""
+(engine.report_from_tokens: binning, ECE, top-5, skipped tokens) against hand-computed cases; the window plan every evaluation
+walk shares (engine._eval_windows) and the state carrier (model.CarriedState); the evaluate command line's arguments; train.py refuses --test-report under more than one rank."""
 import math
 import os
 import re
@@ -127,19 +127,123 @@ def test_no_tokens_and_bad_bins():
         _report([1.0], [0.5], [0.1], [0], bins=0)
 
 
-def test_windows_follow_engine_evaluate():
-    """_report_windows: a stateless model gets the full windows side by side and the ragged one alone, a recurrent one
-    consecutive windows as one; every target once, with its text position."""
+def _plan_source():
     import torch
-    from bayeslms_amd import engine
     cols, rows = 3, 47
-    src = torch.arange(rows * cols).view(cols, rows).t().contiguous()  # the value IS the text position
+    return torch.arange(rows * cols).view(cols, rows).t().contiguous()  # the value IS the text position
+
+
+def _plan(src, recurrent, **kw):
+    """engine._eval_windows as a list, each batch with the text positions of its targets"""
+    from bayeslms_amd import engine
+    return [(d, t, engine._window_positions(src.shape, starts, n), len(starts) * n)
+            for d, t, starts, n in engine._eval_windows(src, 5, recurrent, **kw)]
+
+
+def test_windows_follow_engine_evaluate(monkeypatch):
+    """_eval_windows: a stateless model gets the full windows side by side and the ragged one alone, a recurrent one
+    consecutive windows as one; every target once, with its text position."""
+    monkeypatch.delenv("BLM_EVAL_WINDOWS", raising=False)
+    src = _plan_source()
     for recurrent, shapes in ((False, [(5, 27), (1, 3)]), (True, [(45, 3), (1, 3)])):
-        got = list(engine._report_windows(src, 5, recurrent))
-        assert [tuple(d.shape) for d, _, _ in got] == shapes
-        for d, t, p in got:
+        got = _plan(src, recurrent)
+        assert [tuple(d.shape) for d, _, _, _ in got] == shapes
+        for d, t, p, _ in got:
             assert t.tolist() == p.tolist() and (d.reshape(-1) + 1).tolist() == t.tolist()
-        assert sorted(np.concatenate([p for _, _, p in got]).tolist()) == sorted(src[1:].reshape(-1).tolist())
+        assert sorted(np.concatenate([p for _, _, p, _ in got]).tolist()) == sorted(src[1:].reshape(-1).tolist())
+
+
+def _same(a, b):
+    import torch
+    return a.shape == b.shape and torch.equal(a, b)
+
+
+_NINE = [(5, 3)] * 9 + [(1, 3)]
+_PLAN_CASES = [  # BLM_EVAL_WINDOWS, recurrent, the batches' shapes over all 3 columns (the slice [:, 1:3]: 2 / 3 of the columns)
+    (None, False, [(5, 27), (1, 3)]), (None, True, [(45, 3), (1, 3)]),
+    ("1", False, _NINE), ("1", True, _NINE),
+    ("4", False, [(5, 12), (5, 12), (5, 3), (1, 3)]), ("4", True, [(20, 3), (20, 3), (6, 3)]),
+]
+
+
+@pytest.mark.parametrize("windows,recurrent,shapes", _PLAN_CASES)
+def test_window_plan(monkeypatch, windows, recurrent, shapes):
+    if windows is None:
+        monkeypatch.delenv("BLM_EVAL_WINDOWS", raising=False)
+    else:
+        monkeypatch.setenv("BLM_EVAL_WINDOWS", windows)
+    src = _plan_source()
+    got = _plan(src, recurrent)
+    assert [tuple(d.shape) for d, _, _, _ in got] == shapes
+    for d, t, p, _ in got:
+        assert t.tolist() == p.tolist() and (d.reshape(-1) + 1).tolist() == t.tolist()
+    assert sorted(np.concatenate([p for _, _, p, _ in got]).tolist()) == sorted(src[1:].reshape(-1).tolist())
+    assert sum(w for _, _, _, w in got) == 46  # windows x rows: what evaluate weights each batch's mean loss by
+    # a rank's column slice: positions there are relative to the slice, so shapes and targets only
+    mine = src[:, 1:3].contiguous()
+    got = _plan(mine, recurrent)
+    assert [tuple(d.shape) for d, _, _, _ in got] == [(r, c * 2 // 3) for r, c in shapes]
+    for d, t, _, _ in got:
+        assert (d.reshape(-1) + 1).tolist() == t.tolist()
+    assert sorted(np.concatenate([t.numpy() for _, t, _, _ in got]).tolist()) == sorted(mine[1:].reshape(-1).tolist())
+    assert sum(w for _, _, _, w in got) == 46
+
+
+@pytest.mark.parametrize("windows", [None, "4"])
+@pytest.mark.parametrize("recurrent", [False, True])
+def test_window_plan_ungrouped(monkeypatch, windows, recurrent):
+    """group=False, dynamic evaluation's plan: one window at a time whatever the model and BLM_EVAL_WINDOWS say"""
+    from bayeslms_amd import BayesLMError, engine
+    if windows is None:
+        monkeypatch.delenv("BLM_EVAL_WINDOWS", raising=False)
+    else:
+        monkeypatch.setenv("BLM_EVAL_WINDOWS", windows)
+    src = _plan_source()
+    got = _plan(src, recurrent, group=False)
+    assert [tuple(d.shape) for d, _, _, _ in got] == _NINE
+    for d, t, p, _ in got:
+        assert t.tolist() == p.tolist() and (d.reshape(-1) + 1).tolist() == t.tolist()
+    assert sorted(np.concatenate([p for _, _, p, _ in got]).tolist()) == sorted(src[1:].reshape(-1).tolist())
+    first = _plan(src, recurrent, group=False, limit=3)
+    assert len(first) == 3 and all(_same(a[0], b[0]) and _same(a[1], b[1]) for a, b in zip(first, got))
+    with pytest.raises(BayesLMError, match=r"fit_dyneval: seq_len = 0"):
+        engine._eval_windows(src, 0, recurrent, group=False, who="fit_dyneval")
+    with pytest.raises(BayesLMError, match=r"dyneval_stats: the stream holds \(1, 3\) rows: two are the least that give a target"):
+        engine._eval_windows(src[:1], 5, recurrent, group=False, who="dyneval_stats")
+
+
+def test_carried_state():
+    """model.CarriedState: ``copies`` detached hidden sets for a module with init_hidden, nothing for one without"""
+    import torch
+    from bayeslms_amd.model import CarriedState
+
+    class Counts(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.ones(()))
+
+        def init_hidden(self, columns):
+            return (torch.zeros(columns), torch.zeros(2, columns))
+
+        def forward(self, data, hidden):
+            h, c = hidden
+            return data * self.w, (h + len(data) * self.w, c + len(data) * self.w)
+
+    class Stateless(torch.nn.Module):
+        def forward(self, *args):
+            assert len(args) == 1
+            return args[0] + 1
+
+    state = CarriedState(Counts(), 4, copies=3)
+    out = state(torch.ones(2, 4), 1)
+    assert out.requires_grad and out.shape == (2, 4)
+    state(torch.ones(3, 4), 1)
+    state(torch.ones(7, 4), 0)
+    assert [float(h[0]) for h, _ in state.hidden] == [7.0, 5.0, 0.0]
+    assert [tuple(c.shape) for _, c in state.hidden] == [(2, 4)] * 3 and float(state.hidden[1][1][1, 3]) == 5.0
+    assert not any(t.requires_grad for hc in state.hidden for t in hc)
+    free = CarriedState(Stateless(), 4, copies=3)
+    assert free.hidden is None and free(torch.zeros(2, 4), 2).tolist() == [[1.0] * 4] * 2 and free.hidden is None
 
 
 # ----------------------------------------------------------------------------------------------- command lines

@@ -337,7 +337,7 @@ def test_fit_cache_never_does_worse_than_the_model(dev, deterministic, kind):
         fit = engine.fit_cache(m, src, 35, 60, passes=2)
     finally:
         hook.remove()
-    one_walk = len(list(engine._report_windows(src, 35, hasattr(m, "init_hidden"))))
+    one_walk = len(list(engine._eval_windows(src, 35, hasattr(m, "init_hidden"))))
     print("%s synthetic text: theta %.6g lambda %.4f loss %.6f -> %.6f" % (kind, fit.theta, fit.lam, fit.loss_before, fit.loss_after))
     assert len(walks) == one_walk  # the model walked the text once, whatever the number of passes
     assert fit.loss_after <= fit.loss_before and 0.0 <= fit.lam <= 0.95 and 8 <= len(fit.curve) <= 16
