@@ -23,6 +23,8 @@ NBEST_GRID_MAX = 64  # BLM_NBEST_GRID_MAX
 SWAG_RANK_MAX = 32  # BLM_SWAG_RANK_MAX
 SWAG_DRAWS_MAX = 8  # BLM_SWAG_DRAWS_MAX
 SWAG_SAMPLES_MAX = 64  # BLM_SWAG_SAMPLES_MAX
+LAPLACE_SAMPLES_MAX = 32  # BLM_LAPLACE_SAMPLES_MAX
+LAPLACE_LINKS = {"probit": 0, "expexp": 1}  # blm_laplace_row_stats' link; "mc" is blm_laplace_mc_rows
 OK = 0
 ERR_INVALID, ERR_ABI, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4  # blm_status (include/bayeslm.h)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -32,6 +34,7 @@ STREAM_WEIGHT = 0x10000000   # stream class in the top 4 bits, tensor / site id 
 STREAM_DROPOUT = 0x20000000
 STREAM_LRT = 0x30000000      # pre-activation noise of local reparameterisation (ops.bayes_linear_lrt), + site id
 STREAM_SWAG = 0x40000000     # a SWAG sample's noise: + 0 diagonal, + 1 low rank; the step is the sample id
+STREAM_LAPLACE = 0x50000000  # the logit noise of the last-layer Laplace predictive; the step is the sample id
 
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
@@ -177,6 +180,9 @@ SIGNATURES = {
     "blm_swag_collect": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "blm_swag_sample": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _i64, C.POINTER(SwagDraw), _vp]),
     "blm_logp_avg_accum": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "blm_laplace_curvature": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp]),
+    "blm_laplace_row_stats": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "blm_laplace_mc_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _rngp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_edit_distance": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "blm_nbest_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(NbestGrid), _vp, _vp]),
     "blm_nbest_mbr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, C.POINTER(NbestGrid), _vp, _vp, _vp]),

@@ -738,6 +738,7 @@ class EvalReport:
     mean_mi: Optional[float] = None        # mean mutual information between the word and the weights
     per_token: Optional[dict] = None       # keep_tokens: float / int arrays in text order, skipped tokens included (NaN / -1)
     swag: Optional[dict] = None            # SWAG (SwagPosterior.describe with scale, diag, samples, seed, path); None: the model's own weights
+    laplace: Optional[dict] = None         # last-layer Laplace (LaplacePosterior.describe with prior, link, samples, seed); None: none
     cache: Optional[dict] = None           # neural cache (CacheReport.as_dict, with the fit's block after fit_cache); None: no cache
     dyneval: Optional[dict] = None         # dynamic evaluation (DynEvalReport.as_dict beside the static loss, with the fit's block); None: none
     temperature: Optional[dict] = None     # temperature scaling (temperature_block); None: the distribution as the model gives it
@@ -745,7 +746,7 @@ class EvalReport:
     def as_dict(self):
         d = dataclasses.asdict(self)
         del d["per_token"]
-        for k in ("temperature", "cache", "dyneval", "swag"):  # a run without one writes what it wrote before there was one
+        for k in ("temperature", "cache", "dyneval", "swag", "laplace"):  # a run without one writes what it wrote before there was one
             if d[k] is None:
                 del d[k]
         return d
@@ -870,11 +871,13 @@ def temperature_block(beta, fitted_on=None, at_bound=False, before=None, after=N
             "curve": curve}
 
 
-def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, betas, rows_out=None):
+def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, betas, rows_out=None, chunks=None):
     """The walk evaluate_report, evaluate_temperatures and the neural cache share -> (host arrays in walk order, the (starts,
     rows) of every batch for _text_order, V, S).
     ``rows_out`` (mean weights only): a callable that is handed every window's decoder-input rows (rows, K), in the order of the
     targets, before the next window runs (the neural cache keeps them on the device).
+    ``chunks`` (mean weights only): a callable (rows, targets) that takes the place of the row reduction for every window (the
+    Laplace walks form their own products from the rows); the host arrays are then None.
     ``betas`` None: blm_row_stats reduces each chunk and the float arrays are (tokens,).  A list of J float32 inverse
     temperatures: blm_row_stats_temps reduces it, and nll, conf, entropy and dnll are (J, tokens), those of the tempered
     distributions; nll_s, h_pred and mi stay the untempered (tokens, ...) quantities of ops.linear_mc_logprobs."""
@@ -941,7 +944,10 @@ def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, bet
             if S == 0:
                 x = state(data)
                 x = x.reshape(-1, x.shape[-1])
-                reduce_rows(x, targets)
+                if chunks is None:
+                    reduce_rows(x, targets)
+                else:
+                    chunks(x, targets)
                 if rows_out is not None:
                     rows_out(x)
             else:
@@ -953,6 +959,8 @@ def _report_walk(who, model, source, seq_len, mc_samples, seed, calibration, bet
                 reduce_rows(torch.stack(xs), targets)
             keep["tgt"].append(targets)
             placed.append((starts, n))
+    if chunks is not None:
+        return None, placed, V, S
     empty = ("nll",) if betas is None else ("nll", "conf", "entropy", "dnll", "pred", "rank")
     return _tokens_to_host(keep, None if betas is None else len(betas), empty), placed, V, S
 
@@ -1775,3 +1783,194 @@ def evaluate_swag(model, source, seq_len, posterior, samples, seed=1111, scale=0
                 placed.append((starts, n))
     host = _tokens_to_host(keep, None if betas is None else 1, ("nll", "conf", "entropy", "h_pred", "mi", "pred", "rank", "nll_s"), S)
     return _report_of(host, V, S, bins, betas, order=_text_order(source.shape, placed) if keep_tokens else None)
+
+
+# ----------------------------------------------------------------------------
+# Last-layer Laplace posterior for the decoder (bayeslms_amd/laplace.py; include/bayeslm.h)
+# ----------------------------------------------------------------------------
+LAPLACE_LINKS = ("probit", "expexp", "mc")
+LAPLACE_GRID_MAX = 8  # finite prior precisions one walk of fit_laplace_prior takes
+
+
+@dataclasses.dataclass
+class LaplacePriorFit:
+    """What fit_laplace_prior returns: the prior precision with the lowest mean NLL on the fit text."""
+    tau: float          # the winner; inf: no finite candidate beat the model itself
+    loss: float         # its mean NLL on the fit text
+    loss_base: float    # the model's own (tau = inf, through the same kernels)
+    curve: list         # [tau, loss] per candidate, tau = inf first
+    link: str
+    samples: int
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+
+def _laplace_args(who, link, samples, taus):
+    """The argument checks that need no device -> (link, S, [tau, ...])"""
+    from . import laplace
+    if link not in LAPLACE_LINKS:
+        raise ops.BayesLMError("%s: link %r is none of %s" % (who, link, ", ".join(LAPLACE_LINKS)))
+    try:
+        S = int(samples)
+    except (TypeError, ValueError):
+        raise ops.BayesLMError("%s: samples = %r" % (who, samples))
+    if S != 0 and not 2 <= S <= ops.L.LAPLACE_SAMPLES_MAX:
+        raise ops.BayesLMError("%s: samples must be 0 or lie in 2..%d, got %d: one sample is no average, and blm_laplace_mc_rows "
+                               "takes at most %d" % (who, ops.L.LAPLACE_SAMPLES_MAX, S, ops.L.LAPLACE_SAMPLES_MAX))
+    if link == "mc" and S == 0:
+        raise ops.BayesLMError("%s: the mc link needs samples in 2..%d" % (who, ops.L.LAPLACE_SAMPLES_MAX))
+    if link != "mc" and S != 0:
+        raise ops.BayesLMError("%s: samples = %d with the closed-form link %r, which draws none: samples go with link 'mc'"
+                               % (who, S, link))
+    return link, S, [laplace.prior_precision(t, who) for t in taus]
+
+
+def _laplace_decoder(who, model, posterior=None):
+    from .model import inference_decoder
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        raise ops.BayesLMError("%s runs in a single process (world size %d)" % (who, dist.get_world_size()))
+    dec = inference_decoder(model)
+    if dec is None:
+        raise ops.BayesLMError("%s: %s has no decoder that hands back its input rows" % (who, type(model).__name__))
+    if posterior is not None:
+        posterior.check(model)
+    return dec
+
+
+@contextlib.contextmanager
+def _training_flags_kept(model):
+    """The walk puts the model into eval mode; every module gets its own training flag back, by return or by exception."""
+    flags = [(m, m.training) for m in model.modules()]
+    try:
+        yield
+    finally:
+        for m, f in flags:
+            m.training = f
+
+
+def fit_laplace(model, source, seq_len, max_windows=None):
+    """The last-layer Laplace posterior of ``model``'s decoder from the batchified stream ``source`` (the training text) ->
+    laplace.LaplacePosterior.  The walk is evaluate_report's (same windows, chunks of _REPORT_ROWS rows, eval mode, mean
+    weights, one process) over the first ``max_windows`` windows of ``seq_len`` rows (None: all).  Per chunk: the logits by
+    ops.linear, blm_laplace_curvature in place, the squared rows by blm_lrt_prepare, then ONE TN product that accumulates F_W
+    and, through colsum_a, F_b.  No label enters: every row counts.  F is checked once at the end for values that are not finite.
+    The model is left as found (training flags, decoder scope), also when the walk raises."""
+    from . import laplace
+    who = "fit_laplace"
+    dec = _laplace_decoder(who, model)
+    if max_windows is not None:
+        if int(max_windows) < 1:
+            raise ops.BayesLMError("%s: max_windows = %r" % (who, max_windows))
+        source = source[:int(max_windows) * int(seq_len) + 1]
+    V, K = dec.weight.shape
+    post = laplace.LaplacePosterior(V, K, dec.weight.device, laplace.manifest_of(dec))
+
+    def chunks(x, targets):
+        for a in range(0, x.shape[0], _REPORT_ROWS):
+            h = x[a:a + _REPORT_ROWS].contiguous()
+            logits = ops.linear(h, dec.weight, dec.bias)
+            ops.laplace_curvature(logits, out=logits)
+            post.accumulate(logits, ops._lrt_prepare(h, 0))
+
+    with _training_flags_kept(model):
+        _report_walk(who, model, source, seq_len, 0, 0, True, None, chunks=chunks)
+    if post.n_tokens < 1:
+        raise ops.BayesLMError("%s: the text gave no row" % who)
+    post.check_finite()
+    return post
+
+
+def _laplace_walk(who, model, source, seq_len, posterior, taus, link, S, seed):
+    """ONE walk for every prior precision of ``taus`` -> (one host dict per tau, placed, V).  Per chunk one logits product and
+    one square pass, then per tau one variance product ops.linear(h^2, 1 / (F_W + tau), 1 / (F_b + tau)) and one row launch."""
+    dec = _laplace_decoder(who, model, posterior)
+    inv = [posterior.inverse(t) for t in taus]
+    mc = link == "mc"
+    fields = ("tgt", "nll", "conf", "entropy", "pred", "rank", "nll_s", "h_pred", "mi")
+    keeps = [{k: [] for k in fields} for _ in taus]
+    vbars = [[] for _ in taus]
+    row0 = [0]
+
+    def chunks(x, targets):
+        for a in range(0, x.shape[0], _REPORT_ROWS):
+            h = x[a:a + _REPORT_ROWS].contiguous()
+            t = targets[a:a + _REPORT_ROWS]
+            logits = ops.linear(h, dec.weight, dec.bias)
+            h2 = ops._lrt_prepare(h, 0)
+            for keep, vb, (s_w, s_b) in zip(keeps, vbars, inv):
+                var = ops.linear(h2, s_w, s_b)
+                if mc:
+                    st = ops.laplace_mc_rows(logits, var, S, seed, t, row0[0] + a)
+                    for k, v in (("nll", st.bma_nll), ("conf", st.conf), ("entropy", st.h_pred), ("pred", st.pred), ("rank", st.rank),
+                                 ("nll_s", st.nll_s), ("h_pred", st.h_pred), ("mi", st.mi)):
+                        keep[k].append(v)
+                else:
+                    st = ops.laplace_row_stats(logits, var, t, link)
+                    for k, v in (("nll", st.nll), ("conf", st.conf), ("entropy", st.entropy), ("pred", st.pred), ("rank", st.rank)):
+                        keep[k].append(v)
+                    vb.append(st.vbar)
+        row0[0] += x.shape[0]
+        for keep in keeps:
+            keep["tgt"].append(targets)
+
+    with _training_flags_kept(model):
+        _, placed, V, _ = _report_walk(who, model, source, seq_len, 0, 0, True, None, chunks=chunks)
+    empty = ("nll", "conf", "entropy", "pred", "rank") + (("h_pred", "mi", "nll_s") if mc else ())
+    hosts = []
+    for keep, vb in zip(keeps, vbars):
+        host = _tokens_to_host(keep, None, empty, S)
+        if vb:
+            host["vbar"] = torch.cat(vb).cpu().numpy()
+        hosts.append(host)
+    return hosts, placed, V
+
+
+def evaluate_laplace(model, source, seq_len, posterior, prior_precision, link="probit", samples=0, seed=1111, bins=15,
+                     keep_tokens=False):
+    """evaluate_report's figures under the last-layer Laplace predictive of ``posterior`` (laplace.LaplacePosterior) with the
+    prior precision tau = ``prior_precision`` in (0, inf] -> EvalReport with a ``laplace`` block.  The walk is evaluate_report's;
+    per chunk the logits, the logit variance by one more decoder-sized product, then blm_laplace_row_stats (``link`` 'probit' or
+    'expexp') or blm_laplace_mc_rows (``link`` 'mc' with ``samples`` in 2..32, noise keyed by ``seed``).  Under 'mc' the report
+    carries sample_loss, mean_h_pred and mean_mi as the Monte-Carlo report does; the closed forms have no mutual information.
+    tau = inf is the model itself.  Refused before any launch: more than one rank, a model whose decoder cannot hand back its
+    rows, a posterior made for another decoder, tau <= 0 or NaN, samples outside 0 or 2..32, samples with a closed-form link,
+    'mc' without samples.  The model is left as found, also when the walk raises."""
+    who = "evaluate_laplace"
+    link, S, (tau,) = _laplace_args(who, link, samples, [prior_precision])
+    (host,), placed, V = _laplace_walk(who, model, source, seq_len, posterior, [tau], link, S, seed)
+    vbar = host.pop("vbar", None)
+    rep = _report_of(host, V, S, bins, order=_text_order(source.shape, placed) if keep_tokens else None)
+    rep.laplace = dict(posterior.describe(), prior_precision=tau, link=link, samples=S, seed=int(seed) if S else None)
+    if vbar is not None:
+        ok = (host["tgt"] >= 0) & (host["tgt"] < V)
+        rep.laplace["mean_vbar"] = float(vbar.astype(np.float64)[ok].mean()) if ok.any() else float("nan")
+    return rep
+
+
+def fit_laplace_prior(model, source, seq_len, posterior, taus, link="probit", samples=0, seed=1111):
+    """The prior precision among ``taus`` (1..8 finite values) with the lowest mean NLL on the held-out stream ``source`` ->
+    LaplacePriorFit, from ONE walk of the text: per chunk one logits product, then per candidate one variance product and one
+    row launch.  tau = inf, the model itself, is always a candidate, evaluated through the same kernels and placed first, so
+    that it wins a tie: the fitted loss never exceeds the model's own.  Refusals: evaluate_laplace's, and a tau that is not
+    finite."""
+    from . import laplace
+    who = "fit_laplace_prior"
+    try:
+        taus = list(taus)
+    except TypeError:
+        raise ops.BayesLMError("%s: taus must be 1..%d positive finite numbers, got %r" % (who, LAPLACE_GRID_MAX, taus))
+    if not 1 <= len(taus) <= LAPLACE_GRID_MAX:
+        raise ops.BayesLMError("%s: %d prior precisions, one walk takes 1..%d" % (who, len(taus), LAPLACE_GRID_MAX))
+    link, S, taus = _laplace_args(who, link, samples, taus)
+    if any(math.isinf(t) for t in taus):
+        raise ops.BayesLMError("%s: tau = inf is always a candidate; the grid takes finite values" % who)
+    cands = [float("inf")] + taus
+    hosts, _, V = _laplace_walk(who, model, source, seq_len, posterior, cands, link, S, seed)
+    losses = []
+    for host in hosts:
+        ok = (host["tgt"] >= 0) & (host["tgt"] < V)
+        losses.append(float(host["nll"].astype(np.float64)[ok].sum() / ok.sum()) if ok.any() else float("nan"))
+    best = laplace.select_prior(cands, losses)
+    return LaplacePriorFit(tau=cands[best], loss=losses[best], loss_base=losses[0], curve=[[t, v] for t, v in zip(cands, losses)],
+                           link=link, samples=S)

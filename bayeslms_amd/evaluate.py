@@ -51,7 +51,19 @@ that ``python -m bayeslms_amd.train --swag-save PATH`` wrote (engine.evaluate_sw
 ``--swag-samples 0`` evaluates the SWA mean through the ordinary mean-weight report.  ``--temperature`` is honoured.  The summary
 line gains ``| swag n ... rank ... scale ... samples ...`` and the report a ``swag`` block.  Refused beside ``--swag``:
 ``--mc-samples``, ``--fit-temperature-on``, ``--cache-window`` and the dyneval flags.  Without ``--swag`` the line and the report
-are what they were."""
+are what they were.
+
+Laplace.  ``--laplace PATH`` evaluates ``--data`` under the last-layer Laplace posterior of the decoder saved there
+(engine.evaluate_laplace; bayeslms_amd/laplace.py), ``--laplace-fit-on train.txt [--laplace-fit-windows N] [--laplace-save PATH]``
+fits one first (engine.fit_laplace: one pass over that text, no retraining, any checkpoint).  The prior precision is
+``--laplace-prior-precision TAU`` in (0, inf], or the entry of ``--laplace-prior-grid a,b,c`` (1..8 finite values, and always
+inf, the model itself) with the lowest loss on ``--fit-laplace-prior-on valid.txt`` (engine.fit_laplace_prior, one walk).
+``--laplace-link probit|expexp|mc`` picks the link from logit mean and variance to a distribution (default probit; mc needs
+``--laplace-samples`` 2..32, keyed by ``--mc-seed``, and adds the Monte-Carlo block).  The summary line gains ``| laplace tokens ...
+prior ... link ... [samples ...]`` and, after a prior fit, ``| fit loss a -> b`` of the fit text; the report gains a ``laplace``
+block, in which an infinite prior precision is written as the string ``"inf"`` (JSON has no number for it).  Refused beside
+these flags: ``--mc-samples``, ``--swag``, ``--cache-window``, the dyneval flags, ``--fit-temperature-on`` and a ``--temperature``
+other than 1.  Without them the line and the report are what they were."""
 import argparse
 import json
 import math
@@ -123,7 +135,77 @@ def build_parser():
     p.add_argument('--swag-scale', type=float, default=None, metavar='C',
                    help='with --swag: the scale of the sampled covariance (default 0.5, the value of Maddox et al. 2019; unmeasured here)')
     p.add_argument('--swag-diag', type=int, default=None, choices=[0, 1], help='with --swag: 1 = the diagonal form, no low-rank term')
+    p.add_argument('--laplace', type=str, default='', metavar='PATH', help='evaluate under the last-layer Laplace posterior saved there')
+    p.add_argument('--laplace-fit-on', type=str, default='', metavar='PATH',
+                   help='fit the Laplace posterior of the decoder on this text (the training text), then evaluate --data under it')
+    p.add_argument('--laplace-fit-windows', type=int, default=None, metavar='N', help='windows of --laplace-fit-on that are read (default all)')
+    p.add_argument('--laplace-save', type=str, default='', metavar='PATH', help='write the fitted posterior there')
+    p.add_argument('--laplace-prior-precision', type=float, default=None, metavar='TAU', help='precision of the prior N(0, 1/TAU), in (0, inf]')
+    p.add_argument('--fit-laplace-prior-on', type=str, default='', metavar='PATH',
+                   help='pick the prior precision on this held-out text (the validation text) from --laplace-prior-grid')
+    p.add_argument('--laplace-prior-grid', type=str, default='', metavar='a,b,c', help='1..8 finite prior precisions')
+    p.add_argument('--laplace-link', type=str, default=None, choices=['probit', 'expexp', 'mc'],
+                   help='from logit mean and variance to a distribution (default probit)')
+    p.add_argument('--laplace-samples', type=int, default=None, metavar='S', help='with --laplace-link mc: 2..32 logit samples (--mc-seed keys them)')
     return p
+
+
+def laplace_grid(text):
+    """"a,b,c" -> [a, b, c]: 1..8 positive finite numbers"""
+    try:
+        vals = [float(v) for v in text.split(",") if v.strip()]
+    except ValueError:
+        raise SystemExit("--laplace-prior-grid must be numbers separated by commas (got %r)" % text)
+    if not 1 <= len(vals) <= engine.LAPLACE_GRID_MAX or not all(math.isfinite(v) and v > 0 for v in vals):
+        raise SystemExit("--laplace-prior-grid needs 1..%d values, each positive and finite (got %r)" % (engine.LAPLACE_GRID_MAX, text))
+    return vals
+
+
+def check_laplace_args(args):
+    """The Laplace flags' refusals: before any file or device is touched."""
+    on = bool(args.laplace or args.laplace_fit_on)
+    if not on:
+        for flag, v in (("--laplace-fit-windows", args.laplace_fit_windows), ("--laplace-save", args.laplace_save or None),
+                        ("--laplace-prior-precision", args.laplace_prior_precision),
+                        ("--fit-laplace-prior-on", args.fit_laplace_prior_on or None),
+                        ("--laplace-prior-grid", args.laplace_prior_grid or None), ("--laplace-link", args.laplace_link),
+                        ("--laplace-samples", args.laplace_samples)):
+            if v is not None:
+                raise SystemExit("%s needs --laplace or --laplace-fit-on" % flag)
+        return
+    if args.laplace and args.laplace_fit_on:
+        raise SystemExit("--laplace and --laplace-fit-on exclude each other: load a posterior or fit one")
+    if not args.laplace_fit_on and (args.laplace_fit_windows is not None or args.laplace_save):
+        raise SystemExit("--laplace-fit-windows and --laplace-save need --laplace-fit-on")
+    if args.laplace_fit_windows is not None and args.laplace_fit_windows < 1:
+        raise SystemExit("--laplace-fit-windows must be at least 1 (got %d)" % args.laplace_fit_windows)
+    if bool(args.fit_laplace_prior_on) != bool(args.laplace_prior_grid):
+        raise SystemExit("--fit-laplace-prior-on and --laplace-prior-grid go together")
+    if args.fit_laplace_prior_on and args.laplace_prior_precision is not None:
+        raise SystemExit("--fit-laplace-prior-on and --laplace-prior-precision exclude each other: give tau or the text to pick it on")
+    if not args.fit_laplace_prior_on and args.laplace_prior_precision is None:
+        raise SystemExit("a Laplace posterior needs its prior: --laplace-prior-precision TAU, or --fit-laplace-prior-on with --laplace-prior-grid")
+    if args.laplace_prior_precision is not None and not args.laplace_prior_precision > 0:
+        raise SystemExit("--laplace-prior-precision must lie in (0, inf] (got %r)" % args.laplace_prior_precision)
+    if args.laplace_prior_grid:
+        laplace_grid(args.laplace_prior_grid)
+    link, S = args.laplace_link or "probit", args.laplace_samples or 0
+    if link == "mc" and not 2 <= S <= 32:
+        raise SystemExit("--laplace-link mc needs --laplace-samples in 2..32 (got %r)" % args.laplace_samples)
+    if link != "mc" and args.laplace_samples is not None:
+        raise SystemExit("--laplace-samples with --laplace-link %s: the closed-form links draw no sample" % link)
+    if args.mc_samples:
+        raise SystemExit("Laplace with --mc-samples: the posterior stands at the mean weights; its own samples are --laplace-samples")
+    if args.swag:
+        raise SystemExit("Laplace with --swag: two posteriors over the same decoder; the two together are not built")
+    if args.cache_window is not None:
+        raise SystemExit("Laplace with --cache-window: the cache mixes with the model's own distribution")
+    if args.dyneval_lr is not None or args.dyneval_decay is not None or args.fit_dyneval_on:
+        raise SystemExit("Laplace with dynamic evaluation: the curvature was fitted at the trained weights, which the update moves")
+    if args.fit_temperature_on:
+        raise SystemExit("Laplace with --fit-temperature-on: a temperature on top of the Laplace predictive is not built")
+    if args.temperature is not None and args.temperature != 1.0:
+        raise SystemExit("Laplace with --temperature %r: a temperature on top of the Laplace predictive is not built" % args.temperature)
 
 
 def check_swag_args(args):
@@ -237,6 +319,7 @@ def check_args(args):
     check_cache_args(args)
     check_dyneval_args(args)
     check_swag_args(args)
+    check_laplace_args(args)
     if args.temperature is not None and args.fit_temperature_on:
         raise SystemExit("--temperature and --fit-temperature-on exclude each other: give T or the text to fit it on")
     if args.temperature is not None and not (math.isfinite(args.temperature) and args.temperature > 0):
@@ -267,6 +350,13 @@ def summary_line(rep):
     w = rep.swag
     if w:
         line += " | swag n %d rank %d scale %.6g samples %d" % (w["n"], w["rank"], w["scale"], w["samples"])
+    lp = rep.laplace
+    if lp:
+        line += " | laplace tokens %d prior %.6g link %s" % (lp["tokens"], lp["prior_precision"], lp["link"])
+        if lp["samples"]:
+            line += " samples %d" % lp["samples"]
+        if lp.get("fitted_on"):
+            line += " | fit loss %.4f -> %.4f" % (lp["fit_loss_before"], lp["fit_loss_after"])
     d = rep.dyneval
     if d:
         line += " | dyneval rule %s lr %.6g decay %.6g | loss %.4f -> %.4f | ppl %.2f -> %.2f" % (
@@ -325,6 +415,8 @@ def main(argv=None):
     temperature, fit = (1.0 if args.temperature is None else args.temperature), None
     if args.swag:
         return swag_main(args, model, corpus, text, device, temperature)
+    if args.laplace or args.laplace_fit_on:
+        return laplace_main(args, model, corpus, text, device)
     if args.fit_temperature_on:
         fit = engine.fit_temperature(model, D.batchify(fit_text, args.batch_size, device), args.seq_len, mc_samples=args.mc_samples,
                                      seed=args.mc_seed, bins=args.bins, passes=args.fit_passes)
@@ -400,6 +492,60 @@ def swag_main(args, model, corpus, text, device, temperature):
     if args.write_tokens:
         write_tokens(rep, corpus.dictionary.idx2word, args.write_tokens)
     return rep
+
+
+def laplace_main(args, model, corpus, text, device):
+    """--laplace / --laplace-fit-on: the report under the decoder's last-layer Laplace predictive"""
+    from . import laplace
+    from ._lib import BayesLMError
+
+    def stream_of(flag, path):
+        toks = corpus.tokenize(path)
+        if len(toks) // args.batch_size < 2:
+            raise SystemExit("%s holds %d tokens: fewer than two rows of --batch-size %d columns" % (flag, len(toks), args.batch_size))
+        return D.batchify(toks, args.batch_size, device)
+
+    link, S = args.laplace_link or "probit", args.laplace_samples or 0
+    try:
+        if args.laplace:
+            posterior = laplace.LaplacePosterior.load(args.laplace, device)
+            posterior.check(model)  # the walks check again: four small sums on the device each time
+        else:
+            posterior = engine.fit_laplace(model, stream_of("--laplace-fit-on", args.laplace_fit_on), args.seq_len, args.laplace_fit_windows)
+            if args.laplace_save:
+                posterior.save(args.laplace_save)
+    except BayesLMError as e:
+        raise SystemExit("%s %s: %s" % ("--laplace" if args.laplace else "--laplace-fit-on", args.laplace or args.laplace_fit_on, e))
+    tau, pfit = args.laplace_prior_precision, None
+    if args.fit_laplace_prior_on:
+        pfit = engine.fit_laplace_prior(model, stream_of("--fit-laplace-prior-on", args.fit_laplace_prior_on), args.seq_len, posterior,
+                                        laplace_grid(args.laplace_prior_grid), link=link, samples=S, seed=args.mc_seed)
+        tau = pfit.tau
+    rep = engine.evaluate_laplace(model, D.batchify(text, args.batch_size, device), args.seq_len, posterior, tau, link=link, samples=S,
+                                  seed=args.mc_seed, bins=args.bins, keep_tokens=bool(args.write_tokens))
+    rep.laplace["path"] = args.laplace or args.laplace_save or None
+    if pfit is not None:
+        rep.laplace.update(fitted_on=args.fit_laplace_prior_on, fit_loss_before=pfit.loss_base, fit_loss_after=pfit.loss, curve=pfit.curve)
+    print(summary_line(rep), flush=True)
+    if args.write_report:
+        d = rep.as_dict()
+        d["laplace"] = laplace_block_json(d["laplace"])
+        with open(args.write_report, 'w') as f:
+            json.dump(d, f)
+    if args.write_tokens:
+        write_tokens(rep, corpus.dictionary.idx2word, args.write_tokens)
+    return rep
+
+
+def laplace_block_json(block):
+    """The ``laplace`` block as JSON takes it: an infinite prior precision (the block's own and the curve's) is the string "inf",
+    since JSON has no token for it."""
+    def tau(v):
+        return "inf" if isinstance(v, float) and math.isinf(v) else v
+    out = dict(block, prior_precision=tau(block["prior_precision"]))
+    if out.get("curve"):
+        out["curve"] = [[tau(t), v] for t, v in out["curve"]]
+    return out
 
 
 if __name__ == '__main__':

@@ -2739,6 +2739,133 @@ def logp_avg_accum(logits, acc, s, S, targets=None, hsum=None, nll_s=None, V=Non
     return acc
 
 
+# ----------------------------------------------------------------------------
+# last-layer Laplace posterior: the three row kernels of csrc/laplace.hip (definitions: include/bayeslm.h)
+# ----------------------------------------------------------------------------
+def _laplace_rows(who, name, t, V=None):
+    """A row-major (R, >= V) float32 device matrix, used in place whatever its row stride and base -> (R, V, row stride as the
+    kernel takes it)"""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.stride(-1) != 1:
+        raise BayesLMError("%s: %s must be a row-major (R, V) matrix" % (who, name))
+    dev_tensor(t[:1], "%s: %s" % (who, name))
+    R, V = t.shape[0], int(V if V is not None else t.shape[1])
+    if not 1 <= V <= t.shape[1]:
+        raise BayesLMError("%s: V = %d outside [1, %d], the columns of %s" % (who, V, t.shape[1], name))
+    ld = t.stride(0) if R > 1 else max(t.stride(0), V)
+    if ld < V:
+        raise BayesLMError("%s: the rows of %s overlap (row stride %d < %d)" % (who, name, ld, V))
+    return R, V, ld
+
+
+def _laplace_targets(who, targets, R):
+    if targets is None:
+        return None
+    tgt = dev_tensor(targets.reshape(-1), "%s: targets" % who, torch.int64)
+    if tgt.numel() != R:
+        raise BayesLMError("%s: %d targets for %d rows" % (who, tgt.numel(), R))
+    return tgt
+
+
+def laplace_curvature(logits, out=None, V=None):
+    """a = p (1 - p), p = softmax of the first V columns of each row of ``logits`` (R, >= V) (blm_laplace_curvature): the diagonal
+    Gauss-Newton factor of the decoder's Laplace posterior.  ``out`` None: a new (R, V) matrix; ``out`` the same tensor as
+    ``logits``: in place; any other overlap is refused.  Row strides are honoured; where a row of ``out`` has room for them,
+    the columns V .. Vq - 1 (V rounded up to 4) are written 0.  -> out"""
+    who = "laplace_curvature"
+    R, V, ld = _laplace_rows(who, "logits", logits, V)
+    if out is None:
+        out = torch.empty(R, V, device=logits.device, dtype=torch.float32)
+    Ro, _, lda = _laplace_rows(who, "out", out, V)
+    if Ro != R:
+        raise BayesLMError("%s: logits has %d rows, out %d" % (who, R, Ro))
+    if R == 0:
+        return out
+    L.require_gfx950()
+    calls().blm_laplace_curvature(ptr(logits), ld, ptr(out), lda, R, V, stream())
+    return out
+
+
+class LaplaceRowStats(NamedTuple):
+    """RowStats of the closed-form Laplace predictive (include/bayeslm.h, blm_laplace_row_stats), and the variance figure."""
+    nll: Optional[torch.Tensor]   # (R,) float32; None without targets
+    conf: torch.Tensor            # (R,) float32
+    entropy: torch.Tensor         # (R,) float32
+    pred: torch.Tensor            # (R,) int32
+    rank: Optional[torch.Tensor]  # (R,) int32; None without targets
+    vbar: torch.Tensor            # (R,) float32 sum_v ptilde_v var_v
+
+
+def _laplace_pair(who, z, var, V):
+    R, V, ldz = _laplace_rows(who, "z", z, V)
+    Rv, _, ldv = _laplace_rows(who, "var", var, V)
+    if Rv != R:
+        raise BayesLMError("%s: z has %d rows, var %d" % (who, R, Rv))
+    return R, V, ldz, ldv
+
+
+def laplace_row_stats(z, var, targets=None, link="probit", V=None):
+    """ops.row_stats of y = link(z, var) for every row of the logit means ``z`` and variances ``var`` (R, >= V), y formed in
+    registers from one read of each (blm_laplace_row_stats).  ``link``: 'probit', y = z / sqrt(1 + pi / 8 var), or 'expexp',
+    y = z + var / 2.  A row with a NaN or a var that is negative or not finite is NaN / -1 throughout.  -> LaplaceRowStats"""
+    who = "laplace_row_stats"
+    if link not in L.LAPLACE_LINKS:
+        raise BayesLMError("%s: link %r is neither 'probit' nor 'expexp' (the 'mc' link is laplace_mc_rows)" % (who, link))
+    R, V, ldz, ldv = _laplace_pair(who, z, var, V)
+    dev = z.device
+    conf, entropy, vbar = (torch.empty(R, device=dev, dtype=torch.float32) for _ in range(3))
+    pred = torch.empty(R, device=dev, dtype=torch.int32)
+    tgt = _laplace_targets(who, targets, R)
+    nll = rank = None
+    if tgt is not None:
+        nll = torch.empty(R, device=dev, dtype=torch.float32)
+        rank = torch.empty(R, device=dev, dtype=torch.int32)
+    if R:
+        L.require_gfx950()
+        calls().blm_laplace_row_stats(ptr(z), ldz, ptr(var), ldv, ptr(tgt), R, V, L.LAPLACE_LINKS[link], ptr(nll), ptr(conf),
+                                      ptr(entropy), ptr(pred), ptr(rank), ptr(vbar), stream())
+    return LaplaceRowStats(nll, conf, entropy, pred, rank, vbar)
+
+
+class LaplaceMcRows(NamedTuple):
+    """The Monte-Carlo Laplace predictive per row (include/bayeslm.h, blm_laplace_mc_rows)."""
+    bma_nll: Optional[torch.Tensor]  # (R,) float32 -log pbar[target]; None without targets
+    nll_s: Optional[torch.Tensor]    # (R, S) float32, a view of the kernel's (S, R); None without targets
+    h_pred: torch.Tensor             # (R,) float32 entropy of pbar
+    mi: torch.Tensor                 # (R,) float32 mean_s KL(p_s || pbar)
+    conf: torch.Tensor               # (R,) float32 max pbar
+    pred: torch.Tensor               # (R,) int32
+    rank: Optional[torch.Tensor]     # (R,) int32; None without targets
+
+
+def laplace_mc_rows(z, var, samples, seed, targets=None, row0=0, V=None):
+    """The model average over S = ``samples`` (1..32) logit samples z + sqrt(var) eps for every row of ``z`` and ``var``
+    (R, >= V) (blm_laplace_mc_rows); eps of row r, column v and sample s is element ((row0 + r) Vq + v) of the Philox normal
+    stream (seed, STREAM_LAPLACE, step = s), Vq = V rounded up to 4, made in registers.  ``row0``: the global index of the first
+    row, so that a text gives the same figures however it is chunked.  -> LaplaceMcRows"""
+    who = "laplace_mc_rows"
+    S, row0 = int(samples), int(row0)
+    if not 1 <= S <= L.LAPLACE_SAMPLES_MAX:
+        raise BayesLMError("%s: samples = %d outside 1..%d" % (who, S, L.LAPLACE_SAMPLES_MAX))
+    if not 0 <= row0 <= 1 << 40:
+        raise BayesLMError("%s: row0 = %d outside 0..2^40" % (who, row0))
+    R, V, ldz, ldv = _laplace_pair(who, z, var, V)
+    dev = z.device
+    h_pred, mi, conf = (torch.empty(R, device=dev, dtype=torch.float32) for _ in range(3))
+    pred = torch.empty(R, device=dev, dtype=torch.int32)
+    tgt = _laplace_targets(who, targets, R)
+    bma = nll_s = rank = None
+    if tgt is not None:
+        bma = torch.empty(R, device=dev, dtype=torch.float32)
+        nll_s = torch.empty(S, R, device=dev, dtype=torch.float32)
+        rank = torch.empty(R, device=dev, dtype=torch.int32)
+    if R:
+        L.require_gfx950()
+        r = L.rng(seed, L.STREAM_LAPLACE, 0)
+        calls().blm_laplace_mc_rows(ptr(z), ldz, ptr(var), ldv, ptr(tgt), R, V, S, C.byref(r), row0, ptr(bma), ptr(nll_s), ptr(h_pred),
+                                    ptr(mi), ptr(conf), ptr(pred), ptr(rank), stream())
+    return LaplaceMcRows(bma, None if nll_s is None else nll_s.t(), h_pred, mi, conf, pred, rank)
+
+
 def sample_rows(x, temperature=0.0, seed=0, stream_id=0, step=0, top_k=0, top_p=1.0):
     """One id per row of the (R, V) matrix x (blm_sample_rows): argmax at temperature 0, else Gumbel-max over x / temperature
     with Philox noise keyed by (seed, stream_id, step) and the (row, column) counter.  -> (R,) int64

@@ -42,6 +42,7 @@ typedef enum blm_status {
 #define BLM_STREAM_DROPOUT 0x20000000u  /* + site id */
 #define BLM_STREAM_LRT     0x30000000u  /* + site id: the pre-activation noise of local reparameterisation */
 #define BLM_STREAM_SWAG    0x40000000u  /* + 0: a SWAG sample's diagonal noise, + 1: its low-rank noise; step = sample id */
+#define BLM_STREAM_LAPLACE 0x50000000u  /* the logit noise of the last-layer Laplace predictive; step = sample id */
 
 typedef struct blm_rng {
   uint64_t seed;    /* Philox key                                             */
@@ -711,6 +712,60 @@ int blm_swag_sample(float* out, int64_t ld_out, const float* mean, const float* 
  * < V, S outside 1..BLM_SWAG_SAMPLES_MAX, s outside [0, S), extents too large.  rows == 0: BLM_OK. */
 int blm_logp_avg_accum(const float* logits, int64_t ld, float* acc, int64_t ld_acc, const int64_t* targets, int rows, int V, int s,
                        int S, float* hsum, float* nll_s, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Last-layer Laplace posterior for the decoder (csrc/laplace.hip; bayeslms_amd/laplace.py; MacKay 1992; Kristiadi, Hein, Hennig
+ * 2020; Daxberger et al. 2021): a Gaussian over the decoder's weights fitted after training, from one pass over a text.
+ *
+ * Decoder: z = W h + b with W (V, K) at the trained (mean) weights, p = softmax(z).  Prior N(0, 1/tau I), 0 < tau <= inf.
+ * Posterior precision, the diagonal of the generalised Gauss-Newton matrix summed over the N rows of a fit text:
+ *   a_t[v] = p_t[v] (1 - p_t[v]);   F_W[v,k] = sum_t a_t[v] h_t[k]^2;   F_b[v] = sum_t a_t[v];   Lambda = F + tau.
+ * No label enters: every row of the fit text counts, whatever its target.
+ * Predictive logits of a new row h: mean z, variance var[v] = sum_k h[k]^2 / Lambda_W[v,k] + 1 / Lambda_b[v] -- under a diagonal
+ * posterior exactly diagonal over v.  tau = inf gives var = 0, the model itself.
+ * Three links from (z, var) to a next-word distribution:
+ *   probit  ptilde = softmax(z / sqrt(1 + (pi / 8) var)), the mean-field approximation.  NOT invariant to a shift of the logits
+ *           z + c: the result depends on where the decoder's bias happens to put the row.
+ *   expexp  ptilde = softmax(z + var / 2) = E[e^{z_v}] / sum_u E[e^{z_u}].  Shift-invariant.
+ *   mc      S samples, the estimate the two closed forms approximate and the only link with a mutual information:
+ *             z_s[v] = fma(sqrt(var[v]), eps_s[v], z[v]);  p_s = softmax(z_s);  pbar = (1/S) sum_s p_s;
+ *             bma_nll = -log pbar[t];  h_pred = -sum_v pbar log pbar;  mi = (1/S) sum_s sum_v p_s (log p_s - log pbar), the KL
+ *             form of blm_linear_mc_stats, never a difference of two entropies;  conf = max_v pbar, pred the lowest index that
+ *             holds it, rank that of the target under pbar;  nll_s[s] = lse_s - z_s[t].
+ * Noise: eps_s[r, v] is element ((row0 + r) Vq + v) of the Philox normal stream (seed, BLM_STREAM_LAPLACE, step = s), Vq = V
+ * rounded up to 4: the values blm_philox_normal writes; row0 is the global index of the chunk's first row.  A token's figures
+ * therefore do not depend on how the text was chunked, on S, or on which other samples run beside it.
+ *
+ * The three entry points: vector ALU, one workgroup per row, folds in a fixed order without atomics (the same bits in every
+ * run), 16-byte accesses where bases are 16-byte aligned and strides multiples of 4, a guarded scalar path otherwise.  No
+ * workspace.  BLM_ERR_INVALID before any launch: a NULL operand, a negative count, V <= 0, a row stride below V, extents too
+ * large, and what each entry adds below.  Zero rows: BLM_OK, nothing launched.
+ * -------------------------------------------------------------------------- */
+#define BLM_LAPLACE_SAMPLES_MAX 32
+/* a[r, v] = fma(-p, p, p) with p = exp(x - lse) of row r of logits (rows, V; row stride ld), v < V; columns V .. Vq - 1 of a are
+ * written 0 when lda >= Vq.  a == logits with lda == ld is in place; any other overlap is refused.  One read of the row, one
+ * write, for V <= 36864 on the 16-byte path (the row is held in registers); two sweeps of the row otherwise.  A column at -inf
+ * gives 0; a row that holds a NaN gives a NaN row. */
+int blm_laplace_curvature(const float* logits, int64_t ld, float* a, int64_t lda, int rows, int V, void* stream);
+/* blm_row_stats' five figures of y[v] = link(z[r, v], var[r, v]) -- link 0: probit, 1: expexp -- with its rules for ties, NULL
+ * outputs and targets, and vbar[r] = sum_v ptilde_v var_v, a per-token variance figure (may be NULL).  z and var (R, V; row
+ * strides ldz, ldv) are each read once; y is formed in registers and never stored.  The probit's reciprocal square root is the
+ * hardware's (1 ulp).  A row with a NaN, or with a var that is negative, NaN or infinite, is answered as blm_row_stats answers
+ * a NaN row (vbar NaN too); a target outside [0, V) as there.  BLM_ERR_INVALID also: another link, nll or rank without tgt. */
+int blm_laplace_row_stats(const float* z, int64_t ldz, const float* var, int64_t ldv, const int64_t* tgt, int R, int V, int link,
+                          float* nll, float* conf, float* entropy, int32_t* pred, int32_t* rank, float* vbar, void* stream);
+/* The mc link over S samples, 1 <= S <= BLM_LAPLACE_SAMPLES_MAX; rng gives seed and stream, rng->step is not read.  Outputs are
+ * (R,), nll_s is (S, R) with sample s of row r at [s * R + r]; each may be NULL; bma_nll, nll_s and rank need tgt.  Nothing of
+ * S x V reaches memory: the noise is made in registers and made again wherever a later sweep needs it (three times in all).
+ * Sweep 1 finds lse_s, eight samples per pass over the row (z and var come from HBM once, the later passes re-read a row the
+ * workgroup just streamed); sweep 2 forms pbar of a column, then that column's KL terms.  One form for every V.  In fp32:
+ * sd = sqrt(var), pbar = (sum_s exp(z_s - lse_s)) * (1 / S), s ascending; sample s runs the same operations whatever S is.
+ * A row with a NaN or with a var that is negative, NaN or infinite gives NaN in every float output and -1 in pred and rank; a
+ * target outside [0, V) gives NaN in bma_nll and nll_s and -1 in rank for that row only.  BLM_ERR_INVALID also: S out of
+ * range, row0 outside 0..2^40. */
+int blm_laplace_mc_rows(const float* z, int64_t ldz, const float* var, int64_t ldv, const int64_t* tgt, int R, int V, int S,
+                        const blm_rng* rng, int64_t row0, float* bma_nll, float* nll_s, float* h_pred, float* mi, float* conf,
+                        int32_t* pred, int32_t* rank, void* stream);
 
 /* --------------------------------------------------------------------------
  * Word error rate of rescored n-best lists (csrc/nbest.hip; bayeslms_amd/nbest_wer.py): word-level alignment in bulk, selection
