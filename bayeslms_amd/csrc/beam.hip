@@ -382,14 +382,6 @@ __global__ __launch_bounds__(kThreads) void all_done_kernel(const uint8_t* done,
   if (threadIdx.x == 0) *all_done = ok ? 1 : 0;
 }
 
-// Lowest index wins a tie; a NaN score never wins (blm_sample_rows' rule).
-__device__ __forceinline__ void best_of(float& v, int& i, float v2, int i2) {
-  if (v2 > v || (v2 == v && i2 < i) || (v != v && v2 == v2)) {
-    v = v2;
-    i = i2;
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void sample_rows_filtered_kernel(const float* x, int64_t ldx, int V, float inv_t, int greedy,
                                                                         int top_k, float top_p, blm_rng rng, int64_t* out) {
   __shared__ SelSmem sm;
@@ -441,8 +433,7 @@ __global__ __launch_bounds__(kThreads) void sample_rows_filtered_kernel(const fl
   }
   const int nb = index_bits(V);
   const uint32_t imask = (1u << nb) - 1u;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
+  blm::Best b = {-INFINITY, blm::kNone};
   for (int c = threadIdx.x; c < V; c += kThreads) {
     float s = xr[c];
     if (cstar != 0 && (((u64)order_key(s) << nb) | (u64)(imask - (uint32_t)c)) < cstar) continue;
@@ -452,24 +443,10 @@ __global__ __launch_bounds__(kThreads) void sample_rows_filtered_kernel(const fl
       const float uu = ((float)(u.x >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0, 1)
       s = s * inv_t - logf(-logf(uu));                                         // Gumbel-max
     }
-    best_of(bv, bi, s, c);
+    blm::best_of(b, s, c);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(bv, o, 64);
-    const int i2 = __shfl_xor(bi, o, 64);
-    best_of(bv, bi, v2, i2);
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[w] = bv;
-    si[w] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < kThreads / 64; ++k) best_of(bv, bi, sv[k], si[k]);
-    out[row] = bi == 0x7fffffff ? 0 : bi;
-  }
+  blm::block_best<kThreads / 64>(b, sv, si);
+  if (threadIdx.x == 0) out[row] = b.i == blm::kNone ? 0 : b.i;
 }
 
 }  // namespace

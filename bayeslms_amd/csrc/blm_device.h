@@ -10,6 +10,15 @@
 
 namespace blm {
 
+// every pointer given is 16-byte aligned (a null pointer counts as aligned): what a float4 access of each needs
+__device__ __forceinline__ bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
+// component c (0..3) of a float4
+__device__ __forceinline__ float comp(const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
+
 // ---------------------------------------------------------------- Philox4x32-10
 // Same generator as oracle/philox.py (Random123 philox4x32_R(10)).
 struct u32x4 {
@@ -131,6 +140,103 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 #pragma unroll
   for (int i = 1; i < NW; ++i) t = fmaxf(t, red[i]);
   return t;
+}
+
+// a value every lane holds alike (a row reduction's result): one SGPR, no VGPR
+__device__ __forceinline__ float uniform(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// Row reductions of a 1024-thread workgroup (16 waves) that cost one register per value: the 16 per-wave partials are read
+// back one per lane and folded by a butterfly (block_sum<16> above reads all 16 into registers of every lane -- three sums are
+// 48 registers, which the register-resident row kernels do not leave).  Any number of values behind ONE barrier pair; `red` is
+// one row of 16 floats of LDS per value.  Fixed order -- wave_sum / wave_max, then offsets 8, 4, 2, 1: the same bits from every
+// run.  ROW_UNIFORM: the results go through uniform().  ROW_EACH: each value's butterfly is finished before the next one's
+// begins, instead of all values step by step -- the same arithmetic, another instruction order; a call site keeps the one its
+// kernel was scheduled and measured with.
+enum RowOp { ROW_SUM, ROW_MAX };
+enum RowForm { ROW_PLAIN = 0, ROW_UNIFORM = 1, ROW_EACH = 2 };
+template <RowOp OP>
+__device__ __forceinline__ float row_step(float f, int o) {
+  return OP == ROW_SUM ? f + __shfl_xor(f, o, 64) : fmaxf(f, __shfl_xor(f, o, 64));
+}
+template <RowOp OP, int FORM = ROW_PLAIN, class... F>
+__device__ __forceinline__ void row_fold(float (*red)[16], F&... f) {
+  ((f = OP == ROW_SUM ? wave_sum(f) : wave_max(f)), ...);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int i = 0;
+  __syncthreads();
+  if (lane == 0) ((red[i++][w] = f), ...);
+  __syncthreads();
+  i = 0;
+  if (FORM & ROW_EACH) {
+    ((f = row_step<OP>(row_step<OP>(row_step<OP>(row_step<OP>(red[i++][lane & 15], 8), 4), 2), 1),
+      f = (FORM & ROW_UNIFORM) ? uniform(f) : f), ...);
+  } else {
+    ((f = red[i++][lane & 15]), ...);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) ((f = row_step<OP>(f, o)), ...);
+    if (FORM & ROW_UNIFORM) ((f = uniform(f)), ...);
+  }
+}
+
+// Arg-max of scored indices: the lowest index wins a tie, and a NaN score never wins (it yields to any number, and nothing
+// yields to it).  kNone is the index of "nothing seen yet"; it loses every tie.
+struct Best {
+  float v;
+  int i;
+};
+constexpr int kNone = 0x7fffffff;
+__device__ __forceinline__ void best_of(Best& b, float v2, int i2) {
+  if (v2 > b.v || (v2 == b.v && i2 < b.i) || (b.v != b.v && v2 == v2)) {
+    b.v = v2;
+    b.i = i2;
+  }
+}
+__device__ __forceinline__ void wave_best(Best& b) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(b.v, o, 64);
+    const int i2 = __shfl_xor(b.i, o, 64);
+    best_of(b, v2, i2);
+  }
+}
+// The workgroup's best of NW waves -> thread 0 (the other threads' values are partial); sv / si are NW words of LDS each.
+// With `flag` (and NW words sf), thread 0's *flag also becomes the OR of every thread's, through the same barrier and loop.
+// block_best2: two at once behind the one barrier, sv / si two rows of NW.
+template <int NW>
+__device__ __forceinline__ void block_best(Best& b, float* sv, int* si, int* flag = nullptr, int* sf = nullptr) {
+  wave_best(b);
+  if (flag) *flag = __any(*flag);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    sv[w] = b.v;
+    si[w] = b.i;
+    if (flag) sf[w] = *flag;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 1; k < NW; ++k) {
+      best_of(b, sv[k], si[k]);
+      if (flag) *flag |= sf[k];
+    }
+}
+template <int NW>
+__device__ __forceinline__ void block_best2(Best& a, Best& b, float (*sv)[NW], int (*si)[NW]) {
+  wave_best(a);
+  wave_best(b);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    sv[0][w] = a.v; si[0][w] = a.i;
+    sv[1][w] = b.v; si[1][w] = b.i;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < NW; ++k) {
+      best_of(a, sv[0][k], si[0][k]);
+      best_of(b, sv[1][k], si[1][k]);
+    }
+  }
 }
 
 // ---------------------------------------------------------------- activations

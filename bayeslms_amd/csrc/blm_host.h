@@ -30,6 +30,23 @@ inline bool extents_ok(std::initializer_list<long> dims) {
   }
   return true;
 }
+// every pointer given is 16-byte aligned; a null pointer (an operand the call leaves out) counts as aligned
+template <class... P>
+inline bool aligned16(const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ... | uintptr_t(0)) & 15) == 0;
+}
+// The bytes [first, last) that an (M, V) float matrix at row stride ld touches (M >= 1), and the two questions the entry points
+// ask of them: do two matrices share a byte, and may a result d be written where an operand z is read -- only over z itself,
+// element for element, or clear of it.
+struct Span {
+  uintptr_t first, last;
+};
+inline Span span_of(const void* p, long M, long ld, long V) {
+  const uintptr_t first = reinterpret_cast<uintptr_t>(p);
+  return {first, first + ((uintptr_t)(M - 1) * (uintptr_t)ld + (uintptr_t)V) * 4};
+}
+inline bool overlaps(const Span& a, const Span& b) { return a.first < b.last && b.first < a.last; }
+inline bool in_place_or_disjoint(const Span& d, const Span& z) { return d.first == z.first || !overlaps(d, z); }
 // blm_colsum2 with a factor on the sums (out and, if given, out2 alike): the guarded-loader route of blm_gemm's colsum_a, whose
 // sums carry the call's alpha -- the only caller with scale != 1, and it passes no out2
 int colsum_scaled(const float* x, int64_t ld, float* out, float* out2, int M, int N, int accumulate, float scale, void* stream);

@@ -245,22 +245,13 @@ __global__ __launch_bounds__(kThreads) void log_softmax_rows_kernel(const float*
   for (int c = threadIdx.x; c < V; c += kThreads) orow[c] = xr[c] - lse;
 }
 
-// Lowest index wins a tie; a NaN score never wins.
-__device__ __forceinline__ void best_of(float& v, int& i, float v2, int i2) {
-  if (v2 > v || (v2 == v && i2 < i) || (v != v && v2 == v2)) {
-    v = v2;
-    i = i2;
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void sample_rows_kernel(const float* x, int64_t ldx, int V, float inv_t, int greedy,
                                                                blm_rng rng, int64_t* out) {
   __shared__ float sv[kThreads / 64];
   __shared__ int si[kThreads / 64];
   const int row = blockIdx.x;
   const float* xr = x + (size_t)row * ldx;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
+  blm::Best b = {-INFINITY, blm::kNone};
   for (int c = threadIdx.x; c < V; c += kThreads) {
     float s = xr[c];
     if (!greedy) {
@@ -269,24 +260,10 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(const float* x, i
       const float uu = ((float)(u.x >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0, 1)
       s = s * inv_t - logf(-logf(uu));                                         // Gumbel-max
     }
-    best_of(bv, bi, s, c);
+    blm::best_of(b, s, c);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(bv, o, 64);
-    const int i2 = __shfl_xor(bi, o, 64);
-    best_of(bv, bi, v2, i2);
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[w] = bv;
-    si[w] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < kThreads / 64; ++k) best_of(bv, bi, sv[k], si[k]);
-    out[row] = bi == 0x7fffffff ? 0 : bi;
-  }
+  blm::block_best<kThreads / 64>(b, sv, si);
+  if (threadIdx.x == 0) out[row] = b.i == blm::kNone ? 0 : b.i;
 }
 
 int chunks_of(int ctx_max) { return (ctx_max + kCh - 1) / kCh; }

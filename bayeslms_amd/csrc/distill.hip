@@ -12,51 +12,12 @@
 // blm_ce_soft_temp_fwd_bwd / blm_ce_soft_topk_temp_fwd_bwd (further below): both with a softmax temperature on the soft term, in
 // kernels of their own; the kernels up to there are what temperature 1 runs and are not touched by them.
 #include <cmath>
+#include <type_traits>
 
 #include "blm_device.h"
 #include "blm_host.h"
 
 namespace blm {
-
-// Block reductions of a 1024-thread workgroup (16 waves) that cost one register per value: the 16 per-wave partials are read
-// back one per lane and folded by a butterfly (blm_device.h's block_sum<16> reads all 16 into registers of every lane -- three
-// sums are 48 registers, which the register-resident rows below do not leave).  Fixed order: the same bits from every run.
-__device__ __forceinline__ float fold16_sum(float r) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
-  return r;
-}
-__device__ __forceinline__ float row_max(float v, float* red) {
-  v = wave_max(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float r = red[lane & 15];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) r = fmaxf(r, __shfl_xor(r, o, 64));
-  return r;
-}
-__device__ __forceinline__ float row_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  return fold16_sum(red[lane & 15]);
-}
-__device__ __forceinline__ void row_sum3(float& a, float& b, float& c, float (*red)[16]) {  // three sums behind one barrier pair
-  a = wave_sum(a);
-  b = wave_sum(b);
-  c = wave_sum(c);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; }
-  __syncthreads();
-  a = fold16_sum(red[0][lane & 15]);
-  b = fold16_sum(red[1][lane & 15]);
-  c = fold16_sum(red[2][lane & 15]);
-}
 
 struct SoftCoef {
   float p, q, t;  // gradient = p * softmax - q * teacher - t * onehot
@@ -119,14 +80,15 @@ __global__ __launch_bounds__(1024) void ce_soft_row_kernel(const float* logits, 
     qz += ((q0 > 0.f ? q0 * v[i].x : 0.f) + (q1 > 0.f ? q1 * v[i].y : 0.f)) +
           ((q2 > 0.f ? q2 * v[i].z : 0.f) + (q3 > 0.f ? q3 * v[i].w : 0.f));
   }
-  const float M_ = row_max(m, red[0]);
+  float M_ = m;
+  row_fold<ROW_MAX>(red, M_);
   float l = __expf(ze - M_);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     if (!(t0 + 4096u * i + 3 < Vu)) continue;
     l += __expf(v[i].x - M_) + __expf(v[i].y - M_) + __expf(v[i].z - M_) + __expf(v[i].w - M_);
   }
-  row_sum3(l, Q, qz, red);
+  row_fold<ROW_SUM, ROW_EACH>(red, l, Q, qz);
   const float lse = M_ + __logf(l);
   const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
   float* d = dlogits ? dlogits + row * ld : nullptr;
@@ -148,7 +110,7 @@ __global__ __launch_bounds__(1024) void ce_soft_row_kernel(const float* logits, 
       *reinterpret_cast<float4*>(d + j) = g;
     }
   }
-  k = row_sum(k, red[0]);
+  row_fold<ROW_SUM>(red, k);
   if (threadIdx.x == 0) {
     const float n = valid ? lse - xt : 0.f, s = Q * lse - qz;
     loss[row] = (1.f - lambda) * n + lambda * s;
@@ -192,10 +154,11 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_soft_kernel(const float* logits, 
   }
   const long t = tgt[row];
   const bool valid = t >= 0 && t < V;
-  const float xt = valid ? x[t] : 0.f;  // read before any in-place gradient write (block_max has barriers)
-  const float M_ = row_max(m, red[0]);
+  const float xt = valid ? x[t] : 0.f;  // read before any in-place gradient write (the reductions below have barriers)
+  float M_ = m;
+  row_fold<ROW_MAX>(red, M_);
   l = m == -INFINITY ? 0.f : l * __expf(m - M_);
-  row_sum3(l, Q, qz, red);
+  row_fold<ROW_SUM, ROW_EACH>(red, l, Q, qz);
   const float lse = M_ + __logf(l);
   const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
   float* d = dlogits ? dlogits + row * ld : nullptr;
@@ -217,7 +180,7 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_soft_kernel(const float* logits, 
     k += soft_elem(x[j], y[j], lse, c, g);
     if (d) d[j] = (valid && j == t) ? g - c.t : g;
   }
-  k = row_sum(k, red[0]);
+  row_fold<ROW_SUM>(red, k);
   if (threadIdx.x == 0) {
     const float n = valid ? lse - xt : 0.f, s = Q * lse - qz;
     loss[row] = (1.f - lambda) * n + lambda * s;
@@ -300,7 +263,8 @@ __global__ __launch_bounds__(1024) void ce_topk_row_kernel(const float* logits, 
     if (!(t0 + 4096u * i + 3 < Vu)) continue;
     m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
   }
-  const float M_ = row_max(m, red[0]);
+  float M_ = m;
+  row_fold<ROW_MAX>(red, M_);
   float l = __expf(ze - M_);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -308,10 +272,11 @@ __global__ __launch_bounds__(1024) void ce_topk_row_kernel(const float* logits, 
     l += __expf(v[i].x - M_) + __expf(v[i].y - M_) + __expf(v[i].z - M_) + __expf(v[i].w - M_);
   }
   float Q = e.q, qz = e.q > 0.f ? e.q * e.z : 0.f;
-  row_sum3(l, Q, qz, red);
+  row_fold<ROW_SUM, ROW_EACH>(red, l, Q, qz);
   const float lse = M_ + __logf(l);
   const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
-  const float k = row_sum(topk_kl(e, lse), red[0]);
+  float k = topk_kl(e, lse);
+  row_fold<ROW_SUM>(red, k);
   if (dlogits) {
     float* d = dlogits + row * ld;
     if (extra) d[je] = c.p * __expf(ze - lse) - (tu == je ? c.t : 0.f);
@@ -358,15 +323,17 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_topk_kernel(const float* logits, 
   const TopkEntry e = topk_entry(ids + row * ldk, logq + row * ldk, x, K, V);
   const long t = tgt[row];
   const bool valid = t >= 0 && t < V;
-  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (row_max has barriers)
+  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (the reductions below have barriers)
   const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;
-  const float M_ = row_max(m, red[0]);
+  float M_ = m;
+  row_fold<ROW_MAX>(red, M_);
   l = m == -INFINITY ? 0.f : l * __expf(m - M_);
   float Q = e.q, qz = e.q > 0.f ? e.q * e.z : 0.f;
-  row_sum3(l, Q, qz, red);
+  row_fold<ROW_SUM, ROW_EACH>(red, l, Q, qz);
   const float lse = M_ + __logf(l);
   const SoftCoef c = soft_coef(lambda, valid, Q, gscale);
-  const float k = row_sum(topk_kl(e, lse), red[0]);
+  float k = topk_kl(e, lse);
+  row_fold<ROW_SUM>(red, k);
   if (dlogits) {
     float* d = dlogits + row * ld;
     for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {  // each element read and written by the same thread
@@ -389,47 +356,13 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_topk_kernel(const float* logits, 
 // ---- distillation temperature: blm_ce_soft_temp_fwd_bwd / blm_ce_soft_topk_temp_fwd_bwd (definitions: include/bayeslm.h) ----
 // The hard term stays at temperature 1, the soft term compares softmax(beta z) with the teacher raised to beta and renormalised
 // over its live entries, so one read of a row has to give both softmax(z) and softmax(beta z).  Three rounds per row:
-//   1. max z and max live l                                          (row_max2: one barrier pair)
+//   1. max z and max live l                                          (one row_fold: one barrier pair)
 //   2. sum exp(z - m), s_b = sum exp(beta (z - m)), Z = sum e_v, A = sum e_v (z_v - m),  e_v = exp(beta (l_v - ml))
-//                                                                    (row_sum4: one barrier pair)
+//                                                                    (one row_fold: one barrier pair)
 //   3. the KL terms and the gradient, every exponent formed from the max-shifted values: log p = (z - m) - log sum,
 //      log p~ = beta (z - m) - log s_b, log q~ = beta (l - ml) - log Z
 // soft = log s_b - beta A / Z, which is lse_b - beta sum q~ z with the beta m of both terms cancelled before it is rounded.
 // The untempered kernels above are not touched: temperature 1 launches them.
-__device__ __forceinline__ float uniform(float v) {  // a value every lane holds alike (a row reduction's result): one SGPR, no VGPR
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ void row_max2(float& a, float& b, float (*red)[16]) {  // two maxima behind one barrier pair
-  a = wave_max(a);
-  b = wave_max(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[0][w] = a; red[1][w] = b; }
-  __syncthreads();
-  a = red[0][lane & 15];
-  b = red[1][lane & 15];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    a = fmaxf(a, __shfl_xor(a, o, 64));
-    b = fmaxf(b, __shfl_xor(b, o, 64));
-  }
-  a = uniform(a);
-  b = uniform(b);
-}
-__device__ __forceinline__ void row_sum4(float& a, float& b, float& c, float& d, float (*red)[16]) {  // four sums, one barrier pair
-  a = wave_sum(a);
-  b = wave_sum(b);
-  c = wave_sum(c);
-  d = wave_sum(d);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; red[3][w] = d; }
-  __syncthreads();
-  a = uniform(fold16_sum(red[0][lane & 15]));
-  b = uniform(fold16_sum(red[1][lane & 15]));
-  c = uniform(fold16_sum(red[2][lane & 15]));
-  d = uniform(fold16_sum(red[3][lane & 15]));
-}
 
 struct TempRow {  // a row's constants of round 3, the same in every lane
   float beta, m, logl, logs, ml, logZ;  // log p = (z - m) - logl,  log p~ = beta (z - m) - logs,  log q~ = beta (l - ml) - logZ
@@ -521,7 +454,7 @@ __global__ __launch_bounds__(1024) void ce_soft_temp_row_kernel(const float* log
     m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
     ml = fmaxf(ml, fmaxf(fmaxf(u[i].x, u[i].y), fmaxf(u[i].z, u[i].w)));
   }
-  row_max2(m, ml, red);
+  row_fold<ROW_MAX, ROW_UNIFORM>(red, m, ml);
   const float mls = ml > -INFINITY ? ml : 0.f;
   float sl = 0.f, sb = 0.f, Z = 0.f, A = 0.f;
   temp_acc(ze, le, beta, m, mls, sl, sb, Z, A);  // ze = le = -inf without an extra column: four zeros
@@ -533,7 +466,7 @@ __global__ __launch_bounds__(1024) void ce_soft_temp_row_kernel(const float* log
     temp_acc(v[i].z, u[i].z, beta, m, mls, sl, sb, Z, A);
     temp_acc(v[i].w, u[i].w, beta, m, mls, sl, sb, Z, A);
   }
-  row_sum4(sl, sb, Z, A, red);
+  row_fold<ROW_SUM, ROW_UNIFORM | ROW_EACH>(red, sl, sb, Z, A);
   const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
   float* d = dlogits ? dlogits + row * ld : nullptr;
   float ge;
@@ -554,7 +487,7 @@ __global__ __launch_bounds__(1024) void ce_soft_temp_row_kernel(const float* log
       *reinterpret_cast<float4*>(d + j) = g;
     }
   }
-  k = row_sum(k, red[0]);
+  row_fold<ROW_SUM>(red, k);
   if (threadIdx.x == 0) temp_finish(row, r, xt, k, lambda, scale, loss, nll, soft, kl, lse_out);
 }
 
@@ -585,7 +518,7 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_soft_temp_kernel(const float* log
   const long t = tgt[row];
   const bool valid = t >= 0 && t < V;
   const float xt = valid ? x[t] : 0.f;  // read before any in-place gradient write
-  row_max2(m, ml, red);
+  row_fold<ROW_MAX, ROW_UNIFORM>(red, m, ml);
   const float mls = ml > -INFINITY ? ml : 0.f;
   float sl = 0.f, sb = 0.f, Z = 0.f, A = 0.f;
   for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {
@@ -596,7 +529,7 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_soft_temp_kernel(const float* log
     temp_acc(v.w, u.w, beta, m, mls, sl, sb, Z, A);
   }
   for (int j = V4 + threadIdx.x; j < V; j += SOFT_TPB) temp_acc(x[j], y[j], beta, m, mls, sl, sb, Z, A);
-  row_sum4(sl, sb, Z, A, red);
+  row_fold<ROW_SUM, ROW_UNIFORM | ROW_EACH>(red, sl, sb, Z, A);
   const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
   float* d = dlogits ? dlogits + row * ld : nullptr;
   float k = 0.f;
@@ -616,7 +549,7 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_soft_temp_kernel(const float* log
     k += temp_elem(x[j], y[j], r, g);
     if (d) d[j] = (valid && j == t) ? g - r.hard : g;
   }
-  k = row_sum(k, red[0]);
+  row_fold<ROW_SUM>(red, k);
   if (threadIdx.x == 0) temp_finish(row, r, xt, k, lambda, scale, loss, nll, soft, kl, lse_out);
 }
 
@@ -677,7 +610,7 @@ __global__ __launch_bounds__(1024) void ce_topk_temp_row_kernel(const float* log
     if (!(t0 + 4096u * i + 3 < Vu)) continue;
     m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
   }
-  row_max2(m, ml, red);
+  row_fold<ROW_MAX, ROW_UNIFORM>(red, m, ml);
   const float mls = ml > -INFINITY ? ml : 0.f;
   float sl = __expf(ze - m), sb = __expf(beta * (ze - m));
 #pragma unroll
@@ -687,10 +620,10 @@ __global__ __launch_bounds__(1024) void ce_topk_temp_row_kernel(const float* log
     sb += __expf(beta * (v[i].x - m)) + __expf(beta * (v[i].y - m)) + __expf(beta * (v[i].z - m)) + __expf(beta * (v[i].w - m));
   }
   float Z = __expf(beta * (e.l - mls)), A = Z > 0.f ? Z * (e.z - m) : 0.f;
-  row_sum4(sl, sb, Z, A, red);
+  row_fold<ROW_SUM, ROW_UNIFORM | ROW_EACH>(red, sl, sb, Z, A);
   const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
-  float gu;
-  const float k = row_sum(temp_elem(e.z, e.l, r, gu), red[0]);
+  float gu, k = temp_elem(e.z, e.l, r, gu);
+  row_fold<ROW_SUM>(red, k);
   if (dlogits) {
     float* d = dlogits + row * ld;
     if (extra) d[je] = temp_grad(ze, r) - (tu == je ? r.hard : 0.f);
@@ -741,18 +674,18 @@ __global__ __launch_bounds__(SOFT_TPB) void ce_topk_temp_kernel(const float* log
   const TempEntry e = temp_entry(ids + row * ldk, logq + row * ldk, x, K, V);
   const long t = tgt[row];
   const bool valid = t >= 0 && t < V;
-  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (row_max2 has barriers)
+  const float xt = valid ? x[t] : 0.f;  // as e.z: read before any in-place gradient write (the reductions below have barriers)
   const unsigned tu = valid ? (unsigned)t : 0xFFFFFFFFu;
   float m = mt, ml = e.l;
-  row_max2(m, ml, red);
+  row_fold<ROW_MAX, ROW_UNIFORM>(red, m, ml);
   const float mls = ml > -INFINITY ? ml : 0.f;
   sl = mt == -INFINITY ? 0.f : sl * __expf(mt - m);
   sb = mt == -INFINITY ? 0.f : sb * __expf(beta * (mt - m));
   float Z = __expf(beta * (e.l - mls)), A = Z > 0.f ? Z * (e.z - m) : 0.f;
-  row_sum4(sl, sb, Z, A, red);
+  row_fold<ROW_SUM, ROW_UNIFORM | ROW_EACH>(red, sl, sb, Z, A);
   const TempRow r = temp_row(beta, m, ml, sl, sb, Z, A, lambda, scale, valid, gscale);
-  float gu;
-  const float k = row_sum(temp_elem(e.z, e.l, r, gu), red[0]);
+  float gu, k = temp_elem(e.z, e.l, r, gu);
+  row_fold<ROW_SUM>(red, k);
   if (dlogits) {
     float* d = dlogits + row * ld;
     for (int j = threadIdx.x * 4; j < V4; j += SOFT_TPB * 4) {  // each element read and written by the same thread
@@ -784,7 +717,15 @@ __global__ __launch_bounds__(1024) void soft_sum_kernel(const float* __restrict_
 }  // namespace blm
 
 using namespace blm;
-#define ST static_cast<hipStream_t>(stream)
+
+// The gradient may be written over the logits it is the gradient of, element for element, and over nothing else read here.
+static int dlogits_args(const char* fn, const Span& d, const Span& z, const Span& q, const Span* ids) {
+  if (ids && overlaps(d, *ids)) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps ids", fn);
+  if (overlaps(d, q)) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logq", fn);
+  if (!in_place_or_disjoint(d, z))
+    return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logits without being logits itself (in place means dlogits == logits)", fn);
+  return BLM_OK;
+}
 
 // The argument checks of the dense entry points, under the name `fn` of the one that was called -> BLM_OK to go on.
 static int soft_args(const char* fn, const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
@@ -795,15 +736,8 @@ static int soft_args(const char* fn, const float* logits, int64_t ld, const floa
     return blm_fail(BLM_ERR_INVALID, "%s: row strides ld = %lld, ldq = %lld must be >= V = %d (and M x stride an addressable extent)", fn,
                     (long long)ld, (long long)ldq, V);
   if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "%s: lambda = %g outside [0, 1]", fn, (double)lambda);
-  if (M == 0) return BLM_OK;
-  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), q0 = reinterpret_cast<uintptr_t>(logq), d0 = reinterpret_cast<uintptr_t>(dlogits);
-  if (dlogits) {  // the gradient may be written over the logits it is the gradient of, element for element, and over nothing else read here
-    const uintptr_t zn = ((uintptr_t)(M - 1) * (uintptr_t)ld + (uintptr_t)V) * 4, qn = ((uintptr_t)(M - 1) * (uintptr_t)ldq + (uintptr_t)V) * 4;
-    if (d0 < q0 + qn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logq", fn);
-    if (d0 != z0 && d0 < z0 + zn && z0 < d0 + zn)
-      return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logits without being logits itself (in place means dlogits == logits)", fn);
-  }
-  return BLM_OK;
+  if (M == 0 || !dlogits) return BLM_OK;
+  return dlogits_args(fn, span_of(dlogits, M, ld, V), span_of(logits, M, ld, V), span_of(logq, M, ldq, V), nullptr);
 }
 // ... and what the tempered entry points refuse beside: beta = 1 / T and the factor on the soft term
 static int temp_args(const char* fn, float beta, float soft_scale) {
@@ -812,56 +746,6 @@ static int temp_args(const char* fn, float beta, float soft_scale) {
     return blm_fail(BLM_ERR_INVALID, "%s: soft_scale = %g: a finite factor >= 0 expected", fn, (double)soft_scale);
   return BLM_OK;
 }
-
-extern "C" int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
-                                   float* loss, float* nll, float* soft, float* kl, float* lse, float* loss_sum, float* dlogits,
-                                   float grad_scale, int M, int V, void* stream) {
-  if (const int bad = soft_args("blm_ce_soft_fwd_bwd", logits, ld, logq, ldq, tgt, lambda, loss, dlogits, M, V)) return bad;
-  if (M == 0) return BLM_OK;
-  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), q0 = reinterpret_cast<uintptr_t>(logq), d0 = reinterpret_cast<uintptr_t>(dlogits);
-  const bool vec = ((ld & 3) == 0) && ((ldq & 3) == 0) && (((z0 | q0 | d0) & 15) == 0);
-  if (vec && V >= 4 && V <= 4096 * 3)
-    hipLaunchKernelGGL(ce_soft_row_kernel<3>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
-                       lse, dlogits, grad_scale, V);
-  else if (vec && V <= 4096 * 9)
-    hipLaunchKernelGGL(ce_soft_row_kernel<9>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
-                       lse, dlogits, grad_scale, V);
-  else
-    hipLaunchKernelGGL(ce_soft_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft, kl,
-                       lse, dlogits, grad_scale, V, vec ? 1 : 0);
-  BLM_HIP(hipGetLastError());
-  if (loss_sum) {
-    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
-    BLM_HIP(hipGetLastError());
-  }
-  return BLM_OK;
-}
-
-extern "C" int blm_ce_soft_temp_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
-                                        float beta, float soft_scale, float* loss, float* nll, float* soft, float* kl, float* lse,
-                                        float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream) {
-  if (const int bad = soft_args("blm_ce_soft_temp_fwd_bwd", logits, ld, logq, ldq, tgt, lambda, loss, dlogits, M, V)) return bad;
-  if (const int bad = temp_args("blm_ce_soft_temp_fwd_bwd", beta, soft_scale)) return bad;
-  if (M == 0) return BLM_OK;
-  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), q0 = reinterpret_cast<uintptr_t>(logq), d0 = reinterpret_cast<uintptr_t>(dlogits);
-  const bool vec = ((ld & 3) == 0) && ((ldq & 3) == 0) && (((z0 | q0 | d0) & 15) == 0);  // the forms of blm_ce_soft_fwd_bwd, by its conditions
-  if (vec && V >= 4 && V <= 4096 * 3)
-    hipLaunchKernelGGL(ce_soft_temp_row_kernel<3>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, beta,
-                       soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
-  else if (vec && V <= 4096 * 9)
-    hipLaunchKernelGGL(ce_soft_temp_row_kernel<9>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, beta,
-                       soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
-  else
-    hipLaunchKernelGGL(ce_soft_temp_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, logq, (long)ldq, tgt, lambda, beta, soft_scale,
-                       loss, nll, soft, kl, lse, dlogits, grad_scale, V, vec ? 1 : 0);
-  BLM_HIP(hipGetLastError());
-  if (loss_sum) {
-    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
-    BLM_HIP(hipGetLastError());
-  }
-  return BLM_OK;
-}
-
 // The argument checks of the top-k entry points, under the name `fn` of the one that was called -> BLM_OK to go on.
 static int topk_args(const char* fn, const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
                      const int64_t* tgt, float lambda, const float* loss, const float* dlogits, int M, int V) {
@@ -874,17 +758,71 @@ static int topk_args(const char* fn, const float* logits, int64_t ld, const int3
   if (ldk < K || !extents_ok({M, ldk}))
     return blm_fail(BLM_ERR_INVALID, "%s: row stride ldk = %lld must be >= K = %d (and M x ldk an addressable extent)", fn, (long long)ldk, K);
   if (!(lambda >= 0.f && lambda <= 1.f)) return blm_fail(BLM_ERR_INVALID, "%s: lambda = %g outside [0, 1]", fn, (double)lambda);
-  if (M == 0) return BLM_OK;
-  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), d0 = reinterpret_cast<uintptr_t>(dlogits);
-  if (dlogits) {  // the gradient may be written over the logits it is the gradient of, element for element, and over nothing else read here
-    const uintptr_t zn = ((uintptr_t)(M - 1) * (uintptr_t)ld + (uintptr_t)V) * 4, kn = ((uintptr_t)(M - 1) * (uintptr_t)ldk + (uintptr_t)K) * 4;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(ids), q0 = reinterpret_cast<uintptr_t>(logq);
-    if (d0 < i0 + kn && i0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps ids", fn);
-    if (d0 < q0 + kn && q0 < d0 + zn) return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logq", fn);
-    if (d0 != z0 && d0 < z0 + zn && z0 < d0 + zn)
-      return blm_fail(BLM_ERR_INVALID, "%s: dlogits overlaps logits without being logits itself (in place means dlogits == logits)", fn);
+  if (M == 0 || !dlogits) return BLM_OK;
+  const Span i = span_of(ids, M, ldk, K);  // 4-byte ids
+  return dlogits_args(fn, span_of(dlogits, M, ld, V), span_of(logits, M, ld, V), span_of(logq, M, ldk, K), &i);
+}
+
+// The launch of all four entry points.  `vec`: every matrix the kernels read or write by float4 (the logits, the gradient and,
+// DENSE, the teacher row) is 16-byte aligned at a row stride that is a multiple of 4.  Then the row-held form at the first of
+// NV = 3, 9 and -- top-k only, which holds one row and not two -- 16 quads per thread that covers V, else the sweep; the dense
+// entry points' second rung has never asked for V >= 4.  row(nv) and sweep(vec) launch the entry point's own kernels.  Last the
+// fixed-order loss_sum, if asked for.
+template <int NV>
+using nv_c = std::integral_constant<int, NV>;
+template <bool DENSE, class Row, class Sweep>
+static int soft_launch(const float* logits, int64_t ld, const float* logq, int64_t ldq, const float* dlogits, int V, const float* loss,
+                       int M, float* loss_sum, hipStream_t st, Row row, Sweep sweep) {
+  const bool vec = (ld & 3) == 0 && (!DENSE || ((ldq & 3) == 0 && aligned16(logq))) && aligned16(logits, dlogits);
+  const bool quad = vec && V >= 4;
+  if (quad && V <= 4096 * 3) row(nv_c<3>{});
+  else if ((DENSE ? vec : quad) && V <= 4096 * 9) row(nv_c<9>{});
+  else if (!DENSE && quad && V <= 4096 * 16) {
+    if constexpr (!DENSE) row(nv_c<16>{});
+  } else sweep(vec ? 1 : 0);
+  BLM_HIP(hipGetLastError());
+  if (loss_sum) {
+    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, st, loss, (long)M, loss_sum);
+    BLM_HIP(hipGetLastError());
   }
   return BLM_OK;
+}
+
+extern "C" int blm_ce_soft_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                                   float* loss, float* nll, float* soft, float* kl, float* lse, float* loss_sum, float* dlogits,
+                                   float grad_scale, int M, int V, void* stream) {
+  if (const int bad = soft_args("blm_ce_soft_fwd_bwd", logits, ld, logq, ldq, tgt, lambda, loss, dlogits, M, V)) return bad;
+  if (M == 0) return BLM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return soft_launch<true>(
+      logits, ld, logq, ldq, dlogits, V, loss, M, loss_sum, st,
+      [&](auto nv) {
+        hipLaunchKernelGGL(ce_soft_row_kernel<decltype(nv)::value>, dim3(M), dim3(1024), 0, st, logits, (long)ld, logq, (long)ldq, tgt,
+                           lambda, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
+      },
+      [&](int vec) {
+        hipLaunchKernelGGL(ce_soft_kernel, dim3(M), dim3(SOFT_TPB), 0, st, logits, (long)ld, logq, (long)ldq, tgt, lambda, loss, nll, soft,
+                           kl, lse, dlogits, grad_scale, V, vec);
+      });
+}
+
+extern "C" int blm_ce_soft_temp_fwd_bwd(const float* logits, int64_t ld, const float* logq, int64_t ldq, const int64_t* tgt, float lambda,
+                                        float beta, float soft_scale, float* loss, float* nll, float* soft, float* kl, float* lse,
+                                        float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream) {
+  if (const int bad = soft_args("blm_ce_soft_temp_fwd_bwd", logits, ld, logq, ldq, tgt, lambda, loss, dlogits, M, V)) return bad;
+  if (const int bad = temp_args("blm_ce_soft_temp_fwd_bwd", beta, soft_scale)) return bad;
+  if (M == 0) return BLM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return soft_launch<true>(
+      logits, ld, logq, ldq, dlogits, V, loss, M, loss_sum, st,
+      [&](auto nv) {
+        hipLaunchKernelGGL(ce_soft_temp_row_kernel<decltype(nv)::value>, dim3(M), dim3(1024), 0, st, logits, (long)ld, logq, (long)ldq, tgt,
+                           lambda, beta, soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
+      },
+      [&](int vec) {
+        hipLaunchKernelGGL(ce_soft_temp_kernel, dim3(M), dim3(SOFT_TPB), 0, st, logits, (long)ld, logq, (long)ldq, tgt, lambda, beta,
+                           soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V, vec);
+      });
 }
 
 extern "C" int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
@@ -892,24 +830,17 @@ extern "C" int blm_ce_soft_topk_fwd_bwd(const float* logits, int64_t ld, const i
                                         float* loss_sum, float* dlogits, float grad_scale, int M, int V, void* stream) {
   if (const int bad = topk_args("blm_ce_soft_topk_fwd_bwd", logits, ld, ids, logq, ldk, K, tgt, lambda, loss, dlogits, M, V)) return bad;
   if (M == 0) return BLM_OK;
-  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), d0 = reinterpret_cast<uintptr_t>(dlogits);
-  const bool vec = ((ld & 3) == 0) && (((z0 | d0) & 15) == 0);
-#define TOPK_ROW(NV)                                                                                                                  \
-  hipLaunchKernelGGL(ce_topk_row_kernel<NV>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, loss, \
-                     nll, soft, kl, lse, dlogits, grad_scale, V)
-  if (vec && V >= 4 && V <= 4096 * 3) TOPK_ROW(3);
-  else if (vec && V >= 4 && V <= 4096 * 9) TOPK_ROW(9);
-  else if (vec && V >= 4 && V <= 4096 * 16) TOPK_ROW(16);
-  else
-    hipLaunchKernelGGL(ce_topk_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, loss, nll,
-                       soft, kl, lse, dlogits, grad_scale, V, vec ? 1 : 0);
-#undef TOPK_ROW
-  BLM_HIP(hipGetLastError());
-  if (loss_sum) {
-    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
-    BLM_HIP(hipGetLastError());
-  }
-  return BLM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return soft_launch<false>(
+      logits, ld, nullptr, 0, dlogits, V, loss, M, loss_sum, st,
+      [&](auto nv) {
+        hipLaunchKernelGGL(ce_topk_row_kernel<decltype(nv)::value>, dim3(M), dim3(1024), 0, st, logits, (long)ld, ids, logq, (long)ldk, K,
+                           tgt, lambda, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
+      },
+      [&](int vec) {
+        hipLaunchKernelGGL(ce_topk_kernel, dim3(M), dim3(SOFT_TPB), 0, st, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, loss,
+                           nll, soft, kl, lse, dlogits, grad_scale, V, vec);
+      });
 }
 
 extern "C" int blm_ce_soft_topk_temp_fwd_bwd(const float* logits, int64_t ld, const int32_t* ids, const float* logq, int64_t ldk, int K,
@@ -919,22 +850,15 @@ extern "C" int blm_ce_soft_topk_temp_fwd_bwd(const float* logits, int64_t ld, co
   if (const int bad = topk_args("blm_ce_soft_topk_temp_fwd_bwd", logits, ld, ids, logq, ldk, K, tgt, lambda, loss, dlogits, M, V)) return bad;
   if (const int bad = temp_args("blm_ce_soft_topk_temp_fwd_bwd", beta, soft_scale)) return bad;
   if (M == 0) return BLM_OK;
-  const uintptr_t z0 = reinterpret_cast<uintptr_t>(logits), d0 = reinterpret_cast<uintptr_t>(dlogits);
-  const bool vec = ((ld & 3) == 0) && (((z0 | d0) & 15) == 0);  // the forms of blm_ce_soft_topk_fwd_bwd, by its conditions
-#define TOPK_TEMP_ROW(NV)                                                                                                                  \
-  hipLaunchKernelGGL(ce_topk_temp_row_kernel<NV>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, beta, \
-                     soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V)
-  if (vec && V >= 4 && V <= 4096 * 3) TOPK_TEMP_ROW(3);
-  else if (vec && V >= 4 && V <= 4096 * 9) TOPK_TEMP_ROW(9);
-  else if (vec && V >= 4 && V <= 4096 * 16) TOPK_TEMP_ROW(16);
-  else
-    hipLaunchKernelGGL(ce_topk_temp_kernel, dim3(M), dim3(SOFT_TPB), 0, ST, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda, beta,
-                       soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V, vec ? 1 : 0);
-#undef TOPK_TEMP_ROW
-  BLM_HIP(hipGetLastError());
-  if (loss_sum) {
-    hipLaunchKernelGGL(soft_sum_kernel, dim3(1), dim3(1024), 0, ST, loss, (long)M, loss_sum);
-    BLM_HIP(hipGetLastError());
-  }
-  return BLM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return soft_launch<false>(
+      logits, ld, nullptr, 0, dlogits, V, loss, M, loss_sum, st,
+      [&](auto nv) {
+        hipLaunchKernelGGL(ce_topk_temp_row_kernel<decltype(nv)::value>, dim3(M), dim3(1024), 0, st, logits, (long)ld, ids, logq, (long)ldk,
+                           K, tgt, lambda, beta, soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V);
+      },
+      [&](int vec) {
+        hipLaunchKernelGGL(ce_topk_temp_kernel, dim3(M), dim3(SOFT_TPB), 0, st, logits, (long)ld, ids, logq, (long)ldk, K, tgt, lambda,
+                           beta, soft_scale, loss, nll, soft, kl, lse, dlogits, grad_scale, V, vec);
+      });
 }

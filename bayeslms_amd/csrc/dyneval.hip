@@ -26,11 +26,6 @@ inline int dyn_grid(long n, int cap) {
   return (int)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
 }
 
-__device__ __forceinline__ bool aligned16(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
-}
-
 __global__ __launch_bounds__(DYN_TPB) void dyneval_accum_kernel(float* __restrict__ ms, const float* __restrict__ g, long n) {
   const long n4 = aligned16(ms, g) ? (n >> 2) : 0;
   const long stride = (long)gridDim.x * DYN_TPB, first = (long)blockIdx.x * DYN_TPB + threadIdx.x;

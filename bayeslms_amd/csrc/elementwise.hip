@@ -855,7 +855,7 @@ extern "C" int blm_embed_fwd(const int64_t* ids, const float* enc, const float* 
   if ((long)T * B == 0) return BLM_OK;
   const long rows = (long)T * B;
   // a view at a storage offset of 1-3 floats has D % 4 == 0 and misaligned rows: the scalar loop (include/bayeslm.h)
-  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(enc) | reinterpret_cast<uintptr_t>(pe) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const bool vec = D % 4 == 0 && aligned16(enc, pe, out);
   hipLaunchKernelGGL(embed_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(TPB), 0, ST, ids, enc, pe, out, T, B, D,
                      (long)vocab, scale, make_key(p, rng, B, D, col_offset, global_cols), vec);
   BLM_HIP(hipGetLastError());
@@ -888,7 +888,7 @@ extern "C" int blm_dropout(const float* x, float* y, int rows, int B, int D, flo
   if (p > 0.f && !rng) return blm_fail(BLM_ERR_INVALID, "blm_dropout: dropout needs rng");
   const long n = (long)rows * B * D;
   if (n == 0) return BLM_OK;
-  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  const bool vec = D % 4 == 0 && aligned16(x, y);
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, x, y, (long)rows,
                      make_key(p, rng, B, D, col_offset, global_cols), vec);
   BLM_HIP(hipGetLastError());
@@ -903,7 +903,7 @@ extern "C" int blm_dropout_rows(const float* x, float* y, int rows, int row0, in
   if (n == 0) return BLM_OK;
   DropKey dk = make_key(p, rng, B, D, col_offset, global_cols);
   dk.row0 = row0;
-  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  const bool vec = D % 4 == 0 && aligned16(x, y);
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, x, y, (long)rows, dk, vec);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
@@ -930,8 +930,7 @@ extern "C" int blm_add_dropout_ln_fwd(const float* x, const float* y, const floa
   if (M == 0) return BLM_OK;
   const DropKey dk = make_key(p, rng, B, D, col_offset, global_cols);
   const dim3 grid((unsigned)((M + 3) / 4));
-  const bool al = (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out) |
-                     reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(s_out)) & 15) == 0);
+  const bool al = aligned16(x, y, out, gamma, beta, s_out);
 #define LN_FWD(V) hipLaunchKernelGGL(add_drop_ln_fwd_reg<V>, grid, dim3(TPB), 0, ST, x, y, gamma, beta, out, s_out, mean, rstd, M, eps_ln, dk)
   if (al && D == 256) LN_FWD(1);
   else if (al && D == 512) LN_FWD(2);
@@ -971,8 +970,7 @@ extern "C" int blm_add_dropout_ln_bwd(const float* dout, const float* s, const f
   const DropKey dk = make_key(p, rng, B, D, col_offset, global_cols);
   int nblk = (int)((M + 3) / 4);
   if (nblk > LN_BWD_BLOCKS) nblk = LN_BWD_BLOCKS;
-  const bool al = (((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(dx) |
-                     reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0);
+  const bool al = aligned16(dout, s, dx, gamma, dy);
   const size_t lds = (size_t)8 * D * sizeof(float);
 #define LN_BWD(V) hipLaunchKernelGGL(add_drop_ln_bwd_reg<V>, dim3(nblk), dim3(TPB), lds, ST, dout, s, gamma, mean, rstd, dx, dy, ws, M, dk)
   if (al && D == 256) LN_BWD(1);
@@ -1014,7 +1012,7 @@ extern "C" int blm_ce_fwd_bwd(const float* logits, int64_t ld, const int64_t* tg
                               float* dlogits, float grad_scale, int M, int V, void* stream) {
   if (!logits || !tgt || !nll || M < 0 || V <= 0 || ld < V) return blm_fail(BLM_ERR_INVALID, "blm_ce_fwd_bwd: bad arguments");
   if (M == 0) return BLM_OK;
-  const bool vec = ((ld & 3) == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0) && (!dlogits || (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0);
+  const bool vec = ((ld & 3) == 0) && aligned16(logits, dlogits);
   if (vec && V <= 4096 * 3)
     hipLaunchKernelGGL(ce_row_kernel<3>, dim3(M), dim3(1024), 0, ST, logits, (long)ld, tgt, nll, lse, dlogits, grad_scale, V);
   else if (vec && V <= 4096 * 9)

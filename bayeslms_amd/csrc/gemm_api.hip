@@ -15,7 +15,6 @@ extern template int launch_op<BLM_GEMM_TN, false>(const GemmP&, hipStream_t);
 
 using namespace blm;
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static int g_gemm_mode = -1;  // -1: not read yet (BLM_GEMM_MODE env: "bf16x3" or "1")
 
@@ -94,7 +93,7 @@ extern "C" int blm_gemm(const blm_gemm_args* a, void* stream) {
     // B source matrix is W: NT -> (N x K), NN -> (K x N)
     const int wrows = a->op == BLM_GEMM_NT ? a->N : a->K;
     p.vb_cols = a->op == BLM_GEMM_NT ? a->K : a->N;
-    if (p.vb_cols % 4 != 0 || !aligned16(a->var_b.lgstd) || (a->var_b.eps && !aligned16(a->var_b.eps)) || !p.b_vec)
+    if (p.vb_cols % 4 != 0 || !aligned16(a->var_b.lgstd, a->var_b.eps) || !p.b_vec)
       return blm_fail(BLM_ERR_INVALID, "blm_gemm: fused sampling needs cols % 4 == 0 and 16-byte aligned mu/lgstd/eps");
     if (a->var_b.row_lo < 0 || a->var_b.srows < 0 || a->var_b.row_lo + a->var_b.srows > wrows)
       return blm_fail(BLM_ERR_INVALID, "blm_gemm: var_b row window outside W");
@@ -217,7 +216,7 @@ extern "C" int blm_linear_nll(const float* x, int64_t ldx, const float* w, int64
   if (M < 0 || N <= 0 || K <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll: bad shape");
   if (M == 0) return BLM_OK;
   if (!x || !w || !tgt || !nll || !ws || ldx < K || ldw < K) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll: bad arguments");
-  if (N % 4 != 0 || !aligned16(ws) || (bias && !aligned16(bias)))
+  if (N % 4 != 0 || !aligned16(ws, bias))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll: needs N %% 4 == 0 and 16-byte aligned bias / workspace");
   return linear_nll_launch(x, ldx, w, ldw, bias, tgt, 0, N, nll, lse, ws, M, N, K, static_cast<hipStream_t>(stream));
 }
@@ -276,7 +275,7 @@ extern "C" int blm_linear_mc_stats(const float* x, int64_t ldx, const float* w, 
   const int Np = (V + 3) / 4 * 4;
   if (!blm::extents_ok({R, ldx}) || !blm::extents_ok({Np, ldw}) || !blm::extents_ok({R, Np}))
     return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_stats: extents too large");
-  if (!aligned16(ws) || (bias && !aligned16(bias)))
+  if (!aligned16(ws, bias))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_mc_stats: needs 16-byte aligned bias / workspace");
   if (M == 0) return BLM_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -325,7 +324,7 @@ extern "C" int blm_linear_mc_logprobs(const float* x, int64_t ldx, const float* 
   const int Np = (V + 3) / 4 * 4;
   if (!blm::extents_ok({R, ldx}) || !blm::extents_ok({Np, ldw}) || !blm::extents_ok({R, Np}) || !blm::extents_ok({M, ldo}))
     return blm_fail(BLM_ERR_INVALID, "blm_linear_mc_logprobs: extents too large");
-  if (!aligned16(ws) || (bias && !aligned16(bias)))
+  if (!aligned16(ws, bias))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_mc_logprobs: needs 16-byte aligned bias / workspace");
   if (M == 0) return BLM_OK;
   const int64_t ws_stats = blm_linear_mc_stats_ws_floats(M, S, V);
@@ -411,8 +410,7 @@ extern "C" int blm_linear_nll2(const float* x1, int64_t ldx1, const float* w1, i
   if (M == 0) return BLM_OK;
   if (!x1 || !x2 || !w1 || !w2 || !tgt || !nll || !wcat || !ws || ldx1 < K1 || ldx2 < K2 || ldw1 < K1 || ldw2 < K2)
     return blm_fail(BLM_ERR_INVALID, "blm_linear_nll2: bad arguments");
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (K1 % 4 || K2 % 4 || ldx1 % 4 || ldx2 % 4 || ldw1 % 4 || ldw2 % 4 || !al(x1) || !al(x2) || !al(w1) || !al(w2) || !al(wcat) || !al(ws))
+  if (K1 % 4 || K2 % 4 || ldx1 % 4 || ldx2 % 4 || ldw1 % 4 || ldw2 % 4 || !aligned16(x1, x2, w1, w2, wcat, ws))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll2: needs K1, K2 and the row strides to be multiples of 4 and 16-byte aligned operands");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int K = K1 + K2, Np = (N + 3) / 4 * 4;
@@ -479,7 +477,7 @@ extern "C" int blm_linear_nll_edges(const float* x, int64_t ldx, const float* w,
     return blm_fail(BLM_ERR_INVALID, "blm_linear_nll_edges: bad arguments");
   if (!blm::extents_ok({M, ldx}) || !blm::extents_ok({N, ldw}) || !blm::extents_ok({M, N}))
     return blm_fail(BLM_ERR_INVALID, "blm_linear_nll_edges: extents too large");
-  if (N % 4 != 0 || !aligned16(ws) || (bias && !aligned16(bias)))
+  if (N % 4 != 0 || !aligned16(ws, bias))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll_edges: needs N %% 4 == 0 and 16-byte aligned bias / workspace");
   if (E == 0) return BLM_OK;
   if (M == 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll_edges: edges without nodes");
@@ -491,7 +489,7 @@ extern "C" int blm_linear_nll_edges(const float* x, int64_t ldx, const float* w,
   BLM_HIP(hipMemsetAsync(tgt0, 0, (size_t)M * sizeof(int64_t), st));
   const int rc = linear_nll_launch(x, ldx, w, ldw, bias, tgt0, 0, nv, nll_rows, lse_rows, ws, M, N, K, st);
   if (rc) return rc;
-  const int vec = aligned16(x) && aligned16(w) && ldx % 4 == 0 && ldw % 4 == 0 && K % 4 == 0;
+  const int vec = aligned16(x, w) && ldx % 4 == 0 && ldw % 4 == 0 && K % 4 == 0;
   hipLaunchKernelGGL(edge_nll_kernel, dim3((unsigned)(((long)E + 3) / 4)), dim3(256), 0, st, x, (long)ldx, w, (long)ldw, bias,
                      reinterpret_cast<const long long*>(edge_node), reinterpret_cast<const long long*>(edge_tgt), lse_rows, nll, (long)E,
                      M, nv, K, vec);
@@ -514,8 +512,7 @@ extern "C" int blm_linear_nll2_edges(const float* x1, int64_t ldx1, const float*
   if (M < 0 || E < 0 || N <= 0 || K1 <= 0 || K2 <= 0) return blm_fail(BLM_ERR_INVALID, "blm_linear_nll2_edges: bad shape");
   if (!x1 || !x2 || !w1 || !w2 || !edge_node || !edge_tgt || !nll || !wcat || !ws || ldx1 < K1 || ldx2 < K2 || ldw1 < K1 || ldw2 < K2)
     return blm_fail(BLM_ERR_INVALID, "blm_linear_nll2_edges: bad arguments");
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (K1 % 4 || K2 % 4 || ldx1 % 4 || ldx2 % 4 || ldw1 % 4 || ldw2 % 4 || !al(x1) || !al(x2) || !al(w1) || !al(w2) || !al(wcat) || !al(ws))
+  if (K1 % 4 || K2 % 4 || ldx1 % 4 || ldx2 % 4 || ldw1 % 4 || ldw2 % 4 || !aligned16(x1, x2, w1, w2, wcat, ws))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_linear_nll2_edges: needs K1, K2 and the row strides to be multiples of 4 and 16-byte aligned operands");
   const int K = K1 + K2, Np = (N + 3) / 4 * 4;
   if (!blm::extents_ok({M, K}) || !blm::extents_ok({Np, K}) || !blm::extents_ok({M, Np}))

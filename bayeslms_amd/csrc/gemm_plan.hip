@@ -313,9 +313,8 @@ blm::PlanKey blm::plan_key(const blm_gemm_args* a) {
   // deterministic mode (blm_set_option("deterministic", 1)): partial sums never meet through float atomics -- every plan, whatever
   // its source (table, override, model), is legalised to one K slice, tail slicing included (choose_plan: !can_split -> splits = 1)
   if (option(OPT_DETERMINISTIC)) k.can_split = 0;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const int ac = a->op == BLM_GEMM_TN ? a->M : a->K, bc = a->op == BLM_GEMM_NT ? a->K : a->N;
-  k.fast = al16(a->A) && al16(a->B) && a->lda % 4 == 0 && a->ldb % 4 == 0 && ac % 4 == 0 && bc % 4 == 0 && ac >= 4 && bc >= 4;
+  k.fast = aligned16(a->A, a->B) && a->lda % 4 == 0 && a->ldb % 4 == 0 && ac % 4 == 0 && bc % 4 == 0 && ac >= 4 && bc >= 4;
   const long arows = a->op == BLM_GEMM_TN ? a->K : a->M, brows = a->op == BLM_GEMM_NT ? a->N : a->K;
   if (arows * (long)a->lda * 4 >= (1L << 32) || brows * (long)a->ldb * 4 >= (1L << 32)) k.fast = 0;
   return k;

@@ -30,8 +30,6 @@ __device__ __forceinline__ float4 lp_load4(const float* p, int j, int V, bool ve
   return r;
 }
 
-__device__ __forceinline__ float lp_comp(const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
-
 // ---------------------------------------------------------------- curvature
 // exp(x - M) of one column for the row's sum; a column at -inf adds nothing, a NaN makes the sum NaN
 __device__ __forceinline__ float curv_term(float x, float M) { return x == -INFINITY ? 0.f : __expf(x - M); }
@@ -397,11 +395,11 @@ __global__ __launch_bounds__(LP_TPB) void laplace_mc_rows_kernel(McArgs p) {
       const int tq = tg >> 2;
       const float4 z4 = lp_load4(zr, 4 * tq, V, vec, -INFINITY);
       const float4 sd = mc_sd4(lp_load4(vr, 4 * tq, V, vec, 0.f));
-      t = lp_comp(mc_psum4(z4, sd, p, blk0 + tq, lse), tg & 3) * inv_s;
+      t = comp(mc_psum4(z4, sd, p, blk0 + tq, lse), tg & 3) * inv_s;
       if (p.nll_s) {
 #pragma unroll 1
         for (int s = 0; s < S; ++s)
-          p.nll_s[(long)s * p.R + row] = bad ? NAN : lse[s] - lp_comp(mc_sample4(z4, sd, p, s, blk0 + tq), tg & 3);
+          p.nll_s[(long)s * p.R + row] = bad ? NAN : lse[s] - comp(mc_sample4(z4, sd, p, s, blk0 + tq), tg & 3);
       }
     } else if (p.nll_s) {
       for (int s = 0; s < S; ++s) p.nll_s[(long)s * p.R + row] = NAN;
@@ -456,16 +454,6 @@ __global__ __launch_bounds__(LP_TPB) void laplace_mc_rows_kernel(McArgs p) {
   if (p.rank) p.rank[row] = (b || !has_t) ? -1 : f.cnt;
 }
 
-inline bool lp_aligned16(const void* a, const void* b) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-}
-
-// the bytes [first, last) a (rows, V) matrix at row stride ld touches
-inline void lp_span(const float* p, long rows, long ld, long V, uintptr_t& first, uintptr_t& last) {
-  first = reinterpret_cast<uintptr_t>(p);
-  last = first + (uintptr_t)(((rows - 1) * ld + V) * 4);
-}
-
 }  // namespace
 }  // namespace blm
 
@@ -475,15 +463,10 @@ extern "C" int blm_laplace_curvature(const float* logits, int64_t ld, float* a, 
     return blm_fail(BLM_ERR_INVALID, "blm_laplace_curvature: bad shape (rows %d, V %d, ld %lld, lda %lld)", rows, V, (long long)ld,
                     (long long)lda);
   if (rows == 0) return BLM_OK;
-  if (a == logits ? lda != ld : true) {
-    uintptr_t x0, x1, a0, a1;
-    blm::lp_span(logits, rows, (long)ld, V, x0, x1);
-    blm::lp_span(a, rows, (long)lda, V, a0, a1);
-    if (x0 < a1 && a0 < x1)
-      return blm_fail(BLM_ERR_INVALID, "blm_laplace_curvature: logits and a overlap (in place takes a == logits and lda == ld)");
-  }
+  if (!(a == logits && lda == ld) && blm::overlaps(blm::span_of(logits, rows, ld, V), blm::span_of(a, rows, lda, V)))
+    return blm_fail(BLM_ERR_INVALID, "blm_laplace_curvature: logits and a overlap (in place takes a == logits and lda == ld)");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = ((ld | lda) & 3) == 0 && blm::lp_aligned16(logits, a);
+  const bool vec = ((ld | lda) & 3) == 0 && blm::aligned16(logits, a);
   if (vec && V <= 4096 * 3)
     hipLaunchKernelGGL(blm::curv_row_kernel<3>, dim3(rows), dim3(1024), 0, st, logits, (long)ld, a, (long)lda, V);
   else if (vec && V <= 4096 * 9)
@@ -506,7 +489,7 @@ extern "C" int blm_laplace_row_stats(const float* z, int64_t ldz, const float* v
     return blm_fail(BLM_ERR_INVALID, "blm_laplace_row_stats: extents too large");
   if (R == 0) return BLM_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int vec = ((ldz | ldv) & 3) == 0 && blm::lp_aligned16(z, var) ? 1 : 0;
+  const int vec = ((ldz | ldv) & 3) == 0 && blm::aligned16(z, var) ? 1 : 0;
   if (link == blm::LINK_PROBIT)
     hipLaunchKernelGGL(blm::laplace_row_stats_kernel<blm::LINK_PROBIT>, dim3(R), dim3(blm::LP_TPB), 0, st, z, (long)ldz, var,
                        (long)ldv, tgt, V, vec, nll, conf, entropy, pred, rank, vbar);
@@ -534,7 +517,7 @@ extern "C" int blm_laplace_mc_rows(const float* z, int64_t ldz, const float* var
   blm::McArgs p;
   p.z = z, p.ldz = (long)ldz, p.var = var, p.ldv = (long)ldv, p.tgt = tgt;
   p.R = R, p.V = V, p.S = S;
-  p.vec = ((ldz | ldv) & 3) == 0 && blm::lp_aligned16(z, var) ? 1 : 0;
+  p.vec = ((ldz | ldv) & 3) == 0 && blm::aligned16(z, var) ? 1 : 0;
   p.seed = rng->seed, p.stream = rng->stream, p.row0 = (long)row0;
   p.bma_nll = bma_nll, p.nll_s = nll_s, p.h_pred = h_pred, p.mi = mi, p.conf = conf, p.pred = pred, p.rank = rank;
   hipLaunchKernelGGL(blm::laplace_mc_rows_kernel, dim3(R), dim3(blm::LP_TPB), 0, st, p);

@@ -22,7 +22,6 @@ static int grid_for(long items) {
   return (int)g;
 }
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 struct ZetaKey {
   blm_rng rng;
@@ -140,7 +139,7 @@ using namespace blm;
 extern "C" int blm_lrt_prepare(const float* src, float* dst, int64_t n, int mode, void* stream) {
   if (!src || !dst || n < 0 || n > kMaxElems || (mode != 0 && mode != 1)) return blm_fail(BLM_ERR_INVALID, "blm_lrt_prepare: bad arguments");
   if (n == 0) return BLM_OK;
-  hipLaunchKernelGGL(lrt_prepare_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, src, dst, (long)n, mode, al16(src) && al16(dst));
+  hipLaunchKernelGGL(lrt_prepare_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, src, dst, (long)n, mode, aligned16(src, dst));
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }
@@ -152,7 +151,7 @@ extern "C" int blm_lrt_combine(float* y, float* s, const float* zeta, const blm_
     return blm_fail(BLM_ERR_INVALID, "blm_lrt_combine: bad arguments");
   const long n = (long)rows * B * N;
   if (n == 0) return BLM_OK;
-  const bool vec = N % 4 == 0 && al16(y) && al16(s) && al16(zeta);
+  const bool vec = N % 4 == 0 && aligned16(y, s, zeta);
   hipLaunchKernelGGL(lrt_combine_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(TPB), 0, ST, y, s, n, k, vec);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
@@ -165,7 +164,7 @@ extern "C" int blm_lrt_bwd_factor(const float* dy, const float* s, float* q, con
     return blm_fail(BLM_ERR_INVALID, "blm_lrt_bwd_factor: bad arguments");
   const long n = (long)rows * B * N;
   if (n == 0) return BLM_OK;
-  const bool vec = N % 4 == 0 && al16(dy) && al16(s) && al16(q) && al16(zeta);
+  const bool vec = N % 4 == 0 && aligned16(dy, s, q, zeta);
   hipLaunchKernelGGL(lrt_bwd_factor_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(TPB), 0, ST, dy, s, q, n, k, vec);
   BLM_HIP(hipGetLastError());
   return BLM_OK;
@@ -175,7 +174,7 @@ extern "C" int blm_lrt_mul(float* out, const float* a, const float* b, int64_t n
   if (!out || !a || !b || n < 0 || n > kMaxElems) return blm_fail(BLM_ERR_INVALID, "blm_lrt_mul: bad arguments");
   if (n == 0) return BLM_OK;
   hipLaunchKernelGGL(lrt_mul_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, ST, out, a, b, (long)n, scale, accumulate != 0,
-                     al16(out) && al16(a) && al16(b));
+                     aligned16(out, a, b));
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

@@ -972,7 +972,6 @@ extern "C" int blm_lstm_step_fwd_gp(const float*, const float*, const float*, co
 extern "C" int blm_lstm_step_bwd_gp(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
                                     float*, float*, float*, int, const float*, const float*, float*, float*, int, int, void*);
 
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" int blm_lstm_step_fwd(const float* xw_t, const float* w_hh, const float* h_prev, const float* c_prev, float* h,
                                  float* c, float* gates_act, const float* h_noise, int B, int H, void* stream) {
@@ -986,7 +985,7 @@ extern "C" int blm_lstm_step_fwd_gp(const float* xw_t, const float* w_hh, const 
       (gate_ovr >= 4 && !rbias) || (gate_ovr == 5 && !z_out))
     return blm_fail(BLM_ERR_INVALID, "blm_lstm_step_fwd: bad arguments");
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 32 != 0 || !al16(w_hh) || !al16(h_prev) || 16.0 * H * H >= 4294967296.0 || 4.0 * B * H >= 4294967296.0)  // 32-bit byte offsets
+  if (H % 32 != 0 || !aligned16(w_hh, h_prev) || 16.0 * H * H >= 4294967296.0 || 4.0 * B * H >= 4294967296.0)  // 32-bit byte offsets
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_step_fwd: needs H % 32 == 0, 16-byte aligned h_prev / w_hh and operands under 4 GB");
   LstmStepP p{xw_t, w_hh, h_prev, c_prev, h, c, gates_act, h_noise, coef4, z_out, gate_ovr < 0 ? -1 : gate_ovr, rbias, B, H, nullptr};
   if (gate_ovr < 0 && B <= 4 && H % 4 == 0 && lstm_gemv()) {  // tiny batches (the scorer's carry chain): one wave per hidden unit
@@ -1041,7 +1040,7 @@ extern "C" int blm_lstm_seq_pair_fwd(const float* xw_a, const float* w_hh_a, flo
   if (!blm::extents_ok({n_a, B, H, 4}) || !blm::extents_ok({n_b, B, H, 4}) || B < 1 || H < 1 || (n_a > 0 && (!xw_a || !w_hh_a || !hs_a || !cs_a)) || (n_b > 0 && (!xw_b || !w_hh_b || !hs_b || !cs_b)))
     return blm_fail(BLM_ERR_INVALID, "blm_lstm_seq_pair_fwd: bad arguments");
   const size_t bh = (size_t)B * H, bg = 4 * bh;
-  const bool pairable = B <= 4 && H % 4 == 0 && lstm_gemv() && (n_a == 0 || (al16(w_hh_a) && al16(hs_a))) && (n_b == 0 || (al16(w_hh_b) && al16(hs_b))) &&
+  const bool pairable = B <= 4 && H % 4 == 0 && lstm_gemv() && (n_a == 0 || aligned16(w_hh_a, hs_a)) && (n_b == 0 || aligned16(w_hh_b, hs_b)) &&
                         (bh * sizeof(float)) % 16 == 0;
   hipStream_t s0 = (hipStream_t)stream;
   const int n = n_a > n_b ? n_a : n_b;
@@ -1078,7 +1077,7 @@ extern "C" int blm_lstm_search_step_fwd(const float* xw8_t, const float* w8_hh, 
   if (!xw8_t || !w8_hh || !h_prev || !c_prev || !probs || !h || !c || B < 0 || H < 0)
     return blm_fail(BLM_ERR_INVALID, "blm_lstm_search_step_fwd: bad arguments");
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 32 != 0 || !al16(w8_hh) || !al16(h_prev) || 32.0 * H * H >= 4294967296.0 || 4.0 * B * H >= 4294967296.0)
+  if (H % 32 != 0 || !aligned16(w8_hh, h_prev) || 32.0 * H * H >= 4294967296.0 || 4.0 * B * H >= 4294967296.0)
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_search_step_fwd: needs H % 32 == 0, 16-byte aligned h_prev / w8_hh and operands under 4 GB");
   LstmStepP p{xw8_t, w8_hh, h_prev, c_prev, h, c, acts8, nullptr, nullptr, nullptr, -1, nullptr, B, H, probs};
   const size_t lds = (size_t)4 * WAVE_LDS * sizeof(float);
@@ -1167,7 +1166,7 @@ extern "C" int blm_lstm_step_bwd_gp(const float* dgates_t, const float* w_hh_t, 
       (dgates_out && gate_ovr == 5 && !dact_out))
     return blm_fail(BLM_ERR_INVALID, "blm_lstm_step_bwd: bad arguments");
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 32 != 0 || !al16(dgates_t) || !al16(w_hh_t))
+  if (H % 32 != 0 || !aligned16(dgates_t, w_hh_t))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_step_bwd: needs H % 32 == 0 and 16-byte aligned dgates_t / w_hh_t");
   LstmBwdP p{dgates_t, w_hh_t, dy_prev, dc_next, c_prev, c, gates_act, dgates_out, dc_prev, dh_out, z_prev, coef4, dact_out,
              dz_out, (dgates_out && gate_ovr >= 0) ? gate_ovr : -1, B, H, 4 * H, (long)H, nullptr, 0, 0, 0, 0, 0.f};
@@ -1211,7 +1210,7 @@ extern "C" int blm_lstm_search_step_bwd(const float* dz8_t, const float* w8_t, c
   if (!dz8_t || !w8_t || !c_prev || !c || !acts8 || !probs || !dz8_out || !dc_prev || !partial || B < 0 || H < 0)
     return blm_fail(BLM_ERR_INVALID, "blm_lstm_search_step_bwd: bad arguments");
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 16 != 0 || !al16(dz8_t) || !al16(w8_t))
+  if (H % 16 != 0 || !aligned16(dz8_t, w8_t))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_search_step_bwd: needs H % 16 == 0 and 16-byte aligned dz8_t / w8_t");
   LstmBwdP p{dz8_t, w8_t, dy_prev, dc_next, c_prev, c, acts8, dz8_out, dc_prev, nullptr, nullptr, probs, partial, nullptr, 8,
              B, H, 8 * H, (long)H, nullptr, 0, 0, 0, 0, 0.f};
@@ -1221,7 +1220,7 @@ extern "C" int blm_lstm_search_step_bwd(const float* dz8_t, const float* w8_t, c
 extern "C" int blm_lstm_step_dh_ld(const float* dz, const float* w_t, float* dh_out, int64_t ldo, int B, int H, int G, void* stream) {
   if (!dz || !w_t || !dh_out || B < 0 || H < 0 || G < 0 || ldo < H) return blm_fail(BLM_ERR_INVALID, "blm_lstm_step_dh: bad arguments");
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !al16(dz) || !al16(w_t))
+  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !aligned16(dz, w_t))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_step_dh: needs H % 16 == 0, G % 64 == 0 and 16-byte aligned dz / w_t");
   LstmBwdP p{dz, w_t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dh_out, nullptr, nullptr, nullptr, nullptr, -1,
              B, H, G, (long)ldo, nullptr, 0, 0, 0, 0, 0.f};
@@ -1234,7 +1233,7 @@ extern "C" int blm_lstm_step_dh_act(const float* dz, const float* w_t, float* ou
       ld_f < (act_mode == 1 ? H : M) || (acts & ~15))
     return blm_fail(BLM_ERR_INVALID, "blm_lstm_step_dh_act: bad arguments");
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !al16(dz) || !al16(w_t))
+  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !aligned16(dz, w_t))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_step_dh_act: needs H % 16 == 0, G % 64 == 0 and 16-byte aligned dz / w_t");
   LstmBwdP p{dz, w_t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, nullptr, nullptr, -1,
              B, H, G, (long)ldo, feat, act_mode, M, ld_f, acts, scale};
@@ -1250,7 +1249,7 @@ extern "C" int blm_lstm_step_dh(const float* dz, const float* w_t, float* dh_out
 static int step_dh_add(const float* dz, const float* w_t, float* out, const float* add, long add_ld, float* add_out, int lo, int n,
                        int B, int H, int G, void* stream) {
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !al16(dz) || !al16(w_t))
+  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !aligned16(dz, w_t))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_gpnn2_seq_fwd: needs H % 16 == 0, G % 64 == 0 and 16-byte aligned operands");
   LstmBwdP p{dz, w_t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, nullptr, nullptr, -1,
              B, H, G, (long)H, nullptr, 0, 0, 0, 0, 0.f, add, add_ld, add_out, lo, n};
@@ -1260,7 +1259,7 @@ static int step_dh_add(const float* dz, const float* w_t, float* out, const floa
 static int step_dh_cell(const float* dz, const float* w_t, float* out, const float* xw, const float* hw, const float* c_prev, int gate,
                         float* h, float* c, float* ga, int B, int H, int G, void* stream) {
   if ((long)B * H == 0) return BLM_OK;
-  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !al16(dz) || !al16(w_t))
+  if (H % 16 != 0 || G % 64 != 0 || G == 0 || !aligned16(dz, w_t))
     return blm_fail(BLM_ERR_UNSUPPORTED, "blm_lstm_gpnn2_seq_fwd: needs H % 16 == 0, G % 64 == 0 and 16-byte aligned operands");
   LstmBwdP p{dz, w_t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, nullptr, nullptr, -1,
              B, H, G, (long)H, nullptr, 3, 0, 0, 0, 0.f, nullptr, 0, nullptr, 0, 0, xw, hw, c_prev, h, c, ga, gate};

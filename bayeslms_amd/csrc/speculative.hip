@@ -5,7 +5,7 @@
 // Rows behind a rejection are wasted work; what that buys is one pass instead of a chain per stream.
 // Per row: max of both rows (one barrier pair), sum exp of both (one more), then one sweep that forms log p, log q, log rho and
 // the Gumbel keys and reduces two arg-maxima (the residual draw, and the plain draw that stands in when no column has
-// rho > 0) by blm_sample_rows' rule: lowest index on ties, a NaN never wins.  No atomics, fixed order: the same bits from every run.
+// rho > 0) by blm_sample_rows' rule (blm_device.h's Best).  No atomics, fixed order: the same bits from every run.
 #include <cmath>
 
 #include "blm_device.h"
@@ -15,66 +15,6 @@ namespace blm {
 namespace {
 
 constexpr int SPEC_TPB = 1024;  // 16 waves
-
-__device__ __forceinline__ float uniform(float v) {  // a value every lane holds alike: one SGPR, no VGPR
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-// two maxima / two sums of a 1024-thread workgroup behind one barrier pair each; fixed order
-__device__ __forceinline__ void row_max2(float& a, float& b, float (*red)[16]) {
-  a = wave_max(a);
-  b = wave_max(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[0][w] = a; red[1][w] = b; }
-  __syncthreads();
-  a = red[0][lane & 15];
-  b = red[1][lane & 15];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    a = fmaxf(a, __shfl_xor(a, o, 64));
-    b = fmaxf(b, __shfl_xor(b, o, 64));
-  }
-  a = uniform(a);
-  b = uniform(b);
-}
-__device__ __forceinline__ void row_sum2(float& a, float& b, float (*red)[16]) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[0][w] = a; red[1][w] = b; }
-  __syncthreads();
-  a = red[0][lane & 15];
-  b = red[1][lane & 15];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
-  a = uniform(a);
-  b = uniform(b);
-}
-
-// Lowest index wins a tie; a NaN score never wins (blm_sample_rows' rule).
-struct Best {
-  float v;
-  int i;
-};
-constexpr int kNone = 0x7fffffff;
-__device__ __forceinline__ void best_of(Best& b, float v2, int i2) {
-  if (v2 > b.v || (v2 == b.v && i2 < b.i) || (b.v != b.v && v2 == v2)) {
-    b.v = v2;
-    b.i = i2;
-  }
-}
-__device__ __forceinline__ void wave_best(Best& b) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(b.v, o, 64);
-    const int i2 = __shfl_xor(b.i, o, 64);
-    best_of(b, v2, i2);
-  }
-}
 
 // The Philox state of a row that no column changes: the ten round keys and the counter words (row, stream, step).  Formed once
 // at the top of the kernel, outside every branch that depends on the thread, and pinned to scalar registers: left to the
@@ -157,24 +97,6 @@ __device__ __forceinline__ void spec_finish(unsigned row, bool bonus, bool bad, 
   cand[row] = bad ? -1 : (resid.i == kNone ? pl : resid.i);
 }
 
-// the two arg-maxima of the workgroup -> thread 0 (the other threads' values are partial)
-__device__ __forceinline__ void row_best2(Best& a, Best& b, float (*sv)[16], int (*si)[16]) {
-  wave_best(a);
-  wave_best(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[0][w] = a.v; si[0][w] = a.i;
-    sv[1][w] = b.v; si[1][w] = b.i;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < SPEC_TPB / 64; ++k) {
-      best_of(a, sv[0][k], si[0][k]);
-      best_of(b, sv[1][k], si[1][k]);
-    }
-  }
-}
-
 // Both rows held in registers, as ce_soft_row_kernel (distill.hip) holds them: 1024 threads x NV float4 of each cover
 // V <= 4096 NV, every row is read from memory once, all 2 NV loads of a thread issued back to back.  Requires V >= 4, ldp and
 // ldq multiples of 4 and 16-byte aligned bases (blm_spec_accept selects).  A bonus row (t = G) has no draft row: it reads its
@@ -212,7 +134,7 @@ __global__ __launch_bounds__(SPEC_TPB) void spec_row_kernel(const float* __restr
     mp = fmaxf(mp, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
     mq = fmaxf(mq, fmaxf(fmaxf(u[i].x, u[i].y), fmaxf(u[i].z, u[i].w)));
   }
-  row_max2(mp, mq, red);
+  row_fold<ROW_MAX, ROW_UNIFORM>(red, mp, mq);
   // a NaN anywhere in a row makes its sum NaN (fmaxf skips it, exp does not); so does a row without a finite maximum
   float sp = extra ? __expf(beta * (ze - mp)) : 0.f, sq = extra ? __expf(beta * (le - mq)) : 0.f;
 #pragma unroll
@@ -221,7 +143,7 @@ __global__ __launch_bounds__(SPEC_TPB) void spec_row_kernel(const float* __restr
     sp += (__expf(beta * (v[i].x - mp)) + __expf(beta * (v[i].y - mp))) + (__expf(beta * (v[i].z - mp)) + __expf(beta * (v[i].w - mp)));
     sq += (__expf(beta * (u[i].x - mq)) + __expf(beta * (u[i].y - mq))) + (__expf(beta * (u[i].z - mq)) + __expf(beta * (u[i].w - mq)));
   }
-  row_sum2(sp, sq, red);
+  row_fold<ROW_SUM, ROW_UNIFORM>(red, sp, sq);
   const bool bad = !(sp == sp) || !(sq == sq);
   const float lsp = __logf(sp), lsq = __logf(sq);
   const SpecRow c = {beta, mp, lsp, mq, lsq, beta * mp + lsp, beta * mq + lsq};
@@ -238,7 +160,7 @@ __global__ __launch_bounds__(SPEC_TPB) void spec_row_kernel(const float* __restr
       spec_elem(v[i].w, u[i].w, j + 3, c, g, plain, resid);
     }
   }
-  row_best2(plain, resid, sv, si);
+  block_best2<SPEC_TPB / 64>(plain, resid, sv, si);
   if (threadIdx.x == 0) spec_finish(row, bonus, bad, x, y, draft, V, c, g, plain, resid, accept, cand);
 }
 
@@ -264,17 +186,17 @@ __global__ __launch_bounds__(SPEC_TPB) void spec_sweep_kernel(const float* __res
     sq += tq > -INFINITY || b != b ? __expf(beta * (b - tq)) : 0.f;
   }
   float mp = tp, mq = tq;
-  row_max2(mp, mq, red);
+  row_fold<ROW_MAX, ROW_UNIFORM>(red, mp, mq);
   // a thread whose columns were all -inf holds a zero sum; a row whose every column is -inf has no finite maximum: NaN, as above
   sp = tp > -INFINITY ? sp * __expf(beta * (tp - mp)) : (mp > -INFINITY ? sp : NAN);
   sq = tq > -INFINITY ? sq * __expf(beta * (tq - mq)) : (mq > -INFINITY ? sq : NAN);
-  row_sum2(sp, sq, red);
+  row_fold<ROW_SUM, ROW_UNIFORM>(red, sp, sq);
   const bool bad = !(sp == sp) || !(sq == sq);
   const float lsp = __logf(sp), lsq = __logf(sq);
   const SpecRow c = {beta, mp, lsp, mq, lsq, beta * mp + lsp, beta * mq + lsq};
   Best plain = {-INFINITY, kNone}, resid = {-INFINITY, kNone};
   for (int j = threadIdx.x; j < V; j += SPEC_TPB) spec_elem(x[j], y[j], (unsigned)j, c, g, plain, resid);
-  row_best2(plain, resid, sv, si);
+  block_best2<SPEC_TPB / 64>(plain, resid, sv, si);
   if (threadIdx.x == 0) spec_finish(row, bonus, bad, x, y, draft, V, c, g, plain, resid, accept, cand);
 }
 
@@ -293,16 +215,8 @@ __global__ __launch_bounds__(SPEC_TPB) void spec_greedy_kernel(const float* __re
     nan |= a != a;
     best_of(b, a, j);
   }
-  wave_best(b);
-  nan = __any(nan);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { sv[w] = b.v; si[w] = b.i; sn[w] = nan; }
-  __syncthreads();
+  block_best<SPEC_TPB / 64>(b, sv, si, &nan, sn);
   if (threadIdx.x == 0) {
-    for (int k = 1; k < SPEC_TPB / 64; ++k) {
-      best_of(b, sv[k], si[k]);
-      nan |= sn[k];
-    }
     const long best = nan ? -1 : (b.i == kNone ? 0 : b.i);
     cand[row] = best;
     if (row < (unsigned)GN) accept[row] = !nan && draft[row] == best ? 1 : 0;
@@ -358,7 +272,7 @@ extern "C" int blm_spec_accept(const float* p, int64_t ldp, const float* q, int6
   if (greedy) {
     hipLaunchKernelGGL(spec_greedy_kernel, grid, block, 0, st, p, (long)ldp, draft, (int)GN, V, accept, cand);
   } else {
-    const bool vec = ((ldp & 3) == 0) && ((ldq & 3) == 0) && (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & 15) == 0);
+    const bool vec = ((ldp & 3) == 0) && ((ldq & 3) == 0) && aligned16(p, q);
     if (vec && V >= 4 && V <= 4096 * 3)
       hipLaunchKernelGGL(spec_row_kernel<3>, grid, block, 0, st, p, (long)ldp, q, (long)ldq, draft, (int)GN, V, beta, *rng, accept, cand);
     else if (vec && V >= 4 && V <= 4096 * 9)

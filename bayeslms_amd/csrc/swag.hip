@@ -26,11 +26,6 @@ inline int swag_grid(long n) {
   return (int)(blocks < 1 ? 1 : (blocks > SWAG_GRID ? SWAG_GRID : blocks));
 }
 
-__device__ __forceinline__ bool swag_aligned16(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
-}
-
 // ---------------------------------------------------------------- collect
 // d = th - mean; mean' = mean + d * inv; m2' = m2 + d * (th - mean'); deviation = th - mean'.  FIRST: mean and m2 are not read.
 template <bool FIRST>
@@ -51,7 +46,7 @@ template <bool FIRST, bool DEV>
 __global__ __launch_bounds__(SWAG_TPB) void swag_collect_kernel(const float* __restrict__ theta, float* __restrict__ mean,
                                                                 float* __restrict__ m2, float* __restrict__ dev, long n,
                                                                 float inv) {
-  const long n4 = swag_aligned16(theta, mean, m2, dev) ? (n >> 2) : 0;
+  const long n4 = aligned16(theta, mean, m2, dev) ? (n >> 2) : 0;
   const long stride = (long)gridDim.x * SWAG_TPB, first = (long)blockIdx.x * SWAG_TPB + threadIdx.x;
   for (long i = first; i < n4; i += stride) {
     const float4 tv = reinterpret_cast<const float4*>(theta)[i];
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(SWAG_TPB) void swag_sample_kernel(float* __restrict
 #pragma clang fp contract(off)
   const SwagCoef c = {draw.a, draw.b, draw.inv_n, draw.var_floor};
   const int count = draw.count;
-  const bool vec = swag_aligned16(out, mean, m2, k_live > 0 ? dev : nullptr) && ((ld_out | (k_live > 0 ? ld_dev : 0)) & 3) == 0;
+  const bool vec = aligned16(out, mean, m2, k_live > 0 ? dev : nullptr) && ((ld_out | (k_live > 0 ? ld_dev : 0)) & 3) == 0;
   const long n4 = vec ? (n >> 2) : 0;
   const long stride = (long)gridDim.x * SWAG_TPB, first = (long)blockIdx.x * SWAG_TPB + threadIdx.x;
   for (long i = first; i < n4; i += stride) {
@@ -170,35 +165,6 @@ __global__ __launch_bounds__(SWAG_TPB) void swag_sample_kernel(float* __restrict
 }
 
 // ---------------------------------------------------------------- log-mean-exp over the samples
-// Block reductions of a 1024-thread workgroup as distill.hip does them: the 16 per-wave partials are read back one per lane and
-// folded by a butterfly.  Fixed order.
-__device__ __forceinline__ float lavg_fold16(float r) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
-  return r;
-}
-__device__ __forceinline__ float lavg_max(float v, float* red) {
-  v = wave_max(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float r = red[lane & 15];
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) r = fmaxf(r, __shfl_xor(r, o, 64));
-  return r;
-}
-__device__ __forceinline__ void lavg_sum2(float& a, float& b, float (*red)[16]) {  // two sums behind one barrier pair
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[0][w] = a; red[1][w] = b; }
-  __syncthreads();
-  a = lavg_fold16(red[0][lane & 15]);
-  b = lavg_fold16(red[1][lane & 15]);
-}
-
 // exp(d) and exp(d) d of one column, d = x - max; a column at -inf adds nothing to either (p log p -> 0 at p = 0), also while
 // the running max of a sweep is still -inf itself, where x - max would be NaN
 __device__ __forceinline__ void lavg_term(float x, float M, float& l, float& u) {
@@ -263,13 +229,14 @@ __global__ __launch_bounds__(1024) void logp_avg_row_kernel(const float* __restr
   float m = -INFINITY;
 #pragma unroll
   for (int i = 0; i < NV; ++i) m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
-  const float M_ = lavg_max(m, red[0]);
+  float M_ = m;
+  row_fold<ROW_MAX>(red, M_);
   float l = 0.f, u = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     lavg_term(v[i].x, M_, l, u); lavg_term(v[i].y, M_, l, u); lavg_term(v[i].z, M_, l, u); lavg_term(v[i].w, M_, l, u);
   }
-  lavg_sum2(l, u, red);
+  row_fold<ROW_SUM>(red, l, u);
   const float logl = __logf(l), lse = M_ + logl;
   if (threadIdx.x == 0) lavg_row_out(t, row, x, V, lse, logl - u / l);
 #pragma unroll
@@ -297,7 +264,7 @@ __global__ __launch_bounds__(1024) void logp_avg_sweep_kernel(const float* __res
   const long row = blockIdx.x;
   const float* x = logits + row * ld;
   float* a = acc + row * ld_acc;
-  const bool vec = ((ld | ld_acc) & 3) == 0 && swag_aligned16(logits, acc);
+  const bool vec = ((ld | ld_acc) & 3) == 0 && aligned16(logits, acc);
   const int V4 = vec ? (V & ~3) : 0;
   float m = -INFINITY, l = 0.f, u = 0.f;
   auto rescale = [&](float mx) {  // the state re-expressed for a max mx > m
@@ -319,9 +286,10 @@ __global__ __launch_bounds__(1024) void logp_avg_sweep_kernel(const float* __res
     if (w > m) rescale(w);
     lavg_term(w, m, l, u);
   }
-  const float M_ = lavg_max(m, red[0]);
+  float M_ = m;
+  row_fold<ROW_MAX>(red, M_);
   if (m < M_) rescale(M_);  // a lane that saw no finite column keeps l = u = 0
-  lavg_sum2(l, u, red);
+  row_fold<ROW_SUM>(red, l, u);
   const float logl = __logf(l), lse = M_ + logl;
   if (threadIdx.x == 0) lavg_row_out(t, row, x, V, lse, logl - u / l);
   for (int j = threadIdx.x * 4; j < V4; j += 4096) {
@@ -409,7 +377,7 @@ extern "C" int blm_logp_avg_accum(const float* logits, int64_t ld, float* acc, i
   if (rows == 0) return BLM_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const blm::LavgTail t = {targets, hsum, nll_s, rows, s, s == S - 1 ? 1 : 0, (float)std::log((double)S)};
-  const bool vec = ((ld | ld_acc) & 3) == 0 && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(acc)) & 15) == 0;
+  const bool vec = ((ld | ld_acc) & 3) == 0 && blm::aligned16(logits, acc);
   if (vec && V <= 4096 * 3)
     hipLaunchKernelGGL(blm::logp_avg_row_kernel<3>, dim3(rows), dim3(1024), 0, st, logits, (long)ld, acc, (long)ld_acc, V, t);
   else if (vec && V <= 4096 * 9)

@@ -343,7 +343,6 @@ static int grid_for(long work_items) {
 
 using namespace blm;
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" int blm_sample_weight(const float* mu, int64_t rows, int64_t cols, const blm_variational* v, float* w_out,
                                  float* kl_out, float kl_weight, void* stream) {
@@ -355,8 +354,7 @@ extern "C" int blm_sample_weight(const float* mu, int64_t rows, int64_t cols, co
   if (kl_out && !v->lgstd) return blm_fail(BLM_ERR_INVALID, "blm_sample_weight: KL requested without lgstd");
   const float kl_scale = v->srows > 0 ? 0.5f * kl_weight / ((float)v->srows * (float)cols) : 0.f;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = (cols % 4 == 0) && al16(mu) && (!w_out || al16(w_out)) && (!v->lgstd || al16(v->lgstd)) &&
-                   (!v->eps || al16(v->eps));
+  const bool vec = (cols % 4 == 0) && aligned16(mu, w_out, v->lgstd, v->eps);
   const bool det = kl_out && blm::option(blm::OPT_DETERMINISTIC);
   const int g = grid_for(vec ? rows * cols / 4 : rows * cols);  // <= 2048 <= KL_DET_SLOTS
   if (vec)
@@ -383,9 +381,9 @@ static int var_group_pack(const blm_var_item* items, int32_t n, bool bwd, VarGro
     if (it.kl_weight != 0.f && !it.v.lgstd) return blm_fail(BLM_ERR_INVALID, "%s: item %d: KL requested without lgstd", who, i);
     if (bwd && it.dlgstd && !it.v.lgstd) return blm_fail(BLM_ERR_INVALID, "%s: item %d: dlgstd without lgstd", who, i);
     p.it[i] = it;
-    bool vec = it.cols % 4 == 0 && al16(it.mu) && (!it.v.lgstd || al16(it.v.lgstd)) && (!it.v.eps || al16(it.v.eps));
-    if (bwd) vec = vec && (!it.dw || al16(it.dw)) && (!it.dmu || al16(it.dmu)) && (!it.dlgstd || al16(it.dlgstd));
-    else vec = vec && (!it.w_out || al16(it.w_out));
+    bool vec = it.cols % 4 == 0 && aligned16(it.mu, it.v.lgstd, it.v.eps);
+    if (bwd) vec = vec && aligned16(it.dw, it.dmu, it.dlgstd);
+    else vec = vec && aligned16(it.w_out);
     p.vec[i] = vec ? 1 : 0;
     const long work = it.rows * it.cols / (vec ? 4 : 1);
     if (work > most) most = work;
@@ -573,7 +571,7 @@ extern "C" int blm_kl_mean_fwd(const float* mu, int64_t ld_mu, const float* lgst
   const bool det = blm::option(blm::OPT_DETERMINISTIC) != 0;  // block partials + one fixed-order finishing block instead of atomics
   hipStream_t st = static_cast<hipStream_t>(stream);
   int blocks;
-  if (ld_mu == cols && (rows * cols) % 4 == 0 && al16(mu) && al16(lgstd)) {
+  if (ld_mu == cols && (rows * cols) % 4 == 0 && aligned16(mu, lgstd)) {
     const long n4 = rows * cols / 4;
     blocks = grid_for(n4 / 4 + 1) < 512 ? grid_for(n4 / 4 + 1) : 512;
     hipLaunchKernelGGL(kl_fwd_flat4_kernel, dim3(blocks), dim3(TPB), 0, st, reinterpret_cast<const float4*>(mu),
