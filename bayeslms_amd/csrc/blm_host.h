@@ -17,6 +17,7 @@ int blm_fail(int status, const char* fmt, ...);
 // passes.  An entry point accepts extents in [0, 2^30] whose product is at most 2^40 elements (4 TB of fp32: far beyond the
 // 288 GB of HBM), and says BLM_ERR_INVALID otherwise.
 #include <initializer_list>
+#include <type_traits>
 namespace blm {
 constexpr long kMaxExtent = 1L << 30, kMaxElems = 1L << 40;
 inline bool extents_ok(std::initializer_list<long> dims) {
@@ -34,6 +35,15 @@ inline bool extents_ok(std::initializer_list<long> dims) {
 template <class... P>
 inline bool aligned16(const P*... p) {
   return ((reinterpret_cast<uintptr_t>(p) | ... | uintptr_t(0)) & 15) == 0;
+}
+// f(std::integral_constant<int, J>) for the built slot count J of 1, 2, 4, 8 that holds `count` values (temperatures, thetas,
+// draws): 1 -> 1, 2 -> 2, 3..4 -> 4, 5..8 -> 8.  The entry point has checked 1 <= count <= 8, with its own message.
+template <class F>
+inline void for_slots(int count, F&& f) {
+  if (count == 1) f(std::integral_constant<int, 1>{});
+  else if (count == 2) f(std::integral_constant<int, 2>{});
+  else if (count <= 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
 }
 // The bytes [first, last) that an (M, V) float matrix at row stride ld touches (M >= 1), and the two questions the entry points
 // ask of them: do two matrices share a byte, and may a result d be written where an operand z is read -- only over z itself,

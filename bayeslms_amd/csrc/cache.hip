@@ -264,15 +264,11 @@ extern "C" int blm_cache_scores(const float* q, int64_t ldq, const float* k, int
   p.q = q, p.ldq = (long)ldq, p.k = k, p.ldk = (long)ldk;
   p.label = label, p.tgt = tgt, p.lo = lo, p.hi = hi;
   p.window = window, p.M = M, p.Nk = Nk, p.K = K;
-  p.vq = (reinterpret_cast<uintptr_t>(q) & 15) == 0 && ldq % 4 == 0;
-  p.vk = (reinterpret_cast<uintptr_t>(k) & 15) == 0 && ldk % 4 == 0;
+  p.vq = blm::aligned16(q) && ldq % 4 == 0;
+  p.vk = blm::aligned16(k) && ldk % 4 == 0;
   p.lse = lse, p.match = match;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int J = thetas->count;
-  if (J == 1) blm::launch_cache<1>(p, thetas, st);
-  else if (J == 2) blm::launch_cache<2>(p, thetas, st);
-  else if (J <= 4) blm::launch_cache<4>(p, thetas, st);
-  else blm::launch_cache<8>(p, thetas, st);
+  blm::for_slots(thetas->count, [&](auto J) { blm::launch_cache<J()>(p, thetas, st); });
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

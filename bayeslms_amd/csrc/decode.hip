@@ -297,7 +297,7 @@ extern "C" int blm_attn_decode(const float* q, int64_t ld_q, const float* kv, co
          1.0f / sqrtf((float)head_dim)};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(p.nchunks, N * nhead, (Tq + kRows - 1) / kRows);
-  if (head_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(kv) & 15) == 0)
+  if (head_dim % 4 == 0 && blm::aligned16(kv))
     hipLaunchKernelGGL(attn_decode_part_kernel<true>, grid, dim3(kThreads), 0, st, p);
   else
     hipLaunchKernelGGL(attn_decode_part_kernel<false>, grid, dim3(kThreads), 0, st, p);

@@ -12,6 +12,7 @@
 
 #include "blm_device.h"
 #include "blm_host.h"
+#include "blm_rowstat.h"
 
 namespace blm {
 namespace {
@@ -124,107 +125,36 @@ __device__ __forceinline__ float link_y(float z, float var) {
   return __builtin_fmaf(0.5f, var, z);
 }
 
-// rowstats.hip's online state with one more sum: w = sum exp(y - m) var
-struct LAcc {
-  float m, s, t, w;
-  int am, cnt, bad;
-};
-
-__device__ __forceinline__ void lrescale(LAcc& a, float M) {
-  if (a.m > -INFINITY) {
-    const float d = a.m - M, f = __expf(d);
-    a.t = f * (a.t + d * a.s);
-    a.s *= f;
-    a.w *= f;
+// y = link(z, var) of the row's columns, formed in registers; the variance rides beside it
+template <int LINK>
+struct LinkCols {
+  const float *zr, *vr;
+  __device__ __forceinline__ float one(int c, float& var) const {
+    var = vr[c];
+    return link_y<LINK>(zr[c], var);
   }
-  a.m = M;
-}
-
-__device__ __forceinline__ void ladd(LAcc& a, float y, float var, int c, float tv, int tg) {
-  const float d = y - a.m, e = __expf(d);
-  const bool fin = y > -INFINITY;  // false for NaN too
-  a.s += fin ? e : 0.f;
-  a.t += fin ? e * d : 0.f;
-  a.w += fin ? e * var : 0.f;
-  a.bad |= (y != y) || !(var >= 0.f && var < INFINITY);
-  a.cnt += (y > tv || (y == tv && c < tg)) ? 1 : 0;
-}
-
-__device__ __forceinline__ void lmerge(LAcc& a, const LAcc& b) {
-  const float M = fmaxf(a.m, b.m);
-  if (b.m > a.m || (b.m == a.m && b.am < a.am)) a.am = b.am;  // before a.m moves
-  LAcc o = b;
-  if (a.m < M) lrescale(a, M);
-  if (o.m < M) lrescale(o, M);
-  a.s += o.s;
-  a.t += o.t;
-  a.w += o.w;
-  a.cnt += b.cnt;
-  a.bad |= b.bad;
-}
+  __device__ __forceinline__ float4 quad(int i, float4& vv) const {
+    const float4 zz = reinterpret_cast<const float4*>(zr)[i];
+    vv = reinterpret_cast<const float4*>(vr)[i];
+    return make_float4(link_y<LINK>(zz.x, vv.x), link_y<LINK>(zz.y, vv.y), link_y<LINK>(zz.z, vv.z), link_y<LINK>(zz.w, vv.w));
+  }
+};
 
 template <int LINK>
 __global__ __launch_bounds__(LP_TPB) void laplace_row_stats_kernel(const float* z, long ldz, const float* var, long ldv,
                                                                    const int64_t* tgt, int V, int vec, float* nll, float* conf,
                                                                    float* entropy, int32_t* pred, int32_t* rank, float* vbar) {
-  __shared__ LAcc red[LP_WAVES];
+  __shared__ RowAccW red[LP_WAVES];
   const int row = blockIdx.x;
-  const float* zr = z + (long)row * ldz;
-  const float* vr = var + (long)row * ldv;
-  const int64_t t64 = tgt ? tgt[row] : -1;
-  const bool has_t = t64 >= 0 && t64 < V;
-  const int tg = has_t ? (int)t64 : -1;
-  const float tv = has_t ? link_y<LINK>(zr[tg], vr[tg]) : NAN;  // NaN compares false: nothing is counted without a target
-  LAcc a{-INFINITY, 0.f, 0.f, 0.f, 0x7fffffff, 0, 0};
+  const LinkCols<LINK> src{z + (long)row * ldz, var + (long)row * ldv};
+  const RowTarget t = row_target(tgt, row, V, src);
+  RowAccW a{{}, -INFINITY, 0.f, 0.f, 0.f, kNone, 0, 0};
   const int n4 = vec ? (V >> 2) : 0;
-  for (int i = threadIdx.x; i < n4; i += LP_TPB) {
-    const float4 zz = reinterpret_cast<const float4*>(zr)[i];
-    const float4 vv = reinterpret_cast<const float4*>(vr)[i];
-    const int c = 4 * i;
-    const float4 y = make_float4(link_y<LINK>(zz.x, vv.x), link_y<LINK>(zz.y, vv.y), link_y<LINK>(zz.z, vv.z), link_y<LINK>(zz.w, vv.w));
-    const float cm = fmaxf(fmaxf(y.x, y.y), fmaxf(y.z, y.w));
-    if (cm > a.m) {
-      lrescale(a, cm);
-      a.am = c + (y.x == cm ? 0 : (y.y == cm ? 1 : (y.z == cm ? 2 : 3)));
-    }
-    ladd(a, y.x, vv.x, c, tv, tg);
-    ladd(a, y.y, vv.y, c + 1, tv, tg);
-    ladd(a, y.z, vv.z, c + 2, tv, tg);
-    ladd(a, y.w, vv.w, c + 3, tv, tg);
-  }
-  for (int c = 4 * n4 + threadIdx.x; c < V; c += LP_TPB) {  // the V % 4 last columns, or the whole row on the scalar path
-    const float v = vr[c], y = link_y<LINK>(zr[c], v);
-    if (y > a.m) {
-      lrescale(a, y);
-      a.am = c;
-    }
-    ladd(a, y, v, c, tv, tg);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    LAcc b;
-    b.m = __shfl_xor(a.m, o, 64);
-    b.s = __shfl_xor(a.s, o, 64);
-    b.t = __shfl_xor(a.t, o, 64);
-    b.w = __shfl_xor(a.w, o, 64);
-    b.am = __shfl_xor(a.am, o, 64);
-    b.cnt = __shfl_xor(a.cnt, o, 64);
-    b.bad = __shfl_xor(a.bad, o, 64);
-    lmerge(a, b);
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) red[w] = a;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  for (int k = 1; k < LP_WAVES; ++k) lmerge(a, red[k]);
-  const float ls = logf(a.s);
-  const bool bad = a.bad != 0;
-  if (nll) nll[row] = (bad || !has_t) ? NAN : (a.m - tv) + ls;
-  if (conf) conf[row] = bad ? NAN : 1.0f / a.s;
-  if (entropy) entropy[row] = bad ? NAN : ls - a.t / a.s;
-  if (pred) pred[row] = bad ? -1 : a.am;
-  if (rank) rank[row] = (bad || !has_t) ? -1 : a.cnt;
-  if (vbar) vbar[row] = bad ? NAN : a.w / a.s;
+  a = row_quads<LP_TPB>(a, src, n4, t);
+  row_columns<LP_TPB>(a, src, 4 * n4 + threadIdx.x, V, t);  // the V % 4 last columns, or the whole row on the scalar path
+  if (!row_state_fold<LP_TPB>(a, red)) return;
+  row_finish(row, a, t, nll, conf, entropy, pred, rank);
+  if (vbar) vbar[row] = a.bad ? NAN : a.w / a.s;
 }
 
 // ---------------------------------------------------------------- Monte-Carlo link

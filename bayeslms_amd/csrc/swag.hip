@@ -355,11 +355,9 @@ extern "C" int blm_swag_sample(float* out, int64_t ld_out, const float* mean, co
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(blm::swag_grid((long)n_floats)), block(blm::SWAG_TPB);
   const long n = (long)n_floats, lo = (long)ld_out, ldd = (long)ld_dev;
-  const int c = draw->count;
-  if (c == 1) hipLaunchKernelGGL((blm::swag_sample_kernel<1>), grid, block, 0, st, out, lo, mean, m2, dev, ldd, k_live, z2, n, *draw);
-  else if (c == 2) hipLaunchKernelGGL((blm::swag_sample_kernel<2>), grid, block, 0, st, out, lo, mean, m2, dev, ldd, k_live, z2, n, *draw);
-  else if (c <= 4) hipLaunchKernelGGL((blm::swag_sample_kernel<4>), grid, block, 0, st, out, lo, mean, m2, dev, ldd, k_live, z2, n, *draw);
-  else hipLaunchKernelGGL((blm::swag_sample_kernel<8>), grid, block, 0, st, out, lo, mean, m2, dev, ldd, k_live, z2, n, *draw);
+  blm::for_slots(draw->count, [&](auto J) {
+    hipLaunchKernelGGL((blm::swag_sample_kernel<J()>), grid, block, 0, st, out, lo, mean, m2, dev, ldd, k_live, z2, n, *draw);
+  });
   BLM_HIP(hipGetLastError());
   return BLM_OK;
 }

@@ -260,6 +260,70 @@ def _weight(t, name, in_place=False):
     return _f32(t, name)
 
 
+def _rows_in_place(who, name, t, V=None, copy=False, overlap=False):
+    """The operand check of the row kernels that take a row stride: ``t`` as a 2-D float32 device matrix with unit inner stride
+    whose first V columns (default: all) are used -> (tensor, R, V, row stride as the kernel takes it).  A view of padded rows
+    is read where it lies, after the device checks of the product path on its first row.  ``copy`` (a read-only operand):
+    anything else goes through `_f32`, which copies a non-contiguous tensor; without it (an operand used in place) anything else
+    is refused, and so are rows that overlap (row stride < V) unless ``overlap`` leaves that to the library."""
+    label = "%s: %s" % (who, name)
+    ok = torch.is_tensor(t) and t.dim() == 2 and t.stride(-1) == 1
+    if ok and (not copy or t.stride(0) >= t.shape[1]):
+        dev_tensor(t[:1], label)  # the view itself is what the kernel reads
+    elif copy and torch.is_tensor(t):
+        t = _f32(t, label)
+        ok = t.dim() == 2 and t.stride(-1) == 1
+    if not ok:
+        raise BayesLMError("%s must be a row-major (R, V) matrix with unit inner stride" % label)
+    R, V, given = t.shape[0], int(V if V is not None else t.shape[1]), V is not None
+    if given and not 1 <= V <= t.shape[1]:  # a matrix without columns is the library's to refuse, or to accept
+        raise BayesLMError("%s: V = %d outside [1, %d], the columns of %s" % (who, V, t.shape[1], name))
+    ld = t.stride(0) if R > 1 else max(t.stride(0), V)  # a single row has no stride to honour: torch may report any
+    if ld < V and not copy and not overlap:
+        raise BayesLMError("%s: the rows of %s overlap (row stride %d < %d)" % (who, name, ld, V))
+    return t, R, V, ld
+
+
+def _rows_pair(who, na, a, nb, b, V, overlap=False):
+    """Two operands of `_rows_in_place`, both used in place, with one row count -> (R, V, row stride of a, of b)"""
+    _, R, V, lda = _rows_in_place(who, na, a, V, overlap=overlap)
+    _, Rb, _, ldb = _rows_in_place(who, nb, b, V, overlap=overlap)
+    if Rb != R:
+        raise BayesLMError("%s: %s has %d rows, %s %d" % (who, na, R, nb, Rb))
+    return R, V, lda, ldb
+
+
+def _row_targets(who, targets, R):
+    """(R,) int64 device targets, one per row, or None"""
+    if targets is None:
+        return None
+    tgt = dev_tensor(targets.reshape(-1), "%s: targets" % who, torch.int64)
+    if tgt.numel() != R:
+        raise BayesLMError("%s: %d targets for %d rows" % (who, tgt.numel(), R))
+    return tgt
+
+
+def _slots(what, struct, field, arg, values, bound, strict, noun, entry):
+    """The ABI struct of the 1..bound values ``entry`` takes per launch (``noun``s: inverse temperatures, thetas): finite
+    float32 numbers > 0 (``strict``) or >= 0, each rounded to float32 once."""
+    above = (lambda v: v > 0.0) if strict else (lambda v: v >= 0.0)
+    kind = "finite float32 number %s 0" % (">" if strict else ">=")
+    try:
+        vs = [float(v) for v in values]
+    except (TypeError, ValueError):
+        raise BayesLMError("%s: %s must be 1..%d %ss, each a %s, got %r" % (what, arg, bound, noun, kind, values))
+    if not 1 <= len(vs) <= bound:
+        raise BayesLMError("%s: %d %ss, %s takes 1..%d per launch" % (what, len(vs), noun, entry, bound))
+    t = struct()
+    t.abi_version, t.count = L.ABI_VERSION, len(vs)
+    slot = getattr(t, field)
+    for j, v in enumerate(vs):
+        slot[j] = v if math.isfinite(v) else 0.0  # ctypes rounds to float32 (an overflow to inf, an underflow to 0 is caught below)
+        if not (math.isfinite(v) and above(v) and above(slot[j]) and slot[j] < math.inf):
+            raise BayesLMError("%s: %s[%d] = %r is not a %s" % (what, arg, j, v, kind))
+    return t
+
+
 def _rows2d(t, N, name):
     """-> ((M, N) view of ``t``, its row stride).  The logits of a vocabulary that is not a multiple of 4 words (wikitext-2: 33278)
     live in a buffer whose rows are padded to one (below): the kernels take the row stride, so such a tensor is used as it is; any
@@ -2375,31 +2439,30 @@ def row_stats(x, targets=None, V=None):
     logits or log-probabilities -- the row is normalised by the kernel -- from one read of x (blm_row_stats; row stride honoured:
     padded rows, and a (R, V) view of padded rows, are read in place).  ``targets`` (R,) int64 or None.  A row that holds a NaN
     is NaN / -1 throughout.  Bit-identical run to run.  -> RowStats"""
-    if torch.is_tensor(x) and x.dim() == 2 and x.stride(-1) == 1 and x.stride(0) >= x.shape[1] and not x.is_contiguous():
-        dev_tensor(x[:1], "x")  # the device checks of the product path; the view itself is what the kernel reads
+    return _row_stats("row_stats", x, targets, V)
+
+
+def _row_stats(who, x, targets, V, temps=None):
+    """row_stats, and with ``temps`` (a blm_row_temps struct) row_stats_temps, whose float figures are (J, R)"""
+    x, R, V, ld = _rows_in_place(who, "x", x, V, copy=True)
+    tgt = _row_targets(who, targets, R)
+    figure = lambda: torch.empty(*(() if temps is None else (temps.count,)), R, device=x.device, dtype=torch.float32)  # noqa: E731
+    index = lambda: torch.empty(R, device=x.device, dtype=torch.int32)  # noqa: E731
+    conf, entropy, pred = figure(), figure(), index()
+    nll, rank = (None, None) if tgt is None else (figure(), index())
+    if temps is None:
+        out = RowStats(nll, conf, entropy, pred, rank)
     else:
-        x = _f32(x, "x")
-    if x.dim() != 2 or x.stride(-1) != 1:
-        raise BayesLMError("row_stats: a row-major (R, V) matrix expected")
-    R, V = x.shape[0], int(V if V is not None else x.shape[1])
-    if not 1 <= V <= x.shape[1]:
-        raise BayesLMError("row_stats: V = %d outside [1, %d], the columns of x" % (V, x.shape[1]))
-    dev = x.device
-    conf, entropy = (torch.empty(R, device=dev, dtype=torch.float32) for _ in range(2))
-    pred = torch.empty(R, device=dev, dtype=torch.int32)
-    tgt = nll = rank = None
-    if targets is not None:
-        tgt = dev_tensor(targets.reshape(-1), "targets", torch.int64)
-        if tgt.numel() != R:
-            raise BayesLMError("row_stats: %d targets for %d rows" % (tgt.numel(), R))
-        nll = torch.empty(R, device=dev, dtype=torch.float32)
-        rank = torch.empty(R, device=dev, dtype=torch.int32)
+        out = RowStatsTemps(nll, conf, entropy, None if tgt is None else figure(), pred, rank)
     if R == 0:
-        return RowStats(nll, conf, entropy, pred, rank)
+        return out
     L.require_gfx950()
-    calls().blm_row_stats(ptr(x), x.stride(0) if R > 1 else max(x.stride(0), V), ptr(tgt), R, V, ptr(nll), ptr(conf), ptr(entropy),
-                          ptr(pred), ptr(rank), stream())
-    return RowStats(nll, conf, entropy, pred, rank)
+    if temps is None:
+        calls().blm_row_stats(ptr(x), ld, ptr(tgt), R, V, ptr(nll), ptr(conf), ptr(entropy), ptr(pred), ptr(rank), stream())
+    else:
+        calls().blm_row_stats_temps(ptr(x), ld, ptr(tgt), R, V, C.byref(temps), ptr(nll), ptr(conf), ptr(entropy), ptr(out.dnll),
+                                    ptr(pred), ptr(rank), stream())
+    return out
 
 
 class RowStatsTemps(NamedTuple):
@@ -2415,19 +2478,7 @@ class RowStatsTemps(NamedTuple):
 
 def row_temps(betas, what="row_stats_temps"):
     """The blm_row_temps struct of 1..8 positive finite inverse temperatures, each rounded to float32 once."""
-    try:
-        bs = [float(b) for b in betas]
-    except (TypeError, ValueError):
-        raise BayesLMError("%s: betas must be 1..%d positive finite numbers, got %r" % (what, L.ROW_TEMPS_MAX, betas))
-    if not 1 <= len(bs) <= L.ROW_TEMPS_MAX:
-        raise BayesLMError("%s: %d inverse temperatures, blm_row_stats_temps takes 1..%d per launch" % (what, len(bs), L.ROW_TEMPS_MAX))
-    t = L.RowTemps()
-    t.abi_version, t.count = L.ABI_VERSION, len(bs)
-    for j, b in enumerate(bs):
-        t.beta[j] = b if math.isfinite(b) else 0.0  # ctypes rounds to float32 (an overflow to inf is caught below)
-        if not (math.isfinite(b) and b > 0.0 and 0.0 < t.beta[j] < math.inf):
-            raise BayesLMError("%s: betas[%d] = %r is not a positive finite float32 inverse temperature" % (what, j, b))
-    return t
+    return _slots(what, L.RowTemps, "beta", "betas", betas, L.ROW_TEMPS_MAX, True, "inverse temperature", "blm_row_stats_temps")
 
 
 def row_stats_temps(x, betas, targets=None, V=None):
@@ -2435,33 +2486,7 @@ def row_stats_temps(x, betas, targets=None, V=None):
     (blm_row_stats_temps): per temperature the NLL of the target, the confidence, the entropy and d nll / d beta of the tempered
     distribution p ~ exp(beta x); prediction and rank do not depend on beta.  Argument rules of row_stats (row stride honoured).
     Temperature j's figures are bit-identical whatever else is in the list.  -> RowStatsTemps"""
-    temps = row_temps(betas)
-    J = temps.count
-    if torch.is_tensor(x) and x.dim() == 2 and x.stride(-1) == 1 and x.stride(0) >= x.shape[1] and not x.is_contiguous():
-        dev_tensor(x[:1], "x")  # the device checks of the product path; the view itself is what the kernel reads
-    else:
-        x = _f32(x, "x")
-    if x.dim() != 2 or x.stride(-1) != 1:
-        raise BayesLMError("row_stats_temps: a row-major (R, V) matrix expected")
-    R, V = x.shape[0], int(V if V is not None else x.shape[1])
-    if not 1 <= V <= x.shape[1]:
-        raise BayesLMError("row_stats_temps: V = %d outside [1, %d], the columns of x" % (V, x.shape[1]))
-    dev = x.device
-    conf, entropy = (torch.empty(J, R, device=dev, dtype=torch.float32) for _ in range(2))
-    pred = torch.empty(R, device=dev, dtype=torch.int32)
-    tgt = nll = dnll = rank = None
-    if targets is not None:
-        tgt = dev_tensor(targets.reshape(-1), "targets", torch.int64)
-        if tgt.numel() != R:
-            raise BayesLMError("row_stats_temps: %d targets for %d rows" % (tgt.numel(), R))
-        nll, dnll = (torch.empty(J, R, device=dev, dtype=torch.float32) for _ in range(2))
-        rank = torch.empty(R, device=dev, dtype=torch.int32)
-    if R == 0:
-        return RowStatsTemps(nll, conf, entropy, dnll, pred, rank)
-    L.require_gfx950()
-    calls().blm_row_stats_temps(ptr(x), x.stride(0) if R > 1 else max(x.stride(0), V), ptr(tgt), R, V, C.byref(temps), ptr(nll),
-                                ptr(conf), ptr(entropy), ptr(dnll), ptr(pred), ptr(rank), stream())
-    return RowStatsTemps(nll, conf, entropy, dnll, pred, rank)
+    return _row_stats("row_stats_temps", x, targets, V, row_temps(betas))
 
 
 class CacheScores(NamedTuple):
@@ -2472,30 +2497,7 @@ class CacheScores(NamedTuple):
 
 def cache_thetas(thetas, what="cache_scores"):
     """The blm_cache_thetas struct of 1..8 finite thetas >= 0, each rounded to float32 once."""
-    try:
-        ts = [float(t) for t in thetas]
-    except (TypeError, ValueError):
-        raise BayesLMError("%s: thetas must be 1..%d finite numbers >= 0, got %r" % (what, L.CACHE_THETAS_MAX, thetas))
-    if not 1 <= len(ts) <= L.CACHE_THETAS_MAX:
-        raise BayesLMError("%s: %d thetas, blm_cache_scores takes 1..%d per launch" % (what, len(ts), L.CACHE_THETAS_MAX))
-    t = L.CacheThetas()
-    t.abi_version, t.count = L.ABI_VERSION, len(ts)
-    for j, v in enumerate(ts):
-        t.theta[j] = v if math.isfinite(v) else 0.0  # ctypes rounds to float32 (an overflow to inf is caught below)
-        if not (math.isfinite(v) and v >= 0.0 and t.theta[j] < math.inf):
-            raise BayesLMError("%s: thetas[%d] = %r is not a finite float32 number >= 0" % (what, j, v))
-    return t
-
-
-def _cache_rows(t, name):
-    """(rows, K) fp32 with unit inner stride, read in place where its row stride allows (a view of padded rows)"""
-    if torch.is_tensor(t) and t.dim() == 2 and t.stride(-1) == 1 and t.stride(0) >= t.shape[1] and not t.is_contiguous():
-        dev_tensor(t[:1], name)  # the device checks of the product path; the view itself is what the kernel reads
-        return t
-    t = _f32(t, name)
-    if t.dim() != 2:
-        raise BayesLMError("cache_scores: %s must be a (rows, K) matrix" % name)
-    return t if t.stride(-1) == 1 else t.contiguous()
+    return _slots(what, L.CacheThetas, "theta", "thetas", thetas, L.CACHE_THETAS_MAX, False, "theta", "blm_cache_scores")
 
 
 def cache_scores(q, k, labels, targets, hi, thetas, window, lo=None):
@@ -2509,9 +2511,7 @@ def cache_scores(q, k, labels, targets, hi, thetas, window, lo=None):
     J, window = th.count, int(window)
     if window < 1:
         raise BayesLMError("cache_scores: window = %d, at least one key is needed" % window)
-    q, k = _cache_rows(q, "q"), _cache_rows(k, "k")
-    M, K = q.shape
-    Nk = k.shape[0]
+    (q, M, K, ldq), (k, Nk, _, ldk) = (_rows_in_place("cache_scores", n, t, copy=True) for n, t in (("q", q), ("k", k)))
     if K < 1 or k.shape[1] != K:
         raise BayesLMError("cache_scores: q is (%d, %d) and k is (%d, %d): one width K >= 1 expected" % (M, K, Nk, k.shape[1]))
     labels = dev_tensor(labels.reshape(-1), "labels", torch.int64)
@@ -2525,7 +2525,6 @@ def cache_scores(q, k, labels, targets, hi, thetas, window, lo=None):
     if M == 0 or Nk == 0:  # nothing to launch: no query, or no key for any of them
         return CacheScores(lse.fill_(-math.inf), match.fill_(-math.inf))
     L.require_gfx950()
-    ldq, ldk = (q.stride(0) if M > 1 else max(q.stride(0), K)), (k.stride(0) if Nk > 1 else max(k.stride(0), K))
     chunks = _row_chunks(M, ldq)
     for r0, r1 in chunks:
         one = len(chunks) == 1
@@ -2621,15 +2620,11 @@ def dyneval_update(p, g, p0, lr, decay, rms=None, mean=None, eps=0.01, zero_grad
 
 
 def _swag_rows(who, name, t, n):
-    """A (rows, >= n) float32 device matrix with unit inner stride, used in place (a row of it may start at any float) -> its
-    row stride as the kernel takes it"""
-    if not torch.is_tensor(t) or t.dim() != 2 or t.stride(-1) != 1 or t.shape[1] != n:
+    """A (rows, n) float32 device matrix used in place (a row of it may start at any float) -> its row stride as the kernel
+    takes it"""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != n:
         raise BayesLMError("%s: %s must be a (rows, %d) matrix with unit inner stride" % (who, name, n))
-    dev_tensor(t[:1], "%s: %s" % (who, name))
-    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), n)
-    if ld < n:
-        raise BayesLMError("%s: the rows of %s overlap (row stride %d < %d)" % (who, name, ld, n))
-    return ld
+    return _rows_in_place(who, name, t)[3]
 
 
 def swag_collect(theta, mean, m2, count, dev_row=None):
@@ -2712,29 +2707,20 @@ def logp_avg_accum(logits, acc, s, S, targets=None, hsum=None, nll_s=None, V=Non
     logaddexp(acc, logp) after, less log S at s = S - 1: log mean_s p_s once every sample is in.  ``hsum`` (R,) gathers the
     samples' entropies the same way; ``nll_s`` (S, R) gets row s = -logp[r, targets[r]] (0 for a target outside [0, V)).
     Row strides are honoured; both matrices are used in place.  The same bits in every run."""
-    for name, t in (("logits", logits), ("acc", acc)):
-        if not torch.is_tensor(t) or t.dim() != 2 or t.stride(-1) != 1:
-            raise BayesLMError("logp_avg_accum: %s must be a row-major (R, V) matrix" % name)
-        dev_tensor(t[:1], "logp_avg_accum: %s" % name)
-    R, V = logits.shape[0], int(V if V is not None else logits.shape[1])
-    if acc.shape[0] != R or not 1 <= V <= min(logits.shape[1], acc.shape[1]):
-        raise BayesLMError("logp_avg_accum: logits %s, acc %s, V = %d" % (tuple(logits.shape), tuple(acc.shape), V))
+    R, V, ld, lda = _rows_pair("logp_avg_accum", "logits", logits, "acc", acc, V, overlap=True)  # the library refuses overlap
     s, S = int(s), int(S)
     if not (1 <= S <= L.SWAG_SAMPLES_MAX and 0 <= s < S):
         raise BayesLMError("logp_avg_accum: sample %d of %d (1..%d samples)" % (s, S, L.SWAG_SAMPLES_MAX))
     if (targets is None) != (nll_s is None):
         raise BayesLMError("logp_avg_accum: targets and nll_s go together")
-    tgt = None
-    if targets is not None:
-        tgt = dev_tensor(targets.reshape(-1), "logp_avg_accum: targets", torch.int64)
-        if dev_tensor(nll_s, "logp_avg_accum: nll_s") is not nll_s or tuple(nll_s.shape) != (S, R) or tgt.numel() != R:
-            raise BayesLMError("logp_avg_accum: nll_s must be a contiguous (%d, %d) matrix beside %d targets" % (S, R, R))
+    tgt = _row_targets("logp_avg_accum", targets, R)
+    if tgt is not None and (dev_tensor(nll_s, "logp_avg_accum: nll_s") is not nll_s or tuple(nll_s.shape) != (S, R)):
+        raise BayesLMError("logp_avg_accum: nll_s must be a contiguous (%d, %d) matrix beside %d targets" % (S, R, R))
     if hsum is not None and (dev_tensor(hsum, "logp_avg_accum: hsum") is not hsum or hsum.numel() != R):
         raise BayesLMError("logp_avg_accum: hsum must be a contiguous array of %d" % R)
     if R == 0:
         return acc
     L.require_gfx950()
-    ld, lda = ((t.stride(0) if R > 1 else max(t.stride(0), V)) for t in (logits, acc))
     calls().blm_logp_avg_accum(ptr(logits), ld, ptr(acc), lda, ptr(tgt), R, V, s, S, ptr(hsum), ptr(nll_s), stream())
     return acc
 
@@ -2742,40 +2728,16 @@ def logp_avg_accum(logits, acc, s, S, targets=None, hsum=None, nll_s=None, V=Non
 # ----------------------------------------------------------------------------
 # last-layer Laplace posterior: the three row kernels of csrc/laplace.hip (definitions: include/bayeslm.h)
 # ----------------------------------------------------------------------------
-def _laplace_rows(who, name, t, V=None):
-    """A row-major (R, >= V) float32 device matrix, used in place whatever its row stride and base -> (R, V, row stride as the
-    kernel takes it)"""
-    if not torch.is_tensor(t) or t.dim() != 2 or t.stride(-1) != 1:
-        raise BayesLMError("%s: %s must be a row-major (R, V) matrix" % (who, name))
-    dev_tensor(t[:1], "%s: %s" % (who, name))
-    R, V = t.shape[0], int(V if V is not None else t.shape[1])
-    if not 1 <= V <= t.shape[1]:
-        raise BayesLMError("%s: V = %d outside [1, %d], the columns of %s" % (who, V, t.shape[1], name))
-    ld = t.stride(0) if R > 1 else max(t.stride(0), V)
-    if ld < V:
-        raise BayesLMError("%s: the rows of %s overlap (row stride %d < %d)" % (who, name, ld, V))
-    return R, V, ld
-
-
-def _laplace_targets(who, targets, R):
-    if targets is None:
-        return None
-    tgt = dev_tensor(targets.reshape(-1), "%s: targets" % who, torch.int64)
-    if tgt.numel() != R:
-        raise BayesLMError("%s: %d targets for %d rows" % (who, tgt.numel(), R))
-    return tgt
-
-
 def laplace_curvature(logits, out=None, V=None):
     """a = p (1 - p), p = softmax of the first V columns of each row of ``logits`` (R, >= V) (blm_laplace_curvature): the diagonal
     Gauss-Newton factor of the decoder's Laplace posterior.  ``out`` None: a new (R, V) matrix; ``out`` the same tensor as
     ``logits``: in place; any other overlap is refused.  Row strides are honoured; where a row of ``out`` has room for them,
     the columns V .. Vq - 1 (V rounded up to 4) are written 0.  -> out"""
     who = "laplace_curvature"
-    R, V, ld = _laplace_rows(who, "logits", logits, V)
+    _, R, V, ld = _rows_in_place(who, "logits", logits, V)
     if out is None:
         out = torch.empty(R, V, device=logits.device, dtype=torch.float32)
-    Ro, _, lda = _laplace_rows(who, "out", out, V)
+    _, Ro, _, lda = _rows_in_place(who, "out", out, V)
     if Ro != R:
         raise BayesLMError("%s: logits has %d rows, out %d" % (who, R, Ro))
     if R == 0:
@@ -2795,14 +2757,6 @@ class LaplaceRowStats(NamedTuple):
     vbar: torch.Tensor            # (R,) float32 sum_v ptilde_v var_v
 
 
-def _laplace_pair(who, z, var, V):
-    R, V, ldz = _laplace_rows(who, "z", z, V)
-    Rv, _, ldv = _laplace_rows(who, "var", var, V)
-    if Rv != R:
-        raise BayesLMError("%s: z has %d rows, var %d" % (who, R, Rv))
-    return R, V, ldz, ldv
-
-
 def laplace_row_stats(z, var, targets=None, link="probit", V=None):
     """ops.row_stats of y = link(z, var) for every row of the logit means ``z`` and variances ``var`` (R, >= V), y formed in
     registers from one read of each (blm_laplace_row_stats).  ``link``: 'probit', y = z / sqrt(1 + pi / 8 var), or 'expexp',
@@ -2810,11 +2764,11 @@ def laplace_row_stats(z, var, targets=None, link="probit", V=None):
     who = "laplace_row_stats"
     if link not in L.LAPLACE_LINKS:
         raise BayesLMError("%s: link %r is neither 'probit' nor 'expexp' (the 'mc' link is laplace_mc_rows)" % (who, link))
-    R, V, ldz, ldv = _laplace_pair(who, z, var, V)
+    R, V, ldz, ldv = _rows_pair(who, "z", z, "var", var, V)
     dev = z.device
     conf, entropy, vbar = (torch.empty(R, device=dev, dtype=torch.float32) for _ in range(3))
     pred = torch.empty(R, device=dev, dtype=torch.int32)
-    tgt = _laplace_targets(who, targets, R)
+    tgt = _row_targets(who, targets, R)
     nll = rank = None
     if tgt is not None:
         nll = torch.empty(R, device=dev, dtype=torch.float32)
@@ -2848,11 +2802,11 @@ def laplace_mc_rows(z, var, samples, seed, targets=None, row0=0, V=None):
         raise BayesLMError("%s: samples = %d outside 1..%d" % (who, S, L.LAPLACE_SAMPLES_MAX))
     if not 0 <= row0 <= 1 << 40:
         raise BayesLMError("%s: row0 = %d outside 0..2^40" % (who, row0))
-    R, V, ldz, ldv = _laplace_pair(who, z, var, V)
+    R, V, ldz, ldv = _rows_pair(who, "z", z, "var", var, V)
     dev = z.device
     h_pred, mi, conf = (torch.empty(R, device=dev, dtype=torch.float32) for _ in range(3))
     pred = torch.empty(R, device=dev, dtype=torch.int32)
-    tgt = _laplace_targets(who, targets, R)
+    tgt = _row_targets(who, targets, R)
     bma = nll_s = rank = None
     if tgt is not None:
         bma = torch.empty(R, device=dev, dtype=torch.float32)
@@ -2954,18 +2908,12 @@ def topk_rows(x, k):
     """The k best entries of every row of the (R, V) matrix x, best first (blm_topk_rows): value descending, then index
     ascending, NaN below -inf; values are copied bit for bit.  1 <= k <= min(V, _lib.TOPK_MAX).
     -> (vals (R, k) float32, ids (R, k) int64)"""
-    if torch.is_tensor(x) and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.dtype == torch.float32:
-        dev_tensor(x[:1], "x", torch.float32)  # rows with a stride of their own (padded odd-vocabulary rows) are read in place
-    else:
-        x = _f32(x, "x")
-    if x.dim() != 2 or x.stride(-1) != 1:
-        raise BayesLMError("topk_rows: a row-major (R, V) matrix expected")
-    R, V = x.shape
+    x, R, V, ld = _rows_in_place("topk_rows", "x", x, copy=True)  # padded odd-vocabulary rows are read in place
     k = int(k)
     vals = torch.empty(R, k, device=x.device, dtype=torch.float32)
     ids = torch.empty(R, k, device=x.device, dtype=torch.int64)
     L.require_gfx950()
-    calls().blm_topk_rows(ptr(x), x.stride(0), R, V, k, ptr(vals), ptr(ids), stream())
+    calls().blm_topk_rows(ptr(x), ld, R, V, k, ptr(vals), ptr(ids), stream())
     return vals, ids
 
 
