@@ -35,6 +35,7 @@ STREAM_DROPOUT = 0x20000000
 STREAM_LRT = 0x30000000      # pre-activation noise of local reparameterisation (ops.bayes_linear_lrt), + site id
 STREAM_SWAG = 0x40000000     # a SWAG sample's noise: + 0 diagonal, + 1 low rank; the step is the sample id
 STREAM_LAPLACE = 0x50000000  # the logit noise of the last-layer Laplace predictive; the step is the sample id
+STREAM_SGMCMC = 0x60000000   # the Langevin noise of an SG-MCMC weight update; the step is the optimisation step
 
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
@@ -180,6 +181,7 @@ SIGNATURES = {
     "blm_swag_collect": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "blm_swag_sample": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _i64, C.POINTER(SwagDraw), _vp]),
     "blm_logp_avg_accum": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "blm_sgmcmc_update": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _rngp, _vp]),
     "blm_laplace_curvature": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp]),
     "blm_laplace_row_stats": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blm_laplace_mc_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _rngp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -604,6 +604,18 @@ class Trainer:
         self.fused_kl = fused_kl
         self.kl_layers = self._find_kl_layers()
         self.last_soft = None  # SoftStats of device scalars: the last distillation step's mean nll, soft loss and KL (step(soft=...))
+        self.sampler = None  # sgmcmc.Sampler: its update takes the place of clip + SGD (set_sampler)
+
+    def set_sampler(self, sampler):
+        """SG-MCMC: from the next step on ``sampler.update(self)`` (sgmcmc.Sampler: blm_sqnorm_multi + blm_sgmcmc_update, noise of
+        step = step_no) takes the place of ops.clip_sgd; None: clip + SGD again, its momentum buffer starting from zero.  Single
+        process only."""
+        if sampler is not None and self.world > 1:
+            raise ops.BayesLMError("Trainer.set_sampler: world size %d: data-parallel sampling is not built" % self.world)
+        if sampler is not None:
+            sampler.begin(self)
+        self.sampler = sampler
+        self.first = True
 
     def _find_kl_layers(self):
         from .model import BayesLinear
@@ -659,7 +671,10 @@ class Trainer:
             loss = mle + kl
             loss.backward()
         self.reducer.finish()
-        ops.clip_sgd(self.table, self.clip, self.lr, self.momentum, self.first, 1.0 / self.world, self.weight_decay)
+        if self.sampler is None:
+            ops.clip_sgd(self.table, self.clip, self.lr, self.momentum, self.first, 1.0 / self.world, self.weight_decay)
+        else:
+            self.sampler.update(self)
         self.first = False
         self.step_no += 1
         return loss.detach(), (kl.detach() if kl is not None else None), hidden
@@ -738,6 +753,7 @@ class EvalReport:
     mean_mi: Optional[float] = None        # mean mutual information between the word and the weights
     per_token: Optional[dict] = None       # keep_tokens: float / int arrays in text order, skipped tokens included (NaN / -1)
     swag: Optional[dict] = None            # SWAG (SwagPosterior.describe with scale, diag, samples, seed, path); None: the model's own weights
+    samples: Optional[dict] = None         # a bank of weight vectors (SampleBank.describe: SG-MCMC samples or an ensemble); None: none
     laplace: Optional[dict] = None         # last-layer Laplace (LaplacePosterior.describe with prior, link, samples, seed); None: none
     cache: Optional[dict] = None           # neural cache (CacheReport.as_dict, with the fit's block after fit_cache); None: no cache
     dyneval: Optional[dict] = None         # dynamic evaluation (DynEvalReport.as_dict beside the static loss, with the fit's block); None: none
@@ -746,7 +762,7 @@ class EvalReport:
     def as_dict(self):
         d = dataclasses.asdict(self)
         del d["per_token"]
-        for k in ("temperature", "cache", "dyneval", "swag", "laplace"):  # a run without one writes what it wrote before there was one
+        for k in ("temperature", "cache", "dyneval", "swag", "laplace", "samples"):  # a run without one writes what it wrote before there was one
             if d[k] is None:
                 del d[k]
         return d
@@ -1736,25 +1752,36 @@ def evaluate_swag(model, source, seq_len, posterior, samples, seed=1111, scale=0
     under mc_samples) reduces log pbar.  mi = H[pbar] - mean_s H[p_s], both untempered.
 
     Refused: samples outside 2..64, a world size above 1, noise source 'torch', a posterior made for another model."""
-    from .model import CarriedState, inference_decoder
     who = "evaluate_swag"
     S = int(samples)
     if not 2 <= S <= 64:
         raise ops.BayesLMError("%s: samples must lie in 2..64, got %d (the SWA mean alone is evaluate_report of "
                                "SwagPosterior.mean_state_dict)" % (who, S))
+
+    def draws(flat):
+        posterior.check(flat)
+        return posterior.draw(S, seed, scale, diag)
+
+    return _samples_walk(who, model, source, seq_len, S, draws, posterior.check, "a SWAG sample replaces every weight and runs",
+                         bins, temperature, keep_tokens)
+
+
+def _samples_walk(who, model, source, seq_len, S, draws_of, check, what, bins, temperature, keep_tokens):
+    """The walk evaluate_swag and evaluate_samples share: ``draws_of(flat)`` -> the (S, P) device matrix of weight vectors in the
+    layout of ``flat`` (the model re-homed), called once inside the re-homing; ``check(model)`` refuses another model first."""
+    from .model import CarriedState, inference_decoder
     if dist.is_initialized() and dist.get_world_size() > 1:
         raise ops.BayesLMError("%s runs in a single process (world size %d)" % (who, dist.get_world_size()))
     betas = _betas_of(who, temperature)
     dec = inference_decoder(model)
     if dec is None:
         raise ops.BayesLMError("%s: %s has no decoder that hands back its input rows" % (who, type(model).__name__))
-    posterior.check(model)
+    check(model)
     V = dec.weight.shape[0]
     keep = {k: [] for k in ("tgt", "nll", "conf", "entropy", "pred", "rank", "nll_s", "h_pred", "mi")}
     placed = []
-    with _rehomed(who, model, "a SWAG sample replaces every weight and runs") as flat:
-        posterior.check(flat)
-        draws = posterior.draw(S, seed, scale, diag)
+    with _rehomed(who, model, what) as flat:
+        draws = draws_of(flat)
         dev = flat.flat_param.device
         with torch.no_grad(), dec.inference(input_rows=True):
             state = CarriedState(model, source.shape[1], S)
@@ -1783,6 +1810,44 @@ def evaluate_swag(model, source, seq_len, posterior, samples, seed=1111, scale=0
                 placed.append((starts, n))
     host = _tokens_to_host(keep, None if betas is None else 1, ("nll", "conf", "entropy", "h_pred", "mi", "pred", "rank", "nll_s"), S)
     return _report_of(host, V, S, bins, betas, order=_text_order(source.shape, placed) if keep_tokens else None)
+
+
+def evaluate_samples(model, source, seq_len, samples, bins=15, temperature=1.0, keep_tokens=False):
+    """evaluate_report's figures under the average of S given weight vectors: ``samples`` is a sgmcmc.SampleBank (SG-MCMC
+    samples, or the members of a deep ensemble: SampleBank.from_checkpoints) or an (S, P) float32 matrix in the layout of
+    FlatBuffers, S = 2..64 -> EvalReport with the Monte-Carlo block and ``per_token["nll_s"]`` under ``keep_tokens``, as
+    evaluate_swag, whose walk this is: evaluate_swag is "draw, then this".  The matrix is moved to the device once and refused
+    beyond swag.DRAW_BYTES.  The model is left as found, by return or by exception.
+
+    Refused: S outside 2..64, a matrix of another width or type, a bank made for another model (swag.PosteriorMismatch), a world
+    size above 1, noise source 'torch'."""
+    from . import sgmcmc as _sgmcmc, swag as _swag
+    who = "evaluate_samples"
+    bank = samples if isinstance(samples, _sgmcmc.SampleBank) else None
+    mat = None if bank is not None else samples
+    if bank is None and (not torch.is_tensor(mat) or mat.dim() != 2 or mat.dtype != torch.float32):
+        raise ops.BayesLMError("%s: samples must be a SampleBank or an (S, P) float32 matrix" % who)
+    S, P = (len(bank), bank.total) if bank is not None else (int(mat.shape[0]), int(mat.shape[1]))
+    if not 2 <= S <= 64:
+        raise ops.BayesLMError("%s: samples must hold 2..64 weight vectors, got %d" % (who, S))
+    if 4 * S * P > _swag.DRAW_BYTES:
+        raise ops.BayesLMError("%s: %d vectors of %d floats are %d bytes (%.2f GiB), beyond the budget of %d bytes: evaluate fewer"
+                               % (who, S, P, 4 * S * P, 4 * S * P / 2.0 ** 30, _swag.DRAW_BYTES))
+
+    def check(m):
+        if bank is not None:
+            bank.check(m)
+        total = m.total if hasattr(m, "flat_param") else _swag.flat_layout(m)[2]
+        if total != P:
+            raise _swag.PosteriorMismatch("total", P, total, "weight vectors", "matrix")
+
+    def draws(flat):
+        check(flat)
+        dev = flat.flat_param.device
+        return bank.to_device(dev) if bank is not None else mat.to(dev).contiguous()
+
+    return _samples_walk(who, model, source, seq_len, S, draws, check, "a weight sample replaces every weight and runs", bins,
+                         temperature, keep_tokens)
 
 
 # ----------------------------------------------------------------------------

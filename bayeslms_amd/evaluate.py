@@ -63,7 +63,15 @@ inf, the model itself) with the lowest loss on ``--fit-laplace-prior-on valid.tx
 prior ... link ... [samples ...]`` and, after a prior fit, ``| fit loss a -> b`` of the fit text; the report gains a ``laplace``
 block, in which an infinite prior precision is written as the string ``"inf"`` (JSON has no number for it).  Refused beside
 these flags: ``--mc-samples``, ``--swag``, ``--cache-window``, the dyneval flags, ``--fit-temperature-on`` and a ``--temperature``
-other than 1.  Without them the line and the report are what they were."""
+other than 1.  Without them the line and the report are what they were.
+
+Sample banks and ensembles.  ``--sample-bank PATH [--bank-samples S]`` evaluates ``--data`` under the average of the latest S
+(default all) weight samples in the bank that ``python -m bayeslms_amd.train --sgmcmc-save PATH`` wrote, ``--ensemble
+a.pt,b.pt,...`` under the average of 2..64 checkpoints of the ``--model-path`` architecture (a deep ensemble; ``--model-path`` may
+be one of them) -- both through engine.evaluate_samples, the walk of evaluate_swag.  ``--temperature`` is honoured.  The summary
+line gains ``| samples kind ... n ...`` and the report a ``samples`` block.  Refused beside either: ``--mc-samples``, ``--swag``,
+the Laplace flags, ``--cache-window``, the dyneval flags and ``--fit-temperature-on``.  Without them the line and the report are
+what they were."""
 import argparse
 import json
 import math
@@ -147,7 +155,49 @@ def build_parser():
     p.add_argument('--laplace-link', type=str, default=None, choices=['probit', 'expexp', 'mc'],
                    help='from logit mean and variance to a distribution (default probit)')
     p.add_argument('--laplace-samples', type=int, default=None, metavar='S', help='with --laplace-link mc: 2..32 logit samples (--mc-seed keys them)')
+    p.add_argument('--sample-bank', type=str, default='', metavar='PATH',
+                   help='evaluate under the average of the weight samples in the bank that train --sgmcmc-save wrote')
+    p.add_argument('--bank-samples', type=int, default=None, metavar='S',
+                   help='with --sample-bank: the latest S vectors of the bank, 2..64 (default: all it holds)')
+    p.add_argument('--ensemble', type=str, default='', metavar='a.pt,b.pt,...',
+                   help='evaluate under the average of 2..64 checkpoints of the --model-path architecture (a deep ensemble); '
+                        '--model-path may be one of them')
     return p
+
+
+def check_samples_args(args):
+    """The refusals of --sample-bank / --ensemble: before any file or device is touched."""
+    if not (args.sample_bank or args.ensemble):
+        if args.bank_samples is not None:
+            raise SystemExit("--bank-samples needs --sample-bank")
+        return
+    if args.sample_bank and args.ensemble:
+        raise SystemExit("--sample-bank and --ensemble exclude each other: one set of weight vectors per run")
+    what = "--sample-bank" if args.sample_bank else "--ensemble"
+    if args.ensemble:
+        if args.bank_samples is not None:
+            raise SystemExit("--bank-samples needs --sample-bank (an ensemble is evaluated whole)")
+        n = len(ensemble_paths(args.ensemble))
+        if not 2 <= n <= 64:
+            raise SystemExit("--ensemble takes 2..64 checkpoints separated by commas (got %d)" % n)
+    elif args.bank_samples is not None and not 2 <= args.bank_samples <= 64:
+        raise SystemExit("--bank-samples must lie in 2..64 (got %d)" % args.bank_samples)
+    if args.mc_samples:
+        raise SystemExit("%s with --mc-samples: the weight vectors are the Monte-Carlo samples of this run" % what)
+    if args.swag:
+        raise SystemExit("%s with --swag: one source of weight samples per run" % what)
+    if args.laplace or args.laplace_fit_on:
+        raise SystemExit("%s with the Laplace flags: the Laplace posterior stands at one set of weights" % what)
+    if args.cache_window is not None:
+        raise SystemExit("%s with --cache-window: the cache runs at the model's own mean weights" % what)
+    if args.dyneval_lr is not None or args.dyneval_decay is not None or args.fit_dyneval_on:
+        raise SystemExit("%s with dynamic evaluation: the two together are not built" % what)
+    if args.fit_temperature_on:
+        raise SystemExit("%s with --fit-temperature-on: fitting a temperature under a bank is not built (--temperature T is honoured)" % what)
+
+
+def ensemble_paths(text):
+    return [p.strip() for p in text.split(",") if p.strip()]
 
 
 def laplace_grid(text):
@@ -316,6 +366,7 @@ def check_cache_args(args):
 
 def check_args(args):
     """Refusals that need neither the input files, the model nor a device."""
+    check_samples_args(args)
     check_cache_args(args)
     check_dyneval_args(args)
     check_swag_args(args)
@@ -350,6 +401,9 @@ def summary_line(rep):
     w = rep.swag
     if w:
         line += " | swag n %d rank %d scale %.6g samples %d" % (w["n"], w["rank"], w["scale"], w["samples"])
+    b = rep.samples
+    if b:
+        line += " | samples kind %s n %d" % (b["kind"], b["n"])
     lp = rep.laplace
     if lp:
         line += " | laplace tokens %d prior %.6g link %s" % (lp["tokens"], lp["prior_precision"], lp["link"])
@@ -415,6 +469,8 @@ def main(argv=None):
     temperature, fit = (1.0 if args.temperature is None else args.temperature), None
     if args.swag:
         return swag_main(args, model, corpus, text, device, temperature)
+    if args.sample_bank or args.ensemble:
+        return samples_main(args, model, corpus, text, device, temperature)
     if args.laplace or args.laplace_fit_on:
         return laplace_main(args, model, corpus, text, device)
     if args.fit_temperature_on:
@@ -485,6 +541,33 @@ def swag_main(args, model, corpus, text, device, temperature):
                                    diag=bool(args.swag_diag), bins=args.bins, temperature=temperature, keep_tokens=bool(args.write_tokens))
     rep.swag = dict(posterior.describe(), scale=scale, diag=bool(args.swag_diag), samples=args.swag_samples, seed=args.mc_seed,
                     path=args.swag)
+    print(summary_line(rep), flush=True)
+    if args.write_report:
+        with open(args.write_report, 'w') as f:
+            json.dump(rep.as_dict(), f)
+    if args.write_tokens:
+        write_tokens(rep, corpus.dictionary.idx2word, args.write_tokens)
+    return rep
+
+
+def samples_main(args, model, corpus, text, device, temperature):
+    """--sample-bank / --ensemble: the report under the average of the bank's weight vectors"""
+    from . import sgmcmc
+    from ._lib import BayesLMError
+    flag, value = ("--sample-bank", args.sample_bank) if args.sample_bank else ("--ensemble", args.ensemble)
+    try:
+        if args.sample_bank:
+            bank = sgmcmc.SampleBank.load(args.sample_bank)
+            bank.check(model)
+            if args.bank_samples is not None:
+                bank = bank.latest(args.bank_samples)
+        else:
+            bank = sgmcmc.SampleBank.from_checkpoints(model, ensemble_paths(args.ensemble))
+        rep = engine.evaluate_samples(model, D.batchify(text, args.batch_size, device), args.seq_len, bank, bins=args.bins,
+                                      temperature=temperature, keep_tokens=bool(args.write_tokens))
+    except BayesLMError as e:
+        raise SystemExit("%s %s: %s" % (flag, value, e))
+    rep.samples = dict(bank.describe(), path=value)
     print(summary_line(rep), flush=True)
     if args.write_report:
         with open(args.write_report, 'w') as f:

@@ -4064,6 +4064,41 @@ def clip_sgd(table, clip, lr, momentum, first, grad_scale=1.0, weight_decay=0.0)
     return table.sq
 
 
+def sqnorm(table):
+    """-> table.sq, the device scalar holding the squared global gradient norm (blm_sqnorm_multi, as clip_sgd runs it)"""
+    L.require_gfx950()
+    table.sq.zero_()
+    calls().blm_sqnorm_multi(ptr(table.grads), ptr(table.sizes), table.n, ptr(table.sq), ptr(table.ws), stream())
+    return table.sq
+
+
+def sgmcmc_update(p, g, sq, clip, lr, sigma, seed=0, step=0, v=None, grad_scale=1.0, weight_decay=0.0, alpha=0.99, damping=1e-5,
+                  stream_id=None):
+    """One SG-MCMC update over flat float32 arrays of one length, in place on ``p`` (and ``v``) (blm_sgmcmc_update, one pass):
+    with c = min(1, clip / (sqrt(sq) grad_scale + 1e-6)) grad_scale and d = c g + weight_decay p,
+      sgld  (``v`` None):  p <- p - lr d + sigma xi
+      psgld:               v <- alpha v + (1 - alpha) d d,  G = 1 / (damping + sqrt(v)),  p <- p - lr G d + sigma sqrt(G) xi
+    xi[i] element i of the Philox normal stream (seed, stream_id = STREAM_SGMCMC, step), i the index into the arrays handed in.
+    ``sq``: the device scalar sqnorm / clip_sgd leave.  sigma = 0 runs the form without the generator.  The defaults of alpha and
+    damping are RMSprop's customary ones and are unmeasured here.  -> p"""
+    arrays = dict(p=p, g=g) if v is None else dict(p=p, g=g, v=v)
+    n = _dyneval_flat("sgmcmc_update", **arrays)
+    if _dyneval_flat("sgmcmc_update", sq=sq) != 1:
+        raise BayesLMError("sgmcmc_update: sq must hold 1 float (the squared gradient norm), got %d" % sq.numel())
+    lr, sigma, weight_decay = (_dyneval_rate("sgmcmc_update", k, x) for k, x in (("lr", lr), ("sigma", sigma),
+                                                                                 ("weight_decay", weight_decay)))
+    clip, alpha, damping = float(clip), float(alpha), float(damping)
+    if not clip > 0.0:
+        raise BayesLMError("sgmcmc_update: clip = %r must be > 0" % clip)
+    if v is not None and not (0.0 <= alpha < 1.0 and damping > 0.0):
+        raise BayesLMError("sgmcmc_update: alpha = %r must lie in [0, 1) and damping = %r be > 0" % (alpha, damping))
+    L.require_gfx950()
+    r = L.rng(seed, L.STREAM_SGMCMC if stream_id is None else stream_id, int(step))
+    calls().blm_sgmcmc_update(ptr(p), ptr(g), ptr(v), ptr(sq), n, clip, lr, float(grad_scale), weight_decay, sigma, alpha, damping,
+                              C.byref(r), stream())
+    return p
+
+
 def adam_step(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
     """In-place torch.optim.Adam update of one tensor (architect.py:33); ``step`` counts from 1."""
     L.require_gfx950()

@@ -64,11 +64,34 @@ def coefficients(scale, k_live, diag=False):
 
 
 class PosteriorMismatch(BayesLMError):
-    """A posterior was made for another model; ``field`` names the first manifest field that differs."""
+    """A posterior (or a bank of weight vectors: ``what`` / ``owner`` name it) was made for another model; ``field`` names the first
+    manifest field that differs."""
 
-    def __init__(self, field, found, wanted):
+    def __init__(self, field, found, wanted, what="swag posterior", owner="posterior"):
         self.field, self.found, self.wanted = field, found, wanted
-        super().__init__("swag posterior: field %r differs: the posterior has %r, this model has %r" % (field, found, wanted))
+        super().__init__("%s: field %r differs: the %s has %r, this model has %r" % (what, field, owner, found, wanted))
+
+
+def check_manifest(total, manifest, model_or_flat, what="swag posterior", owner="posterior"):
+    """Refuses what was made for another model (PosteriorMismatch names the first manifest field that differs).  A model is
+    compared by names, shapes and offsets; an engine.FlatBuffers, which knows no names, by shapes and offsets."""
+    if hasattr(model_or_flat, "flat_param"):
+        flat = model_or_flat
+        theirs = {"total": flat.total, "names": None, "shapes": [list(p.shape) for p in flat.params], "offsets": list(flat.offsets)}
+    else:
+        theirs = manifest_of(model_or_flat)
+    if theirs["total"] != total:
+        raise PosteriorMismatch("total", total, theirs["total"], what, owner)
+    if manifest is None:
+        return
+    for field in ("names", "shapes", "offsets"):
+        a, b = manifest[field], theirs[field]
+        if b is None or a == b:
+            continue
+        if len(a) != len(b):
+            raise PosteriorMismatch("len(%s)" % field, len(a), len(b), what, owner)
+        i = next(i for i, (x, y) in enumerate(zip(a, b)) if x != y)
+        raise PosteriorMismatch("%s[%d]" % (field, i), a[i], b[i], what, owner)
 
 
 class SwagPosterior:
@@ -136,24 +159,7 @@ class SwagPosterior:
     def check(self, model_or_flat):
         """Refuses a posterior made for another model (PosteriorMismatch names the first manifest field that differs).  A model is
         compared by names, shapes and offsets; an engine.FlatBuffers, which knows no names, by shapes and offsets."""
-        if hasattr(model_or_flat, "flat_param"):
-            flat = model_or_flat
-            theirs = {"total": flat.total, "names": None, "shapes": [list(p.shape) for p in flat.params], "offsets": list(flat.offsets)}
-        else:
-            theirs = manifest_of(model_or_flat)
-        if theirs["total"] != self.total:
-            raise PosteriorMismatch("total", self.total, theirs["total"])
-        mine = self.manifest
-        if mine is None:
-            return
-        for field in ("names", "shapes", "offsets"):
-            a, b = mine[field], theirs[field]
-            if b is None or a == b:
-                continue
-            if len(a) != len(b):
-                raise PosteriorMismatch("len(%s)" % field, len(a), len(b))
-            i = next(i for i, (x, y) in enumerate(zip(a, b)) if x != y)
-            raise PosteriorMismatch("%s[%d]" % (field, i), a[i], b[i])
+        check_manifest(self.total, self.manifest, model_or_flat)
 
     def _slices(self, model):
         self.check(model)

@@ -141,7 +141,109 @@ def build_parser():
     p.add_argument('--swag-lr', type=float, default=None, metavar='LR',
                    help='new, optional (with --swag-save): from epoch E on the learning rate is this constant and the halving rule is '
                         'suspended (default: the schedule is untouched)')
+    p.add_argument('--sgmcmc-save', type=str, default='', metavar='PATH',
+                   help='new, optional: from epoch --sgmcmc-start on, replace clip + SGD by a stochastic-gradient MCMC update over all '
+                        'weights (bayeslms_amd/sgmcmc.py; Welling and Teh 2011, Li et al. 2016), collect weight samples and write the '
+                        'bank to PATH at the end of training; bayeslms_amd.evaluate --sample-bank PATH reads it.  Models without '
+                        'variational sites, single process only')
+    p.add_argument('--sgmcmc-lr', type=float, default=None, metavar='LR',
+                   help='new, required with --sgmcmc-save: the rate of the sampler on the mean loss (eps N / 2 for a Langevin step eps '
+                        'over N training tokens); no default can be right')
+    p.add_argument('--sgmcmc-rule', type=str, default=None, choices=['sgld', 'psgld'],
+                   help='new, optional (with --sgmcmc-save): sgld (the default), or psgld, preconditioned by an RMSprop second moment')
+    p.add_argument('--sgmcmc-start', type=int, default=None, metavar='E',
+                   help='new, optional (with --sgmcmc-save): the first epoch, 1-based, that samples (default 1); earlier epochs are '
+                        'ordinary SGD, the burn-in.  From epoch E on the halving rule is suspended')
+    p.add_argument('--sgmcmc-temperature', type=float, default=None, metavar='T',
+                   help='new, optional (with --sgmcmc-save): temperature of the chain, >= 0 (default 1: the posterior)')
+    p.add_argument('--sgmcmc-prior-precision', type=float, default=None, metavar='TAU',
+                   help='new, optional (with --sgmcmc-save): precision of the Gaussian prior, >= 0 (default 1; unmeasured here)')
+    p.add_argument('--sgmcmc-every', type=int, default=None, metavar='N',
+                   help='new, optional (with --sgmcmc-save): 0 = one sample at each epoch\'s end (the default), else one every N '
+                        'optimisation steps from epoch E on')
+    p.add_argument('--sgmcmc-keep', type=int, default=None, metavar='K',
+                   help='new, optional (with --sgmcmc-save): the bank keeps the latest K samples, 2..64 (default 16)')
+    p.add_argument('--sgmcmc-cycles', type=int, default=None, metavar='M',
+                   help='new, optional (with --sgmcmc-save): M > 0 = cyclical SG-MCMC (Zhang et al. 2020): the steps from epoch E on '
+                        'in M cosine cycles starting at --sgmcmc-lr (default 0: a constant rate, noise throughout)')
+    p.add_argument('--sgmcmc-explore', type=float, default=None, metavar='BETA',
+                   help='new, optional (with --sgmcmc-cycles): the share of each cycle run without noise and without collecting, '
+                        'in [0, 1) (default 0.8)')
+    p.add_argument('--sgmcmc-seed', type=int, default=None, metavar='N',
+                   help='new, optional (with --sgmcmc-save): the key of the chain\'s noise (default --seed)')
     return p
+
+
+SGMCMC_FLAGS = ("sgmcmc_save", "sgmcmc_lr", "sgmcmc_rule", "sgmcmc_start", "sgmcmc_temperature", "sgmcmc_prior_precision",
+                "sgmcmc_every", "sgmcmc_keep", "sgmcmc_cycles", "sgmcmc_explore", "sgmcmc_seed")
+
+
+def variational_site_flag(args):
+    """The flag that gives the model of ``args`` a variational site, as text, or None"""
+    if args.uncertainty == 'none':
+        return None
+    if args.model == 'Transformer':
+        pos = {'Bayesian': 'T_bayes_pos', 'Gaussian': 'T_gauss_pos', 'Variational': 'T_v_pos'}.get(args.uncertainty)
+    else:
+        pos = {'Bayesian': 'L_bayes_pos', 'Gaussian': 'L_gauss_pos', 'Variational': 'L_v_pos'}.get(args.uncertainty)
+    return "--uncertainty %s" % args.uncertainty + ("" if pos is None else " --%s %s" % (pos, getattr(args, pos)))
+
+
+def take_sgmcmc_args(args, world, swag_on):
+    """The --sgmcmc-* flags, taken OUT of ``args`` (a run without them prints the configuration it printed before there were any)
+    and refused before anything is loaded -> a namespace (save, lr, rule, start, temperature, prior_precision, every, keep, cycles,
+    explore, seed), or None without --sgmcmc-save."""
+    got = {f: getattr(args, f) for f in SGMCMC_FLAGS}
+    for f in SGMCMC_FLAGS:
+        delattr(args, f)
+    if not got["sgmcmc_save"]:
+        for f in SGMCMC_FLAGS[1:]:
+            if got[f] is not None:
+                raise SystemExit("--%s needs --sgmcmc-save" % f.replace("_", "-"))
+        return None
+
+    def of(name, default):
+        return default if got[name] is None else got[name]
+
+    w = argparse.Namespace(save=got["sgmcmc_save"], lr=got["sgmcmc_lr"], rule=of("sgmcmc_rule", "sgld"), start=of("sgmcmc_start", 1),
+                           temperature=of("sgmcmc_temperature", 1.0), prior_precision=of("sgmcmc_prior_precision", 1.0),
+                           every=of("sgmcmc_every", 0), keep=of("sgmcmc_keep", 16), cycles=of("sgmcmc_cycles", 0),
+                           explore=of("sgmcmc_explore", 0.8), seed=of("sgmcmc_seed", args.seed))
+    if w.lr is None:
+        raise SystemExit("--sgmcmc-save needs --sgmcmc-lr: the rate of the sampler has no default that can be right")
+    if not (math.isfinite(w.lr) and w.lr > 0):
+        raise SystemExit("--sgmcmc-lr must be positive and finite (got %r)" % w.lr)
+    if swag_on:
+        raise SystemExit("--sgmcmc-save with --swag-save: SWAG fits the SGD iterates, and under a sampler there are none")
+    if args.distill_from:
+        raise SystemExit("--sgmcmc-save with --distill-from: sampling a student's weights is not built")
+    if world > 1:
+        raise SystemExit("--sgmcmc-save runs in a single process: data-parallel sampling is not built (world size %d)" % world)
+    if (args.noise_source or os.environ.get("BLM_NOISE_SOURCE", "philox")) == "torch":
+        raise SystemExit("--sgmcmc-save with --noise-source torch: the parity mode follows the reference's run, which has no sampler")
+    site = variational_site_flag(args)
+    if site is not None:
+        raise SystemExit("--sgmcmc-save with %s: that site already carries a variational posterior, and two posteriors over the "
+                         "same weights are not built; sample a model of --uncertainty none" % site)
+    if w.start < 1:
+        raise SystemExit("--sgmcmc-start is a 1-based epoch (got %d)" % w.start)
+    if w.start > args.epochs:
+        raise SystemExit("--sgmcmc-start %d lies beyond --epochs %d: nothing would be sampled" % (w.start, args.epochs))
+    if not (math.isfinite(w.temperature) and w.temperature >= 0):
+        raise SystemExit("--sgmcmc-temperature must be finite and >= 0 (got %r)" % w.temperature)
+    if not (math.isfinite(w.prior_precision) and w.prior_precision >= 0):
+        raise SystemExit("--sgmcmc-prior-precision must be finite and >= 0 (got %r)" % w.prior_precision)
+    if w.every < 0:
+        raise SystemExit("--sgmcmc-every must be 0 (each epoch's end) or a positive number of steps (got %d)" % w.every)
+    if not 2 <= w.keep <= 64:
+        raise SystemExit("--sgmcmc-keep must lie in 2..64 (got %d)" % w.keep)
+    if w.cycles < 0:
+        raise SystemExit("--sgmcmc-cycles must be >= 0 (got %d)" % w.cycles)
+    if got["sgmcmc_explore"] is not None and not w.cycles:
+        raise SystemExit("--sgmcmc-explore needs --sgmcmc-cycles")
+    if not 0 <= w.explore < 1:
+        raise SystemExit("--sgmcmc-explore must lie in [0, 1) (got %r)" % w.explore)
+    return w
 
 
 SWAG_FLAGS = ("swag_save", "swag_start", "swag_every", "swag_rank", "swag_lr")
@@ -395,6 +497,7 @@ def main(argv=None, history=None):
     history.update({"interval_loss": [], "valid_loss": [], "halved_epochs": [], "test_loss": None, "ms_per_batch": []})
     world = int(os.environ.get("WORLD_SIZE", "1"))
     swag_args = take_swag_args(args, world)
+    sg_args = take_sgmcmc_args(args, world, swag_args is not None)
     check_report_args(args, world)
     teacher_shape = check_distill_args(args, world)
     teacher_sd = load_teacher_state(args) if teacher_shape is not None else None
@@ -522,7 +625,33 @@ def main(argv=None, history=None):
             swag_args.start, "every %d steps" % swag_args.every if swag_args.every else "at each epoch's end", swag_args.rank,
             "" if swag_args.lr is None else ", lr %g held from there" % swag_args.lr, swag_args.save))
 
+    sampler = bank = None
+    if sg_args is not None:
+        from . import sgmcmc, swag as _swag
+        steps_per_epoch = len(range(0, train_data.size(0) - 1, args.seq_len))
+        n_tokens = (train_data.size(0) - 1) * train_data.size(1)  # the target tokens one epoch walks
+        schedule = None
+        try:
+            if sg_args.cycles:
+                schedule = sgmcmc.CyclicalSchedule((args.epochs - sg_args.start + 1) * steps_per_epoch, sg_args.cycles, sg_args.lr,
+                                                   sg_args.explore)
+            sampler = sgmcmc.Sampler(sg_args.rule, sg_args.lr, n_tokens, sg_args.temperature, sg_args.prior_precision,
+                                     seed=sg_args.seed, schedule=schedule)
+            bank = sgmcmc.SampleBank(trainer.flat.total, _swag.manifest_of(model), sg_args.keep, sampler.settings())
+            collector = sgmcmc.SampleCollector(trainer, bank, sg_args.start, sg_args.every)
+        except ops.BayesLMError as e:
+            raise SystemExit("--sgmcmc-save: %s" % e)
+        say("sgmcmc: %s from epoch %d, lr %g, temperature %g, prior precision %g over %d tokens (weight decay %g), %s, "
+            "sampling %s, keeping %d, into %s" % (
+                sg_args.rule, sg_args.start, sg_args.lr, sg_args.temperature, sg_args.prior_precision, n_tokens, sampler.weight_decay,
+                "%d cycles, exploring %g of each" % (sg_args.cycles, sg_args.explore) if sg_args.cycles else "a constant rate",
+                "every %d steps" % sg_args.every if sg_args.every else "at each epoch's end", sg_args.keep, sg_args.save))
+
     def swag_collected(epoch, n):
+        if n is not None and bank is not None:
+            say('| sgmcmc n {:d} | epoch {:3d} | step {:d} | lr {:.6g} | sigma {:.6g} |'.format(
+                n, epoch, trainer.step_no, sampler.last_lr, sampler.last_sigma))
+            return
         if n is not None:
             say('| swag n {:d} | epoch {:3d} | step {:d} | rank {:d} | k_live {:d} |'.format(
                 n, epoch, trainer.step_no, collector.posterior.rank, collector.posterior.k_live))
@@ -566,6 +695,8 @@ def main(argv=None, history=None):
                 history["interval_loss"].append(cur)
                 elapsed = time.time() - start
                 history["ms_per_batch"].append(elapsed * 1000 / args.log_interval)
+                if trainer.sampler is not None and trainer.sampler.last_lr is not None:
+                    lr = trainer.sampler.last_lr  # the rate the sampler applied to this step (a cyclical schedule moves it)
                 line = ('| epoch {:3d} | {:5d}/{:5d} batches | lr {:02.3f} | ms/batch {:5.2f} | loss {:5.2f} | '
                         'kl_loss {:5.4} | ppl {:8.2f}'.format(epoch, batch, len(train_data) // args.seq_len, lr,
                                                               elapsed * 1000 / args.log_interval, cur,
@@ -586,10 +717,16 @@ def main(argv=None, history=None):
     try:
         for epoch in range(1, args.epochs + 1):
             t0 = time.time()
-            held = collector is not None and swag_args.lr is not None and collector.active(epoch)
-            if held:  # a constant rate from --swag-start on; the halving rule is suspended below
+            sampling = sampler is not None and collector.active(epoch)
+            if sampling and trainer.sampler is None:  # the burn-in is over: the sampler's update from this epoch on
+                try:
+                    trainer.set_sampler(sampler)
+                except ops.BayesLMError as e:
+                    raise SystemExit("--sgmcmc-save: %s" % e)
+            held = sampling or (swag_args is not None and swag_args.lr is not None and collector.active(epoch))
+            if held and not sampling:  # a constant rate from --swag-start on; the halving rule is suspended below
                 trainer.lr = swag_args.lr
-            train_epoch(epoch, swag_args.lr if held else sched.lr)
+            train_epoch(epoch, (sg_args.lr if sampling else swag_args.lr) if held else sched.lr)
             if collector is not None:
                 swag_collected(epoch, collector.epoch_end(epoch))
             if world > 1:
@@ -624,7 +761,13 @@ def main(argv=None, history=None):
         say('-' * 89)
         say('Exiting from training early')
 
-    if collector is not None:
+    if bank is not None:
+        if len(bank) < 1:
+            say("sgmcmc: no sample was collected: %s is not written" % sg_args.save)
+        else:
+            bank.save(sg_args.save)
+            say("sgmcmc: wrote %s (%d samples of %d seen, %s)" % (sg_args.save, len(bank), bank.seen, sg_args.rule))
+    elif collector is not None:
         if collector.posterior.n < 1:
             say("swag: no iterate was collected: %s is not written" % swag_args.save)
         else:

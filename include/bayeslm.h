@@ -43,6 +43,7 @@ typedef enum blm_status {
 #define BLM_STREAM_LRT     0x30000000u  /* + site id: the pre-activation noise of local reparameterisation */
 #define BLM_STREAM_SWAG    0x40000000u  /* + 0: a SWAG sample's diagonal noise, + 1: its low-rank noise; step = sample id */
 #define BLM_STREAM_LAPLACE 0x50000000u  /* the logit noise of the last-layer Laplace predictive; step = sample id */
+#define BLM_STREAM_SGMCMC  0x60000000u  /* the Langevin noise of an SG-MCMC weight update; step = optimisation step */
 
 typedef struct blm_rng {
   uint64_t seed;    /* Philox key                                             */
@@ -712,6 +713,38 @@ int blm_swag_sample(float* out, int64_t ld_out, const float* mean, const float* 
  * < V, S outside 1..BLM_SWAG_SAMPLES_MAX, s outside [0, S), extents too large.  rows == 0: BLM_OK. */
 int blm_logp_avg_accum(const float* logits, int64_t ld, float* acc, int64_t ld_acc, const int64_t* targets, int rows, int V, int s,
                        int S, float* hsum, float* nll_s, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Stochastic-gradient MCMC (csrc/sgmcmc.hip; bayeslms_amd/sgmcmc.py): one weight update of stochastic-gradient Langevin
+ * dynamics (Welling and Teh, ICML 2011) or of its RMSprop-preconditioned form (Li, Chen, Carlson, Carin, AAAI 2016; on LSTM
+ * language models: Gan, Li, Chen, Pu, Su, Carin, ACL 2017) over n floats of weights in one flat buffer.
+ *
+ * Per element i, in fp32, in exactly this order and without contraction (every product and sum below is one rounded operation,
+ * evaluated left to right inside the parentheses shown):
+ *   c  = min(1, clip / (sqrt(sq) * grad_scale + 1e-6)) * grad_scale          (blm_clip_sgd_multi's clip; once per lane)
+ *   d  = (c * g[i]) + (weight_decay * p[i])
+ *   sgld   (v == NULL):  p[i] = (p[i] - lr * d) + sigma * xi[i]
+ *   psgld  (v != NULL):  v[i] = (alpha * v[i]) + ((1 - alpha) * d) * d,      1 - alpha rounded once by the launcher
+ *                        G    = 1 / (damping + sqrt(v[i]))                   with the NEW v[i]
+ *                        p[i] = (p[i] - (lr * G) * d) + (sigma * sqrt(G)) * xi[i]
+ * sqrt and the division are correctly rounded.  xi[i] is element i of the Philox normal stream (rng.seed, rng.stream, rng.step):
+ * the values blm_philox_normal writes for that blm_rng.  By convention rng.stream = BLM_STREAM_SGMCMC and rng.step is the
+ * optimisation step.  i is the index into the array handed in, whatever the launch geometry and whichever path an element
+ * takes: 16-byte aligned arrays take 16-byte loads and stores over the body and a scalar tail, any other alignment of a float is
+ * ACCEPTED and takes the scalar path whole, and an element gets the same bits either way.  sigma == 0 adds no noise term at all
+ * (the generator does not run, rng may be NULL), so with weight_decay = 0 the sgld rule is blm_clip_sgd_multi at momentum 0 up
+ * to that kernel's contraction.  An entry with g = 0, p = 0 (and v = 0) moves by the noise alone: G = 1 / damping there.
+ *
+ * The term Gamma(theta) of Li et al. (the derivative of the preconditioner, their eq. 3) is DROPPED, as in their practical
+ * algorithm, which argues that the term is small for alpha near 1.  Clipping biases the chain as well.
+ *
+ * sq is the DEVICE scalar blm_sqnorm_multi leaves (the squared norm of g before grad_scale).  p, g and v must not overlap.
+ * No atomics and no reductions: the same bits in every run.
+ * BLM_ERR_INVALID, before any launch: NULL p, g or sq; n outside 0..2^40; clip not > 0; lr, sigma or weight_decay negative or
+ * not finite; with v: alpha outside [0, 1) or damping not > 0; rng == NULL with sigma > 0.  n == 0: BLM_OK.
+ * -------------------------------------------------------------------------- */
+int blm_sgmcmc_update(float* p, const float* g, float* v, const float* sq, int64_t n, float clip, float lr, float grad_scale,
+                      float weight_decay, float sigma, float alpha, float damping, const blm_rng* rng, void* stream);
 
 /* --------------------------------------------------------------------------
  * Last-layer Laplace posterior for the decoder (csrc/laplace.hip; bayeslms_amd/laplace.py; MacKay 1992; Kristiadi, Hein, Hennig
